@@ -13,6 +13,12 @@ then every rank takes G / N images (strong scaling; BASELINE config 3 = --global
 Rank 0 prints ONE JSON line.  For N > 1 the weak-scaling line is the headline and a `strong_gb32` object carries the
 fixed-global-batch-32 measurement (ms/step, images/s, exposed all-reduce time) of the same ranks.
 
+A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step`, ...).  Every other leg --
+the global-batch-32 and batch-4 legs, the per-kernel roofline profile, the sustained leg, inference, the loader and CPU
+baselines, Dice vs ref -- runs only with --full (where the --no-* options switch single legs off again).  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs); the inputs and the initial weights are seeded, so
+two builds run with the same arguments can be compared output for output.
+
 `python bench.py --gpus N` without a torch.distributed environment starts the N ranks ITSELF (fresh child processes, one
 per GPU, rendezvous on 127.0.0.1) before anything in this process has touched the GPU, relays rank 0's JSON line and
 exits with the worst rank's code; under `python -m torch.distributed.run ... bench.py --gpus N` (the driver's form) it is
@@ -74,7 +80,18 @@ def parse():
                     help="force backward-weights onto a stream of its own (default: TrainStepper decides per step -- on for bf16 steps "
                          "of >= 2^20 pixels per process: +1.5 %% at batch 8, DESIGN.md)")
     ap.add_argument("--no-side-stream", action="store_true", help="force one stream (A/B runs)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (global-batch-32 and batch-4 legs, per-kernel roofline profile, "
+                         "sustained leg, inference, loader and CPU baselines); the --no-* options above switch single legs off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (logits, loss terms, gradient norm) and a fixed sample of the "
+                         "updated parameters as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run sets up, warms up, times the steps and prints the headline line: every other leg is --full's
+        args.no_strong_leg = args.no_kernel_profile = args.no_b4_leg = args.no_sustained = True
+        args.no_inference = args.no_cpu_baseline = True
+    return args
 
 
 def cpu_baseline(size: int):
@@ -309,6 +326,32 @@ def loader_throughput(dev, B: int, S: int, amp: bool):
             "host_cores": 1, "bit_equal": same}
 
 
+def _capped(t: torch.Tensor, limit_bytes: int, seed: int) -> torch.Tensor:
+    """`t` as float32 when it fits in `limit_bytes`, else a fixed seeded sample of its elements (sorted flat indices, 1-D)."""
+    t = t.detach().float()
+    k = limit_bytes // 4
+    if t.numel() <= k:
+        return t
+    import numpy as np
+    idx = np.sort(np.random.default_rng(seed).choice(t.numel(), k, replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(out_dir: str, terms, model) -> None:
+    """--dump-outputs: what the last timed step handed back (its terms: logits, every loss term, the gradient norm) and what it
+    left in the model (all parameters, the BatchNorm running statistics) as DIR/<name>.npy in float32.  At most 32 MiB of logits
+    and 16 MiB of parameters: a larger tensor is written as a fixed seeded sample of its elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, t in terms.items():
+        arrays[name] = _capped(torch.as_tensor(t), 32 << 20, 0)
+    arrays["parameters"] = _capped(torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]), 16 << 20, 1)
+    arrays["bn_running_stats"] = torch.cat([b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()])
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -411,6 +454,8 @@ def main():
     images, masks = make_batch(B, 1 + rank)
     elapsed, exposed, last = measure(images, masks, args.steps, args.warmup)
     loss = float(last["loss"].detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)      # before any --full leg steps the same model again
 
     def exposed_stats(ex):
         return {"exposed_allreduce_ms_per_step": round(sum(ex) / max(len(ex), 1), 4) if ex else None,

@@ -4,7 +4,7 @@
 VAR=$1; OUT=gpurun_out/$2; shift 2
 mkdir -p $OUT
 for i in 1 2; do for f in 0 1; do
-  env $VAR=$f python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-inference --no-sustained "$@" > $OUT/ab_${f}_${i}.json 2> $OUT/ab_${f}_${i}.err
+  env $VAR=$f python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-inference --no-sustained "$@" > $OUT/ab_${f}_${i}.json 2> $OUT/ab_${f}_${i}.err
   python - <<PY
 import json
 j = json.load(open("$OUT/ab_${f}_${i}.json"))

@@ -3,7 +3,7 @@
 OUT=gpurun_out/$1; mkdir -p $OUT
 A=$2; B=$3; N=${4:-3}
 for i in $(seq 1 $N); do for v in $A $B; do
-  UH_LIB_PATH=$PWD/scratch/ab/lib_$v.so python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-inference --no-sustained > $OUT/${v}_${i}.json 2> $OUT/${v}_${i}.err
+  UH_LIB_PATH=$PWD/scratch/ab/lib_$v.so python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-inference --no-sustained > $OUT/${v}_${i}.json 2> $OUT/${v}_${i}.err
   python - <<PY
 import json
 j = json.load(open("$OUT/${v}_${i}.json"))

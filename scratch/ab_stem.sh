@@ -3,7 +3,7 @@
 OUT=gpurun_out/$1; mkdir -p $OUT
 for i in 1 2; do for v in stored valu mfma; do
   case $v in stored) E="UH_STEM_RECOMPUTE=0";; valu) E="UH_STEM_VALU=1";; mfma) E="UH_X=0";; esac
-  env $E python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-inference --no-sustained > $OUT/${v}_${i}.json 2> $OUT/${v}_${i}.err
+  env $E python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-inference --no-sustained > $OUT/${v}_${i}.json 2> $OUT/${v}_${i}.err
   python - <<PY
 import json
 j = json.load(open("$OUT/${v}_${i}.json"))

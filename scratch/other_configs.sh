@@ -1,7 +1,7 @@
 #!/bin/bash
 # The other BASELINE configurations / batch sizes on the current binary (one gpurun call).   scratch/other_configs.sh <outdir>
 OUT=gpurun_out/$1; mkdir -p $OUT
-run() { name=$1; shift; python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-inference "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "$name FAILED: $(tail -2 $OUT/$name.err)";
+run() { name=$1; shift; python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-inference "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "$name FAILED: $(tail -2 $OUT/$name.err)";
   python - <<PY
 import json
 try:

@@ -37,3 +37,36 @@ def test_more_ranks_than_devices_is_refused():
         pytest.skip("machine has several GPUs")
     r = _run(["--gpus", "2"])
     assert r.returncode != 0 and "--share-gpu" in r.stderr
+
+
+def test_plain_run_leaves_every_extra_leg_to_full(monkeypatch):
+    """`bench.py --steps K --warmup W` times the steps and nothing else; --full turns every leg on again and the --no-* options
+    still switch single legs off there."""
+    import bench
+    legs = ("no_strong_leg", "no_kernel_profile", "no_b4_leg", "no_sustained", "no_inference", "no_cpu_baseline")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert all(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-sustained", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.no_sustained and a.dump_outputs == "out"
+    assert not any(getattr(a, k) for k in legs if k != "no_sustained")
+
+
+def test_dump_outputs_writes_float32_and_samples_large_tensors_the_same_way(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Conv2d(1, 4, 3), torch.nn.BatchNorm2d(4))
+    big = torch.randn(9 << 20)                                         # 36 MiB of float32: above the 32 MiB share of logits
+    terms = {"loss": torch.tensor(1.5, dtype=torch.bfloat16), "logits": big, "grad_norm": torch.tensor(0.25)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), terms, model)
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"loss.npy", "logits.npy", "grad_norm.npy", "parameters.npy", "bn_running_stats.npy"}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert float(got["loss.npy"]) == 1.5 and got["parameters.npy"].size == sum(p.numel() for p in model.parameters())
+    assert got["logits.npy"].size == (32 << 20) // 4 and np.isin(got["logits.npy"][:100], big.numpy()).all()
+    assert np.array_equal(got["logits.npy"], np.load(tmp_path / "b" / "logits.npy"))     # a fixed sample

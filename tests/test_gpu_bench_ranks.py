@@ -25,7 +25,8 @@ def _bench(args, timeout=360):       # (below the GPU box's 420 s silence limit:
     return json.loads(lines[0])
 
 
-COMMON = ["--steps", "2", "--warmup", "1", "--size", "128", "--no-cpu-baseline", "--no-inference", "--sustained-seconds", "0.05"]
+# (--full: the global-batch-32, batch-4 and sustained legs and the kernel profile are checked here; a plain run times the steps only)
+COMMON = ["--full", "--steps", "2", "--warmup", "1", "--size", "128", "--no-cpu-baseline", "--no-inference", "--sustained-seconds", "0.05"]
 
 
 def test_one_rank_line_is_unchanged():
@@ -86,7 +87,7 @@ def test_config5_recipe_through_the_two_rank_launcher():
     global batch 16), at two ranks over gloo on the test GPU: the line names the config, carries the convT model's gradient
     payload (124.15 MB) and the exposed all-reduce time.  Unmeasured over RCCL on this pool (one-GPU boxes)."""
     out = _bench(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--convt", "--fp32", "--cc-loss", "--global-batch", "16",
-                  "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-inference", "--sustained-seconds", "0.05"])
+                  "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-inference", "--sustained-seconds", "0.05"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["dtype"] == "f32"
     assert out["config"]["baseline_config"].startswith("configs[4]"), out["config"]
     assert out["config"]["global_batch"] == 16 and out["config"]["per_gpu_batch"] == 8
@@ -100,7 +101,7 @@ def test_config5_recipe_through_the_two_rank_launcher():
 def test_config3_strong_leg_with_sync_bn_through_the_two_rank_launcher():
     """BASELINE config 3's workload (global batch 32 over the ranks, bf16, bilinear) with global-batch BatchNorm statistics, at two
     ranks over gloo on the test GPU: names the config, 69.05 MB of gradients per step, SyncBN stated in the line."""
-    out = _bench(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--global-batch", "32", "--sync-bn",
+    out = _bench(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--global-batch", "32", "--sync-bn", "--full",
                   "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-inference", "--sustained-seconds", "0.05"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["dtype"] == "bf16"
     assert out["config"]["baseline_config"].startswith("configs[2]"), out["config"]
@@ -117,3 +118,23 @@ def test_two_ranks_over_rccl():
     out = _bench(["--gpus", "2"] + COMMON)
     assert out["n_gpus"] == 2 and out["collective"]["world"] == 2 and out["collective"]["backend"] == "nccl"
     assert out["strong_gb32"]["global_batch"] == 32
+
+
+def test_plain_run_times_the_steps_only_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full the line carries the headline alone (no extra leg ran); --dump-outputs writes the last timed step's terms
+    and the updated parameters as float32 .npy files, well under 64 MB."""
+    import numpy as np
+    out = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "128", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+    assert out["unit"] == "images/sec" and out["dtype"] == "bf16" and out["metric"].startswith("images/sec")
+    assert out["roofline"] is None and out["kernels"] is None and out["sustained"] is None
+    for key in ("strong_gb32", "per_gpu_batch4", "inference", "loader", "cpu_baseline"):
+        assert key not in out, key
+    files = {f: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    for name in ("logits", "loss", "bce", "dice", "boundary", "grad_norm", "parameters", "bn_running_stats"):
+        assert files[name + ".npy"].dtype == np.float32, name
+        assert np.isfinite(files[name + ".npy"]).all(), name
+    assert files["logits.npy"].shape == (8, 1, 128, 128)
+    assert abs(float(files["loss.npy"]) - out["loss"]) <= 1e-5 * max(1.0, abs(out["loss"]))
+    assert files["parameters.npy"].size == (16 << 20) // 4          # a fixed sample of the 17.3 M parameters
+    assert sum(os.path.getsize(tmp_path / f) for f in files) < 64e6
