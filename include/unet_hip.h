@@ -285,6 +285,24 @@ int uh_bn_relu_upsample2x_fwd(const void* x, int ldx, const float* scale, const 
 int uh_upsample2x_bwd(const void* dy, int lddy, void* dx, int lddx, int B, int h, int w, int C,
                       int Ho, int Wo, int pad_top, int pad_left, int dt, uh_stream stream);
 
+/* ---- SpatialAttention + the gated skip of Up(use_attention=True)  (unet_parts.py:39-60,91-92) ---------------------
+ * x [B,H,W,C] in dt with pixel stride ldx; w = the conv1 weight [1][2][k][k] fp32 contiguous (k = 3 or 7, zero padding k/2).
+ * Forward: pool = fp32 [B*H*W][2] (channel mean, channel max; 8-byte aligned), amax = int32 [B*H*W] (the FIRST maximal
+ * channel, which receives the max's gradient as torch.max(dim=1) routes it), a = fp32 [B*H*W] the sigmoid map; y (may be
+ * NULL: the standalone module) = x * a in dt, rounded once, pixel stride ldy.
+ * Backward: exactly one of dy (the gate: gradient of y, pixel stride lddy; x is then needed) and ga (the standalone map:
+ * fp32 [B*H*W] gradient of a) is given.  ws = fp32 workspace of 3*B*H*W floats, 8-byte aligned (the gradient of pool, then
+ * g_a * a * (1 - a)); dx = dy*a + d(mean)/dx + d(max)/dx in dt (pixel stride lddx); dw = fp32 [2*k*k], summed over
+ * per-workgroup rows dw_partials = fp32 [nblk][2*k*k] with nblk >= uh_spatial_attn_dw_nblk(B, H, W) in a fixed order
+ * (bit-identical between runs).  B <= 65535. */
+int uh_spatial_attn_dw_nblk(int B, int H, int W);
+int uh_spatial_attn_fwd(const void* x, int ldx, const float* w, int k, float* pool, int* amax, float* a, void* y,
+                        int ldy, int B, int H, int W, int C, int dt, uh_stream stream);
+int uh_spatial_attn_bwd(const void* dy, int lddy, const float* ga, const void* x, int ldx, const float* w, int k,
+                        const float* pool, const int* amax, const float* a, float* ws, void* dx, int lddx,
+                        float* dw, float* dw_partials, int nblk, int B, int H, int W, int C, int dt,
+                        uh_stream stream);
+
 /* ---- nn.ConvTranspose2d(Cin, Cout, 2, 2) + F.pad  (unet_parts.py:73,85-88) -----------------
  * w is the parameter itself: [Cin][Cout][2][2] fp32 contiguous; bias [Cout] fp32. */
 int uh_convt2x2_fwd(const void* x, int ldx, const float* w, const float* bias, void* y, int ldy,

@@ -1,6 +1,7 @@
 """MI355X-native UNet segmentation train-step path (hand-written HIP kernels behind the reference's
 nn.Module / loss-function surface).  See DESIGN.md and include/unet_hip.h."""
-from .unet import UNet, UNet_S, UNet_T, UNetDepth, DoubleConv, Down, Up, OutConv  # noqa: F401
+from .unet import UNet, UNet_S, UNet_SA, UNet_T, UNetDepth, DoubleConv, Down, Up, OutConv  # noqa: F401
+from .unet import AttentionUp, SpatialAttention  # noqa: F401
 from .utils.dice_score import dice_coeff, multiclass_dice_coeff, dice_loss  # noqa: F401
 from .utils.boundary_loss import boundary_loss  # noqa: F401
 from .utils.connected_component_loss import connected_component_loss  # noqa: F401

@@ -1426,6 +1426,76 @@ class ConvTranspose2x2PadFn(Function):
         return dx, dw, db, None, None
 
 
+# ----------------------------------------------------------------------------- spatial attention
+def _sa_weight(weight: torch.Tensor):
+    k = int(weight.shape[-1])
+    if tuple(weight.shape) != (1, 2, k, k) or k not in (3, 7):
+        raise RuntimeError(f"SpatialAttention weight must be [1, 2, k, k] with k in (3, 7), got {tuple(weight.shape)}")
+    return weight.detach().float().contiguous(), k
+
+
+def _sa_forward(ctx, x, weight, gate: bool):
+    _require_gpu(x, "activation")
+    x = dense_nhwc(x)
+    B, H, W, C = x.shape
+    wc, k = _sa_weight(weight)
+    npix = B * H * W
+    pool = torch.empty((npix, 2), dtype=torch.float32, device=x.device)
+    amax = torch.empty(npix, dtype=torch.int32, device=x.device)
+    a = torch.empty((B, H, W, 1), dtype=torch.float32, device=x.device)
+    y = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device) if gate else None
+    LIB.call("uh_spatial_attn_fwd", x.data_ptr(), pixel_ld(x), wc.data_ptr(), k, pool.data_ptr(), amax.data_ptr(),
+             a.data_ptr(), _p(y), C, B, H, W, C, _dt(x), _stream())
+    ctx.save_for_backward(x if gate else None, wc, pool, amax, a)
+    ctx.geom = (B, H, W, C, k, tuple(weight.shape), x.dtype)
+    return y if gate else a
+
+
+def _sa_backward(ctx, dy, ga):
+    x, wc, pool, amax, a = ctx.saved_tensors
+    B, H, W, C, k, wshape, dtype = ctx.geom
+    if dy is not None:
+        dy = dense_nhwc(dy if dy.dtype == dtype else dy.to(dtype))
+    else:
+        ga = ga.float().contiguous()
+    dev = pool.device
+    ws = torch.empty(3 * B * H * W, dtype=torch.float32, device=dev)
+    dx = torch.empty((B, H, W, C), dtype=dtype, device=dev)
+    dw = torch.empty(wshape, dtype=torch.float32, device=dev)
+    nblk = LIB.query("uh_spatial_attn_dw_nblk", B, H, W)
+    part = torch.empty((nblk, 2 * k * k), dtype=torch.float32, device=dev)
+    LIB.call("uh_spatial_attn_bwd", _p(dy), 0 if dy is None else pixel_ld(dy), _p(ga), _p(x), 0 if x is None else pixel_ld(x),
+             wc.data_ptr(), k, pool.data_ptr(), amax.data_ptr(), a.data_ptr(), ws.data_ptr(), dx.data_ptr(), C, dw.data_ptr(),
+             part.data_ptr(), nblk, B, H, W, C, UH_BF16 if dtype == torch.bfloat16 else UH_F32, _stream())
+    return dx, dw
+
+
+class SpatialAttnMapFn(Function):
+    """SpatialAttention.forward (unet_parts.py:50-60): x [B,H,W,C] -> a = sigmoid(conv_kxk([mean_c x, max_c x])) as fp32
+    [B,H,W,1].  The max's gradient goes to the FIRST maximal channel, as torch.max(dim=1) routes it."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        return _sa_forward(ctx, x, weight, gate=False)
+
+    @staticmethod
+    def backward(ctx, ga):
+        return _sa_backward(ctx, None, ga)
+
+
+class SpatialAttnGateFn(Function):
+    """The gated skip of Up(use_attention=True) (unet_parts.py:91-92): y = x * SpatialAttention(x), one node (the map
+    never leaves the kernels as a tensor of the graph); y is rounded once to x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        return _sa_forward(ctx, x, weight, gate=True)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _sa_backward(ctx, dy, None)
+
+
 # ----------------------------------------------------------------------------- OutConv
 class OutConv1x1Fn(Function):
     """nn.Conv2d(Cin, n_classes, kernel_size=1) with bias (unet_parts.py:103); logits are fp32."""

@@ -1,11 +1,11 @@
 """UNet assemblies on the HIP blocks.
 
-Drop-in surface of /root/reference/unet/unet_model.py: `UNet`, `UNet_S`, `UNet_T`
+Drop-in surface of /root/reference/unet/unet_model.py: `UNet`, `UNet_S`, `UNet_T`, `UNet_SA`
 (n_channels, n_classes, bilinear=False), attributes n_channels / n_classes / bilinear, children
 inc, down1..downN, up1..upN, outc, forward(x[B,C,H,W]) -> logits[B,n_classes,H,W]
-(unet_model.py:8-38, 52-82, 96-126).  `UNetDepth` builds the same wiring for any width list
-(BASELINE config 4 is the 5-level variant).  UNet_SA / use_checkpointing are out of scope
-(attention is used by no config; use_checkpointing is broken upstream).
+(unet_model.py:8-38, 52-82, 96-126, 140-189).  `UNetDepth` builds the same wiring for any width list
+(BASELINE config 4 is the 5-level variant); `attention=True` gates every skip connection with a SpatialAttention
+map (UNet_SA).  use_checkpointing is out of scope (broken upstream).
 """
 from __future__ import annotations
 
@@ -15,11 +15,12 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .unet_parts import DoubleConv, Down, OutConv, Up
+from .unet_parts import AttentionUp, DoubleConv, Down, OutConv, Up
 
 
 class UNetDepth(nn.Module):
-    def __init__(self, n_channels, n_classes, bilinear=False, widths: Sequence[int] = (64, 128, 256, 512, 1024)):
+    def __init__(self, n_channels, n_classes, bilinear=False, widths: Sequence[int] = (64, 128, 256, 512, 1024),
+                 attention: bool = False):
         super().__init__()
         self.n_channels = n_channels
         self.n_classes = n_classes
@@ -35,7 +36,7 @@ class UNetDepth(nn.Module):
         for j in range(1, self.depth + 1):
             cin = w[self.depth - j + 1]
             cout = w[self.depth - j] // shrink if j < self.depth else w[0]
-            setattr(self, f"up{j}", Up(cin, cout, bilinear))
+            setattr(self, f"up{j}", (AttentionUp if attention else Up)(cin, cout, bilinear))
         self.outc = OutConv(w[0], n_classes)
         # activation dtype of the HIP path when no autocast context is active
         self.compute_dtype = torch.float32
@@ -96,3 +97,10 @@ class UNet_T(UNetDepth):
 
     def __init__(self, n_channels, n_classes, bilinear=False):
         super().__init__(n_channels, n_classes, bilinear, (8, 16, 32, 64, 128))
+
+
+class UNet_SA(UNetDepth):
+    """UNet_S widths 16-32-64-128-256 with a SpatialAttention gate on every skip connection (unet_model.py:140-189)."""
+
+    def __init__(self, n_channels, n_classes, bilinear=False):
+        super().__init__(n_channels, n_classes, bilinear, (16, 32, 64, 128, 256), attention=True)

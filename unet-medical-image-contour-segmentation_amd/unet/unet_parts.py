@@ -7,6 +7,8 @@ sub-module attribute names and therefore state_dict keys -- SURVEY.md A.1):
     Down(in_channels, out_channels)                               unet_parts.py:26-37
     Up(in_channels, out_channels, bilinear=True)                  unet_parts.py:62-98
     OutConv(in_channels, out_channels)                            unet_parts.py:100-106
+    SpatialAttention(kernel_size=7)                               unet_parts.py:39-60
+    AttentionUp(in_channels, out_channels, bilinear=True)         unet_parts.py:62-98 with use_attention=True
 
 The nn.Conv2d / nn.BatchNorm2d / nn.ConvTranspose2d children are PARAMETER CONTAINERS only (same
 init, same keys, visible to optimizers / state_dict / .to()); their torch forward is never called.
@@ -189,7 +191,8 @@ class Up(nn.Module):
     def __init__(self, in_channels, out_channels, bilinear=True, use_attention=False):
         super().__init__()
         if use_attention:
-            raise NotImplementedError("SpatialAttention (UNet_SA only) is outside the hot-path scope (SURVEY.md section 2)")
+            raise NotImplementedError("Up(..., use_attention=True): the attention-gated block is AttentionUp "
+                                      "(unet_parts.AttentionUp; the model is UNet_SA)")
         self.bilinear = bool(bilinear)
         if self.bilinear:
             self.up = nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True)
@@ -200,22 +203,60 @@ class Up(nn.Module):
         self.use_attention = False
         self.attention = nn.Identity()
 
-    def nhwc(self, x1, x2, tail=None, upsampled: bool = False):
-        """`upsampled`: x1 already is the up-sampled, padded tensor (its producer ran with tail=("up", Ho, Wo))."""
+    def _upsample(self, x1, x2, upsampled: bool):
         Ho, Wo = x2.shape[1], x2.shape[2]
         if upsampled:
             if not self.bilinear or tuple(x1.shape[1:3]) != (Ho, Wo):
                 raise RuntimeError("Up.nhwc(upsampled=True) needs a bilinear block and an input of the skip's extent")
-            u = x1
-        elif self.bilinear:
-            u = ops.UpsampleBilinearPadFn.apply(x1, Ho, Wo)
-        else:
-            u = ops.ConvTranspose2x2PadFn.apply(x1, self.up.weight, self.up.bias, Ho, Wo)
+            return x1
+        if self.bilinear:
+            return ops.UpsampleBilinearPadFn.apply(x1, Ho, Wo)
+        return ops.ConvTranspose2x2PadFn.apply(x1, self.up.weight, self.up.bias, Ho, Wo)
+
+    def nhwc(self, x1, x2, tail=None, upsampled: bool = False):
+        """`upsampled`: x1 already is the up-sampled, padded tensor (its producer ran with tail=("up", Ho, Wo))."""
+        u = self._upsample(x1, x2, upsampled)
         return self.conv.nhwc(x2, u, tail=tail)          # channel order [skip, up] as unet_parts.py:95
 
     def forward(self, x1, x2):
         dt = ops.compute_dtype(x1.dtype if x1.dtype == torch.bfloat16 else torch.float32)
         return ops.to_nchw(self.nhwc(ops.to_nhwc(x1, dt), ops.to_nhwc(x2, dt)))
+
+
+class SpatialAttention(nn.Module):
+    """sigmoid(conv_kxk([mean_c x, max_c x])) -> [B,1,H,W] (fp32 map); k = 3 or 7 with zero padding k // 2, no bias."""
+
+    def __init__(self, kernel_size=7):
+        super().__init__()
+        assert kernel_size in (3, 7), "SpatialAttention: kernel_size is 3 or 7"
+        self.conv1 = nn.Conv2d(2, 1, kernel_size, padding=kernel_size // 2, bias=False)
+        self.sigmoid = nn.Sigmoid()
+
+    def nhwc(self, x):
+        """x [B,H,W,C] -> the map [B,H,W,1] fp32."""
+        return ops.SpatialAttnMapFn.apply(x, self.conv1.weight)
+
+    def gate_nhwc(self, x):
+        """x [B,H,W,C] -> x * map in x's dtype (unet_parts.py:91-92), one fused node."""
+        return ops.SpatialAttnGateFn.apply(x, self.conv1.weight)
+
+    def forward(self, x):
+        return ops.to_nchw(self.nhwc(ops.to_nhwc(x, ops.compute_dtype(x.dtype if x.dtype == torch.bfloat16 else torch.float32))))
+
+
+class AttentionUp(Up):
+    """Up with a SpatialAttention gate on the skip (Up(..., use_attention=True) of the reference): the skip is multiplied
+    by its attention map after the up-sampling and before the concat.  Parameters are created in the reference's order
+    (up, conv, attention), so seeded construction and state_dict keys (upN.attention.conv1.weight) match."""
+
+    def __init__(self, in_channels, out_channels, bilinear=True):
+        super().__init__(in_channels, out_channels, bilinear)
+        self.use_attention = True
+        self.attention = SpatialAttention()
+
+    def nhwc(self, x1, x2, tail=None, upsampled: bool = False):
+        u = self._upsample(x1, x2, upsampled)
+        return self.conv.nhwc(self.attention.gate_nhwc(x2), u, tail=tail)
 
 
 class OutConv(nn.Module):
