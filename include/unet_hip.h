@@ -461,6 +461,40 @@ int uh_postprocess_masks(const uint8_t* mask, uint8_t* out, int B, int H, int W,
 int uh_batch_prepare(const uint8_t* img_u8, int C, const uint8_t* mask_u8, const int* turns, int odd_turns, void* image_out,
                      int ld_out, int64_t* labels_out, int* flags_ws, int B, int Hin, int Win, int dt, uh_stream stream);
 
+/* ---- RAW -> contour pipeline, non-inference stages  (seg_main.py; utils/raw2png.py, png_normalize.py, png_denormalize.py,
+ * mask2polygon.py).  Batched over B images of one geometry.
+ *
+ * uh_window_u16: raw2png.py:_apply_windowing.  raw DEVICE uint16 [n] (16-byte aligned), out DEVICE uint8 [n] (8-byte aligned):
+ *   mn = WL - WW/2, mx = WL + WW/2, out = trunc(double(clamp(x, mn, mx) - mn) / double(mx - mn) * 255.0), in IEEE double.
+ *   WW < 2 is refused (the reference divides 0 by 0). */
+int uh_window_u16(const uint16_t* raw, int64_t n, int window_length, int window_width, uint8_t* out, uh_stream stream);
+/* uh_resample_lanczos_u8: Pillow's 8-bit two-pass resample (Image.resize(..., LANCZOS)) of the box (box_x, box_y, box_w,
+ *   box_h) of src DEVICE uint8 [B][Hs][Ws], written at (px, py) into dst DEVICE uint8 [B][Hd][Wd], every other dst pixel 0.
+ *   lut: DEVICE uint8 [256] applied to each source byte first (identity, or class index -> grey level).
+ *   h_bounds / v_bounds: DEVICE int [out_w][2] / [out_h][2] {first tap, number of taps}; h_coef / v_coef: DEVICE int
+ *   [out_w][kh] / [out_h][kv] 22-bit fixed-point weights (Resample.c precompute_coeffs + normalize_coeffs_8bpc, built on the
+ *   host).  Horizontal bounds are relative to box_x; the horizontal pass runs over box rows [row0, row0 + nrows) into ws,
+ *   and vertical bounds are relative to row0.  kh <= 128.  ws: uh_resample_ws_bytes(B, nrows, out_w) bytes. */
+size_t uh_resample_ws_bytes(int B, int nrows, int out_w);
+int uh_resample_lanczos_u8(const uint8_t* src, int B, int Hs, int Ws, int box_x, int box_y, int box_w, int box_h,
+                           const uint8_t* lut, const int* h_bounds, const int* h_coef, int kh, int out_w,
+                           const int* v_bounds, const int* v_coef, int kv, int out_h, int row0, int nrows,
+                           uint8_t* dst, int Hd, int Wd, int px, int py, void* ws, size_t ws_bytes, uh_stream stream);
+/* External contours of (grey > 127): cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) as OpenCV's icvFetchContour
+ * traces them, PARITY UNPINNED (OpenCV is not available here).  grey: DEVICE uint8 [B][H][W]; B <= 1024 and B*H*roundup(W,16)
+ * < 2^31.  ws: uh_contours_ws_bytes() bytes, 16-byte aligned, kept between the two calls.
+ * uh_contours_count fills info: DEVICE int [3 + 2B + 1] = {total contours, total points, error flags, ncont[B], first
+ *   contour of each image [B + 1]}, and npts: DEVICE int [uh_contours_max()] points per contour, contours ordered
+ *   image-major and, within an image, in cv2's list order (reverse raster order of the start pixels).
+ * uh_contours_emit writes the points, int32 {x, y} pairs (8-byte aligned), contour after contour in the same order;
+ *   max_points = capacity in points (>= info[1]).  info[2] != 0 after either call = an inconsistent walk (a bug). */
+size_t uh_contours_ws_bytes(int B, int H, int W);
+size_t uh_contours_max(int B, int H, int W);
+int uh_contours_count(const uint8_t* grey, int B, int H, int W, void* ws, size_t ws_bytes, int* info, int* npts,
+                      uh_stream stream);
+int uh_contours_emit(void* ws, size_t ws_bytes, int B, int H, int W, int* info, const int* npts, int* points,
+                     int64_t max_points, uh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
