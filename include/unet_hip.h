@@ -457,9 +457,24 @@ int uh_postprocess_masks(const uint8_t* mask, uint8_t* out, int B, int H, int W,
  *              the raw 0 / 1 value (data_loading.py:86-87); channels C..ld_out-1 are not written
  *   labels_out int64 [B][Ho][Wo]: 255 -> 2, 128 -> 1, anything else -> 0 (data_loading.py:74-78)
  *   flags_ws   DEVICE int [B] workspace (per-image "holds a value above 1")
- * Decode and the BICUBIC / NEAREST rescale of scale < 1 stay on the host. */
+ * Decode stays on the host; the BICUBIC / NEAREST rescale of scale < 1 is uh_batch_rescale_u8, run before this call. */
 int uh_batch_prepare(const uint8_t* img_u8, int C, const uint8_t* mask_u8, const int* turns, int odd_turns, void* image_out,
                      int ld_out, int64_t* labels_out, int* flags_ws, int B, int Hin, int Win, int dt, uh_stream stream);
+/* uh_batch_rescale_u8: the dataset's rotate + rescale at scale < 1 (data_loading.py:66-70, 100-121), Pillow's bytes exactly:
+ *   img_out  = _rescaled(_quarter_turn(img, t), s, BICUBIC)   DEVICE uint8 [B][out_h][out_w][C], C = 1 or 3
+ *   mask_out = _rescaled(_quarter_turn(mask, t), s, NEAREST)  DEVICE uint8 [B][out_h][out_w]
+ *   of img_u8 DEVICE uint8 [B][Hin][Win][C] / mask_u8 DEVICE uint8 [B][Hin][Win] (either may be null), turns / odd_turns as
+ *   uh_batch_prepare.  The tables describe the ROTATED size Hr x Wr (Win x Hin when odd_turns) and are built on the host:
+ *   h_bounds / h_coef [out_w][2] / [out_w][kh] and v_bounds / v_coef [out_h][2] / [out_h][kv] as uh_resample_lanczos_u8
+ *   (bicubic filter; the horizontal pass covers rotated rows [row0, row0 + nrows), vertical bounds relative to row0);
+ *   span >= the source pixels any 64 consecutive output columns read (xmin of the last + taps - xmin of the first);
+ *   x_index [out_w] / y_index [out_h]: Pillow's NEAREST source column / row of every output pixel.
+ *   ws: uh_batch_rescale_ws_bytes(B, C, nrows, out_w) bytes (the uint8 intermediate of the two passes). */
+size_t uh_batch_rescale_ws_bytes(int B, int C, int nrows, int out_w);
+int uh_batch_rescale_u8(const uint8_t* img_u8, int C, const uint8_t* mask_u8, const int* turns, int odd_turns, int B, int Hin,
+                        int Win, const int* h_bounds, const int* h_coef, int kh, int span, int out_w, const int* v_bounds,
+                        const int* v_coef, int kv, int out_h, int row0, int nrows, const int* x_index, const int* y_index,
+                        uint8_t* img_out, uint8_t* mask_out, void* ws, size_t ws_bytes, uh_stream stream);
 
 /* ---- RAW -> contour pipeline, non-inference stages  (seg_main.py; utils/raw2png.py, png_normalize.py, png_denormalize.py,
  * mask2polygon.py).  Batched over B images of one geometry.

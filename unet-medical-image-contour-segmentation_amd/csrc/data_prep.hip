@@ -9,7 +9,7 @@
 // instead of 4C + 8) and leaves as NHWC fp32 / bf16 in [0,1] + int64 labels, rotated per item.  HBM-bound byte work: a
 // workgroup moves one 64x64 output tile; its source block is read row-wise (whole 64-byte lines for every turn count) into
 // LDS and read back in the rotated order, so neither side of the transpose touches memory with a stride.
-// Decode and the BICUBIC / NEAREST rescale (scale < 1) stay on the host.
+// Decode stays on the host; the BICUBIC / NEAREST rescale of scale < 1 is data_rescale.hip, run before this stage.
 #include "uh_common.h"
 
 namespace {

@@ -6,6 +6,7 @@
     train_step(...)   zero_grad -> forward (autocast) -> loss -> NaN check -> backward -> clip -> step
     TrainStepper      model + optimizer (+ data-parallel sync) bundle used by bench.py
     train_model(...)  the epoch loop of train.py:29-220 on a user-supplied iterable of batches
+    main(argv)        `python -m unet_amd.train`: the reference's command line over a data directory (train_cli.py)
 A reference-style loop with torch.optim.RMSprop / clip_grad_norm_ on `model.parameters()` also
 works unchanged: the modules are ordinary nn.Modules.
 """
@@ -653,3 +654,21 @@ def train_model(model, device, train_batches, val_batches=None, epochs: int = 5,
         if log:
             log(rec)
     return history
+
+
+# ----------------------------------------------------------------------------------- command line
+def get_args(argv=None):
+    """The reference's train.py flags (train_cli.py)."""
+    from .train_cli import get_args as _get_args
+    return _get_args(argv)
+
+
+def main(argv=None) -> int:
+    """`python -m unet_amd.train ...`: the reference's train.py command line (train_cli.py)."""
+    from .train_cli import main as _main
+    return _main(argv)
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

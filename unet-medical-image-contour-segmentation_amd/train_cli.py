@@ -1,0 +1,190 @@
+"""The reference's training command line, /root/reference/train.py:223-309, on the HIP path:
+
+    python -m unet_amd.train -e 5 -b 1 -l 1e-5 -s 0.5 -c 3 [--bilinear] [-f model.pth] [--no-amp]
+                             [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
+
+It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
+train.py:29-220, restated literally ("reproduced, not fixed"):
+  - train batches shuffled, the last one partial (shuffle=True, drop_last=False); validation in order, drop_last=True;
+  - one TrainStepper step per batch (the NaN check raises as train.py:149-151);
+  - evaluate(..., postprocess=True) whenever global_step % (n_train // batch_size) == 0, never when that divisor is 0
+    (train.py:174-187: it can fall mid-epoch or more than once per epoch), then lr = cosine_warm_restarts_lr(lr, dice);
+  - checkpoint_dir/checkpoint_epoch{E}.pth when E > epochs / 2 and E % 5 == 0, with mask_values = train + val
+    (train.py:208-216); model_epoch{epochs}.pth, a plain state_dict, in the working directory (train.py:220);
+  - --load drops mask_values (train.py:275-280); -v is accepted and unused, as in the reference.
+Input batches come from DeviceBatchLoader: decode threads, pinned collation, rotation + BICUBIC / NEAREST rescale + /255
++ label remap on the device (csrc/data_rescale.hip, csrc/data_prep.hip), bit-identical to stacking ds[i].
+--amp (the default) is the project's bf16 path; --no-amp trains in fp32.  There is no CPU fallback: without a GPU the
+command exits with status 2."""
+from __future__ import annotations
+
+import argparse
+import logging
+import math
+import os
+import sys
+import time
+from pathlib import Path
+from typing import Dict, List, Optional
+
+import torch
+
+MODELS = ("UNet_S", "UNet", "UNet_T", "UNet_SA")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Train the UNet on images and target masks")
+    # the reference's flags, short forms and defaults (train.py:223-236)
+    p.add_argument("--epochs", "-e", metavar="E", type=int, default=5, help="Number of epochs")
+    p.add_argument("--batch-size", "-b", dest="batch_size", metavar="B", type=int, default=1, help="Batch size")
+    p.add_argument("--learning-rate", "-l", metavar="LR", type=float, default=1e-5, help="Learning rate", dest="lr")
+    p.add_argument("--load", "-f", type=str, default=False, help="Load model from a .pth file")
+    p.add_argument("--scale", "-s", type=float, default=0.5, help="Downscaling factor of the images")
+    p.add_argument("--validation", "-v", dest="val", type=float, default=10.0,
+                   help="Percent of the data that is used as validation (0-100); accepted and unused, as in the reference")
+    p.add_argument("--amp", action="store_true", default=True, help="Use mixed precision (bf16; the default)")
+    p.add_argument("--bilinear", action="store_true", default=False, help="Use bilinear upsampling")
+    p.add_argument("--classes", "-c", type=int, default=3, help="Number of classes")
+    # additions
+    p.add_argument("--no-amp", dest="amp", action="store_false", help="Train in fp32")
+    p.add_argument("--model", choices=MODELS, default="UNet_S", help="Network (train.py:253 uses UNet_S)")
+    p.add_argument("--data-root", default="data/data-without-black-shadow",
+                   help="Directory holding imgs/{train,val} and masks/{train,val}")
+    p.add_argument("--checkpoint-dir", default="./checkpoints", help="Where checkpoint_epoch{E}.pth files go")
+    p.add_argument("--workers", type=int, default=8, help="Decode threads per loader")
+    p.add_argument("--seed", type=int, default=None, help="Seeds model init and shuffling (default: unseeded)")
+    return p
+
+
+def get_args(argv=None) -> argparse.Namespace:
+    return build_parser().parse_args(argv)
+
+
+# ------------------------------------------------------------------------------------- cadence (train.py:161-216)
+def eval_due(global_step: int, n_train: int, batch_size: int) -> bool:
+    division_step = n_train // batch_size
+    return division_step > 0 and global_step % division_step == 0
+
+
+def checkpoint_due(epoch: int, epochs: int) -> bool:
+    return epoch > epochs * 0.5 and epoch % 5 == 0
+
+
+def cadence(n_train: int, batch_size: int, epochs: int) -> Dict[str, List]:
+    """{'eval_steps': [(epoch, global_step)] at which evaluate runs, 'checkpoint_epochs': [E]} of the loop below
+    (steps per epoch: ceil(n_train / batch_size), the last batch partial)."""
+    steps = math.ceil(n_train / batch_size)
+    evals, gs = [], 0
+    for epoch in range(1, epochs + 1):
+        for _ in range(steps):
+            gs += 1
+            if eval_due(gs, n_train, batch_size):
+                evals.append((epoch, gs))
+    return {"eval_steps": evals, "checkpoint_epochs": [e for e in range(1, epochs + 1) if checkpoint_due(e, epochs)]}
+
+
+def build_model(name: str, n_classes: int, bilinear: bool):
+    from . import unet
+    return getattr(unet, name)(n_channels=1, n_classes=n_classes, bilinear=bilinear)
+
+
+def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: int, learning_rate: float, amp: bool,
+                 checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
+                 train_loader=None, log=None) -> List[Dict]:
+    """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
+    last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
+    images over the epoch's wall time without its evaluations) and the seconds spent evaluating."""
+    from .evaluate import evaluate
+    from .checkpoint import save_checkpoint
+    from .train import TrainStepper, cosine_warm_restarts_lr
+    from .utils.data_loading import DeviceBatchLoader
+    n_train = len(train_set)
+    if train_loader is None:
+        train_loader = DeviceBatchLoader(train_set, batch_size, shuffle=True, drop_last=False, seed=seed, workers=workers,
+                                         device=device)
+    val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
+    stepper = TrainStepper(model, lr=learning_rate, amp=amp)
+    lr = learning_rate
+    global_step = 0
+    history = []
+    for epoch in range(1, epochs + 1):
+        model.train()
+        losses = []
+        dice = (None, None, None)
+        eval_s = 0.0
+        seen = 0
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        for batch in train_loader:
+            images, true_masks = batch["image"], batch["mask"]
+            terms = stepper.step(images, true_masks)
+            losses.append(terms["loss"].detach())
+            seen += images.shape[0]
+            global_step += 1
+            if eval_due(global_step, n_train, batch_size):
+                torch.cuda.synchronize(device)
+                te = time.perf_counter()
+                val_score, val_post, val_min = evaluate(model, val_loader, device, amp)          # postprocess=True
+                lr = cosine_warm_restarts_lr(learning_rate, float(val_score))                    # scheduler.step(val_score)
+                stepper.optimizer.param_groups[0]["lr"] = lr
+                dice = (float(val_score), float(val_post), float(val_min))
+                eval_s += time.perf_counter() - te
+                if log:
+                    log(f"Validation Dice score: {dice[0]}  postprocessed: {dice[1]}  min: {dice[2]}")
+        torch.cuda.synchronize(device)
+        wall = time.perf_counter() - t0
+        epoch_loss = 0.0
+        for v in torch.stack(losses).float().cpu().tolist() if losses else []:
+            epoch_loss += v                                                                      # loss.item() summed
+        rec = {"epoch": epoch, "loss": epoch_loss, "val_dice": dice[0], "val_dice_post": dice[1], "val_dice_min": dice[2],
+               "lr": lr, "images": seen, "img_s": seen / max(wall - eval_s, 1e-9), "eval_s": eval_s}
+        if checkpoint_dir is not None and checkpoint_due(epoch, epochs):
+            path = os.path.join(checkpoint_dir, f"checkpoint_epoch{epoch}.pth")
+            save_checkpoint(model, path, mask_values=train_set.mask_values + val_set.mask_values)
+            rec["checkpoint"] = path
+        history.append(rec)
+        if log:
+            log(f"Epoch {epoch}/{epochs}: loss (total) {epoch_loss:.6g}, Dice {dice[0]} / post {dice[1]} / min {dice[2]}, "
+                f"lr {lr:.6g}, {rec['img_s']:.1f} images/s ({seen} images, evaluation {eval_s:.2f} s)"
+                + (f", checkpoint {rec['checkpoint']}" if "checkpoint" in rec else ""))
+    stepper.close()
+    return history
+
+
+def main(argv=None) -> int:
+    args = get_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(levelname)s: %(message)s")
+    if not torch.cuda.is_available():
+        logging.error("train: no GPU found. This port trains on the MI355X through its HIP kernels and has no CPU path.")
+        return 2
+    from .checkpoint import load_checkpoint
+    from .utils.data_loading import BasicDataset
+    device = torch.device("cuda", torch.cuda.current_device())
+    logging.info(f"Using device {device}")
+    root = Path(args.data_root)
+    train_set = BasicDataset(root / "imgs" / "train", root / "masks" / "train", args.scale)
+    val_set = BasicDataset(root / "imgs" / "val", root / "masks" / "val", args.scale)
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
+    model = build_model(args.model, args.classes, args.bilinear)
+    model = model.to(memory_format=torch.channels_last)
+    logging.info(f"Network: {args.model}, {model.n_channels} input channels, {model.n_classes} output channels (classes), "
+                 f"{'bilinear' if args.bilinear else 'transposed conv'} upscaling")
+    if args.load:
+        load_checkpoint(model, args.load, device="cpu")                       # mask_values dropped (train.py:275-280)
+        logging.info(f"Model loaded from {args.load}")
+    model.to(device=device)
+    n_train, n_val = len(train_set), len(val_set)
+    logging.info(f"Starting training: epochs {args.epochs}, batch size {args.batch_size}, learning rate {args.lr}, "
+                 f"training items {n_train}, validation items {n_val}, scale {args.scale}, "
+                 f"{'bf16 autocast' if args.amp else 'fp32'}, checkpoints in {args.checkpoint_dir}")
+    run_training(model, device, train_set, val_set, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.lr,
+                 amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed, workers=args.workers, log=logging.info)
+    path = f"model_epoch{args.epochs}.pth"
+    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
+    logging.info(f"Model saved to {path}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

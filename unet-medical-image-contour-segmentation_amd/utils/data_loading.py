@@ -11,7 +11,7 @@ table; images are rescaled with BICUBIC, masks with NEAREST, and an image is div
 above 1.  `ds[i]` is the reference's host path (PIL + numpy).
 
 The device stage (csrc/data_prep.hip, `uh_batch_prepare`): `ds.raw_item(i)` stops after the decode (and, for scale < 1,
-the host-side rotation + rescale) and returns uint8 pixels + the number of quarter turns still to apply;
+the host-side rotation + rescale, unless host_rescale=False hands that to csrc/data_rescale.hip) and returns uint8 pixels + the number of quarter turns still to apply;
 `collate_raw` stacks such items into pinned uint8 batches and `prepare_batch_device` turns a batch into the NHWC fp32 /
 bf16 image tensor in [0, 1] and the int64 labels ON THE GPU -- rotation by index, the per-image /255 rule and the label
 remap in one kernel -- so a batch crosses PCIe at 1 + C bytes per pixel instead of 4C + 8 and no PIL / numpy arithmetic
@@ -20,6 +20,7 @@ runs per pixel on the host (above ~1 000 img/s the PIL load
 from __future__ import annotations
 
 import os
+import threading
 from pathlib import Path
 from typing import Dict, List
 
@@ -111,30 +112,36 @@ class BasicDataset(Dataset):
                 "mask": torch.from_numpy(np.ascontiguousarray(classes)).long()}
 
 
-    def raw_item(self, index: int) -> Dict[str, object]:
+    def raw_item(self, index: int, host_rescale: bool = True) -> Dict[str, object]:
         """Item `index` up to the point where arithmetic starts: uint8 pixels [H, W] or [H, W, C], uint8 mask grey levels
-        [H, W] and `turns`, the quarter turns the device stage still has to apply.  At scale 1 the files are decoded and
-        nothing else (the rescale to the same size is the identity, data_loading.py:66-70); at scale < 1 the host rotates
-        and rescales exactly like `__getitem__` (PIL's resampling is not restated on the device) and turns = 0."""
+        [H, W], `turns`, the quarter turns the device stage still has to apply, and `scale`, the rescale it still has to
+        apply.  At scale 1 the files are decoded and nothing else (the rescale to the same size is the identity,
+        data_loading.py:66-70).  At scale < 1 the host rotates and rescales exactly like `__getitem__` (turns = 0, scale =
+        1.0) unless host_rescale=False: then the decoded pixels come back with their turns and the dataset's scale, for
+        prepare_batch_device(..., scale=...) (csrc/data_rescale.hip) to rotate and resample."""
         from PIL import Image
         views = QUARTER_TURNS if self.augment else 1
         stem, turns = self.ids[index // views], index % views
         image = load_image(self._only(self.images_dir, stem, "image"))
         mask = load_image(self._only(self.mask_dir, stem + self.mask_suffix, "mask"))
         assert image.size == mask.size, f"Image and mask {stem} should be the same size, but are {image.size} and {mask.size}"
-        if self.scale != 1:
+        scale = 1.0
+        if self.scale != 1 and host_rescale:
             image = _rescaled(_quarter_turn(image, turns), self.scale, Image.BICUBIC)
             mask = _rescaled(_quarter_turn(mask, turns), self.scale, Image.NEAREST)
             turns = 0
+        elif self.scale != 1:
+            scale = float(self.scale)
         pixels, grey = np.asarray(image), np.asarray(mask)
         if pixels.dtype != np.uint8 or grey.dtype != np.uint8:
             raise TypeError(f"raw_item: {stem} does not decode to 8-bit pixels ({pixels.dtype}, {grey.dtype}); use ds[i]")
-        return {"image_u8": pixels, "mask_u8": grey, "turns": int(turns)}
+        return {"image_u8": pixels, "mask_u8": grey, "turns": int(turns), "scale": scale}
 
 
 def collate_raw(items, pin: bool = True) -> Dict[str, torch.Tensor]:
     """Stack `raw_item`s into uint8 batches [B,H,W,C] / [B,H,W] (pinned host memory) + an int32 turn table.  Every item
-    must produce the same output shape: equal decoded sizes and, unless the images are square, turn counts of one parity."""
+    must produce the same output shape: equal decoded sizes, one `scale` and, unless the images are square, turn counts of
+    one parity.  The batch's `scale` (1.0 for items without one) goes to prepare_batch_device."""
     imgs = [it["image_u8"] if it["image_u8"].ndim == 3 else it["image_u8"][..., None] for it in items]
     shape = imgs[0].shape
     if any(a.shape != shape for a in imgs) or any(it["mask_u8"].shape != shape[:2] for it in items):
@@ -142,21 +149,26 @@ def collate_raw(items, pin: bool = True) -> Dict[str, torch.Tensor]:
     turns = [int(it["turns"]) & 3 for it in items]
     if shape[0] != shape[1] and len({t & 1 for t in turns}) > 1:
         raise ValueError("collate_raw: non-square images rotated by odd and even quarter turns do not stack")
+    scales = {float(it.get("scale", 1.0)) for it in items}
+    if len(scales) > 1:
+        raise ValueError("collate_raw: the items of a batch must have one scale")
     B = len(items)
     image = torch.empty((B,) + shape, dtype=torch.uint8, pin_memory=pin and torch.cuda.is_available())
     mask = torch.empty((B,) + shape[:2], dtype=torch.uint8, pin_memory=pin and torch.cuda.is_available())
     for b, (a, it) in enumerate(zip(imgs, items)):
         np.copyto(image[b].numpy(), a)
         np.copyto(mask[b].numpy(), it["mask_u8"])
-    return {"image_u8": image, "mask_u8": mask, "turns": torch.tensor(turns, dtype=torch.int32)}
+    return {"image_u8": image, "mask_u8": mask, "turns": torch.tensor(turns, dtype=torch.int32), "scale": scales.pop()}
 
 
 def prepare_batch_device(image_u8: torch.Tensor, mask_u8: torch.Tensor, turns=None, device=None,
-                         dtype: torch.dtype = torch.float32) -> Dict[str, torch.Tensor]:
+                         dtype: torch.dtype = torch.float32, scale: float = 1.0) -> Dict[str, torch.Tensor]:
     """uint8 batch (host, ideally pinned, or already on the GPU) -> {'image': logical [B,C,H,W] tensor in `dtype`
     (channels_last memory, values as data_loading.py:86-87 produces them), 'mask': int64 [B,H,W] classes}: what
     train.py:113-114 hands to the model, with rotation / normalisation / label remap done by ONE kernel on the GPU
-    (`uh_batch_prepare`).  No CPU fallback."""
+    (`uh_batch_prepare`).  With scale != 1 the batch is first rotated and rescaled as `_rescaled(_quarter_turn(.))` does
+    with Pillow (BICUBIC image, NEAREST mask: `uh_batch_rescale_u8`, utils/data_rescale.py), and the /255 rule is then
+    decided on the rescaled bytes.  No CPU fallback."""
     from .. import ops
     from .._lib import LIB
     dev = torch.device(device) if device is not None else (image_u8.device if image_u8.is_cuda else torch.device("cuda", torch.cuda.current_device()))
@@ -169,6 +181,11 @@ def prepare_batch_device(image_u8: torch.Tensor, mask_u8: torch.Tensor, turns=No
     B, H, W, C = image_u8.shape
     if tuple(mask_u8.shape) != (B, H, W) or not 1 <= C <= 4:
         raise ValueError(f"prepare_batch_device: image batch {tuple(image_u8.shape)} / mask batch {tuple(mask_u8.shape)}")
+    scale = float(scale)
+    if not 0 < scale <= 1:
+        raise ValueError("prepare_batch_device: scale must be between 0 and 1")
+    if scale != 1 and C not in (1, 3):
+        raise ValueError(f"prepare_batch_device: the device rescale takes 1 or 3 channels, not {C}")
     tl = None
     odd = 0
     if turns is not None:
@@ -185,6 +202,11 @@ def prepare_batch_device(image_u8: torch.Tensor, mask_u8: torch.Tensor, turns=No
         img_d = image_u8.contiguous().to(dev, non_blocking=True)
         msk_d = mask_u8.contiguous().to(dev, non_blocking=True)
         t_d = torch.tensor(tl, dtype=torch.int32).to(dev, non_blocking=True) if tl is not None else None
+        if scale != 1:
+            from .data_rescale import batch_rescale
+            img_d, msk_d = batch_rescale(img_d, msk_d, t_d, odd, scale)     # rotated: uh_batch_prepare applies no turn
+            B, H, W, C = img_d.shape
+            t_d, odd = None, 0
         Ho, Wo = (W, H) if odd else (H, W)
         image = torch.empty((B, Ho, Wo, C), dtype=dtype, device=dev)
         labels = torch.empty((B, Ho, Wo), dtype=torch.int64, device=dev)
@@ -193,6 +215,95 @@ def prepare_batch_device(image_u8: torch.Tensor, mask_u8: torch.Tensor, turns=No
                  image.data_ptr(), C, labels.data_ptr(), flags.data_ptr(), B, H, W, ops._dt(image),
                  torch.cuda.current_stream().cuda_stream)
     return {"image": image.permute(0, 3, 1, 2), "mask": labels}
+
+
+class DeviceBatchLoader:
+    """The reference's DataLoader(ds, batch_size, shuffle, drop_last, pin_memory=True) (train.py:57-59) with the arithmetic
+    on the device: decode threads run `ds.raw_item(i, host_rescale=False)`, a batch is collated into pinned buffers and
+    `prepare_batch_device` rotates, rescales (csrc/data_rescale.hip), divides and remaps it on the GPU.  Yields device
+    batches {'image': fp32 [B,C,H,W] (channels_last), 'mask': int64 [B,H,W]} equal bit for bit to stacking `ds[i]`.
+
+    Decode runs in THREADS (Pillow and the copies release the GIL): no process is forked after the GPU is initialised.
+    `prefetch` batches are decoded ahead of the one being consumed.  host_rescale=True leaves the rescale to Pillow in
+    the decode threads (raw_item's default; kept for comparison).  `epoch_order(e)` is the item order of epoch e (0-based,
+    one epoch per iteration): a seeded permutation when shuffle, else range(len(ds)); `orders` records every epoch served.
+    A dataset that does not decode to 8-bit (raw_item raises TypeError: .npy / float images) is served through ds[i] and
+    the host tensors are moved to the device; that is logged once."""
+
+    def __init__(self, ds, batch_size: int = 1, shuffle: bool = False, drop_last: bool = False, seed=None, workers: int = 8,
+                 device=None, prefetch: int = 2, host_rescale: bool = False):
+        if batch_size < 1 or workers < 1 or prefetch < 1:
+            raise ValueError("DeviceBatchLoader: batch_size, workers and prefetch must be positive")
+        self.ds, self.batch_size, self.shuffle, self.drop_last = ds, int(batch_size), bool(shuffle), bool(drop_last)
+        self.seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        self.workers, self.prefetch, self.device = int(workers), int(prefetch), device
+        self.epoch = 0
+        self.orders: List[List[int]] = []
+        self.host_items = False           # set once raw_item has refused the dataset (TypeError)
+        self._switch = threading.Lock()
+        self.host_rescale = bool(host_rescale)     # True: Pillow rescales in the decode threads (the earlier path; benchmarks)
+
+    def epoch_order(self, epoch: int) -> List[int]:
+        n = len(self.ds)
+        if not self.shuffle:
+            return list(range(n))
+        return torch.randperm(n, generator=torch.Generator().manual_seed(self.seed + epoch)).tolist()
+
+    def batches_of(self, order: List[int]) -> List[List[int]]:
+        b = self.batch_size
+        out = [order[i:i + b] for i in range(0, len(order), b)]
+        if self.drop_last and out and len(out[-1]) < b:
+            out.pop()
+        return out
+
+    def __len__(self) -> int:
+        n, b = len(self.ds), self.batch_size
+        return n // b if self.drop_last else (n + b - 1) // b
+
+    def _raw(self, i):
+        if not self.host_items:
+            try:
+                return self.ds.raw_item(i, host_rescale=self.host_rescale)
+            except TypeError as e:
+                with self._switch:
+                    if not self.host_items:
+                        import logging
+                        logging.info(f"DeviceBatchLoader: {e}; serving ds[i] through the host path")
+                    self.host_items = True
+        return self.ds[i]
+
+    def _collate(self, idx, futures):
+        items = [f.result() for f in futures]
+        if all("image_u8" in it for it in items):
+            return collate_raw(items)
+        # the TypeError fallback (a batch that straddled the switch re-reads its raw items through ds[i])
+        host = [it if "image" in it else self.ds[i] for i, it in zip(idx, items)]
+        return {"image": torch.stack([h["image"] for h in host]), "mask": torch.stack([h["mask"] for h in host])}
+
+    def __iter__(self):
+        from concurrent.futures import ThreadPoolExecutor
+        order = self.epoch_order(self.epoch)
+        self.epoch += 1
+        self.orders.append(order)
+        batches = self.batches_of(order)
+        dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        with ThreadPoolExecutor(self.workers) as items_pool, ThreadPoolExecutor(self.prefetch) as batch_pool:
+            def submit(idx):
+                return batch_pool.submit(self._collate, idx, [items_pool.submit(self._raw, i) for i in idx])
+
+            pending = [submit(idx) for idx in batches[:self.prefetch + 1]]
+            nxt = len(pending)
+            while pending:
+                batch = pending.pop(0).result()
+                if nxt < len(batches):
+                    pending.append(submit(batches[nxt]))
+                    nxt += 1
+                if "image_u8" in batch:
+                    yield prepare_batch_device(batch["image_u8"], batch["mask_u8"], batch["turns"], device=dev,
+                                               scale=batch["scale"])
+                else:
+                    yield {"image": batch["image"].to(dev, non_blocking=True, memory_format=torch.channels_last),
+                           "mask": batch["mask"].to(dev, non_blocking=True)}
 
 
 class CarvanaDataset(BasicDataset):

@@ -3,6 +3,8 @@
     letterbox_geometry(width, height, target=512) -> (nw, nh, px, py)       png_normalize.py:536-556
     lanczos_coeffs(in_size, out_size) -> (bounds [out][2], coef [out][k])   Pillow Resample.c precompute_coeffs +
                                                                             normalize_coeffs_8bpc (LANCZOS, 8-bit)
+    resample_coeffs(in_size, out_size, filter)                              the same for 'lanczos' or 'bicubic' (the
+                                                                            dataset rescale, utils/data_rescale.py)
     ResamplePlan(in_w, in_h, out_w, out_h)                                  both passes' tables, on the device, cached
     letterbox(images) -> uint8 [B, 512, 512]                                png_normalize.py:_process_single_image
 
@@ -49,12 +51,29 @@ def _lanczos(x: float) -> float:
     return 0.0
 
 
-@lru_cache(maxsize=64)
-def lanczos_coeffs(in_size: int, out_size: int):
-    """-> (bounds int32 [out][2] = {xmin, taps}, coef int32 [out][ksize]) for the box (0, in_size)."""
+def _bicubic(x: float) -> float:
+    """Resample.c bicubic_filter, a = -0.5."""
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+FILTERS = {"lanczos": (_lanczos, 3.0), "bicubic": (_bicubic, 2.0)}     # Resample.c: filter function, support
+
+
+@lru_cache(maxsize=256)
+def resample_coeffs(in_size: int, out_size: int, filter: str = "lanczos"):
+    """-> (bounds int32 [out][2] = {xmin, taps}, coef int32 [out][ksize]) for the box (0, in_size): Resample.c
+    precompute_coeffs + normalize_coeffs_8bpc with `filter` ('lanczos' or 'bicubic')."""
+    fn, fsupport = FILTERS[filter]
     scale = float(in_size) / out_size
     filterscale = max(scale, 1.0)
-    support = 3.0 * filterscale
+    support = fsupport * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), np.int32)
     coef = np.zeros((out_size, ksize), np.int32)
@@ -64,7 +83,7 @@ def lanczos_coeffs(in_size: int, out_size: int):
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        k = [_lanczos((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        k = [fn((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for w in k:
             ww += w
@@ -73,6 +92,12 @@ def lanczos_coeffs(in_size: int, out_size: int):
         coef[xx, :xmax] = [int(-0.5 + w * one) if w < 0 else int(0.5 + w * one) for w in k]
         bounds[xx] = (xmin, xmax)
     return bounds, coef
+
+
+@lru_cache(maxsize=64)
+def lanczos_coeffs(in_size: int, out_size: int):
+    """-> (bounds int32 [out][2] = {xmin, taps}, coef int32 [out][ksize]) for the box (0, in_size)."""
+    return resample_coeffs(in_size, out_size, "lanczos")
 
 
 def _identity_coeffs(n: int):
