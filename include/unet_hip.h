@@ -510,6 +510,21 @@ int uh_contours_count(const uint8_t* grey, int B, int H, int W, void* ws, size_t
 int uh_contours_emit(void* ws, size_t ws_bytes, int B, int H, int W, int* info, const int* npts, int* points,
                      int64_t max_points, uh_stream stream);
 
+/* ---- predict.py / evaluate.py PNG dumps: the byte stages around the eval forward  (csrc/predict_io.hip) -------------
+ * uh_predict_prepare_u8: the image branch of BasicDataset.preprocess at scale 1 for a batch of decoded grey images of one
+ *   size (data_loading.py:86-87, predict.py:19-20): img_u8 DEVICE uint8 [B][H][W] -> image_out DEVICE float32 [B][1][H][W];
+ *   an image that holds a byte > 1 becomes u / 255 (the correctly rounded fp32 quotient numpy computes), any other image keeps
+ *   its raw 0.0 / 1.0.  The test is made per image on the device; flags_ws: DEVICE int [B] workspace.
+ * uh_logits_to_classes_u8: argmax over the classes, straight to one byte per pixel: logits [npix][ncls] (the head's NHWC
+ *   view) in dt (UH_F32 / UH_BF16) -> classes_out DEVICE uint8 [npix]; first maximum, a NaN counts as the maximum (the rule
+ *   of uh_argmax_classes).  ncls <= 256.
+ * uh_classes_to_grey_u8: grey_out[i] = lut[classes[i]] for n bytes, lut DEVICE uint8 [256]; grey_out may be classes
+ *   (in place).  The reference's tables: predict.py:52-58 / evaluate.py:150-154 (0, 128, 255), evaluate.py:160-163
+ *   (post-processed: 2 -> 255, everything else 0), evaluate.py:96-97,103-105 (binary head: 1 -> 255). */
+int uh_predict_prepare_u8(const uint8_t* img_u8, float* image_out, int* flags_ws, int B, int H, int W, uh_stream stream);
+int uh_logits_to_classes_u8(const void* logits, int64_t npix, int ncls, int dt, uint8_t* classes_out, uh_stream stream);
+int uh_classes_to_grey_u8(const uint8_t* classes, uint8_t* grey_out, const uint8_t* lut, int64_t n, uh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,9 @@
 """Validation metric of /root/reference/evaluate.py:12-171: eval-mode forward (running statistics folded into the conv
 epilogue), device-side masks, raw Dice and -- with postprocess=True -- the Dice after utils/post_process.postprocess_mask,
-which here runs on the device for the whole batch (the reference copies every image to the host for OpenCV).  PNG dumps
-(epoch_pred_dir) are host-side file output and are not written."""
+which here runs on the device for the whole batch (the reference copies every image to the host for OpenCV).  With
+epoch_pred_dir the predictions are also written as grey-coded PNGs (evaluate.py:35-40, 88-105, 146-164): the coding is one
+table pass per batch on the device (uh_classes_to_grey_u8), the files are encoded and written by a background writer, and
+evaluate returns once they are on disk.  Without it nothing of that runs."""
 from __future__ import annotations
 
 import torch
@@ -9,6 +11,37 @@ import torch
 from . import ops
 from .utils.dice_score import dice_coeff
 from .utils.post_process import postprocess_mask
+
+
+class _PredDump:
+    """pred_batch{k}_sample{i}.png under epoch_pred_dir, k counting from 1, and the same names under postprocessed/ when
+    post-processing is on (evaluate.py:35-40, 88-105, 146-164)."""
+
+    def __init__(self, epoch_pred_dir, postprocess: bool, device):
+        import os
+        from .predict import GREY_BINARY, GREY_CLASSES, GREY_POSTPROCESSED
+        from .utils.png_writer import OrderedPngWriter
+        self.dir = os.fspath(epoch_pred_dir)
+        self.post_dir = os.path.join(self.dir, "postprocessed") if postprocess else None
+        os.makedirs(self.post_dir if postprocess else self.dir, exist_ok=True)
+        self.luts = {k: torch.from_numpy(v.copy()).to(device) for k, v in
+                     (("classes", GREY_CLASSES), ("postprocessed", GREY_POSTPROCESSED), ("binary", GREY_BINARY))}
+        self.writer = OrderedPngWriter()
+        self.order = 0
+
+    def add(self, batch_index: int, raw_u8, raw_table: str, post_u8=None, post_table=None):
+        import os
+        grey = [(self.dir, ops.classes_to_grey_u8(raw_u8.contiguous(), self.luts[raw_table]))]
+        if post_u8 is not None:
+            grey.append((self.post_dir, ops.classes_to_grey_u8(post_u8.contiguous(), self.luts[post_table])))
+        host = [(d, g.cpu().numpy()) for d, g in grey]
+        for i in range(raw_u8.shape[0]):
+            for d, g in host:                      # the raw file, then its post-processed twin, as the reference writes them
+                self.writer.submit(self.order, os.path.join(d, f"pred_batch{batch_index}_sample{i}.png"), g[i])
+                self.order += 1
+
+    def close(self):
+        self.writer.close()
 
 
 @torch.inference_mode()
@@ -22,6 +55,7 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
     dice_score = torch.zeros((), dtype=torch.float32, device=device)
     dice_post = torch.zeros((), dtype=torch.float32, device=device)
     min_dice = torch.full((), 10.0, dtype=torch.float32, device=device)
+    dump = _PredDump(epoch_pred_dir, postprocess, device) if epoch_pred_dir is not None else None
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
         for batch in dataloader:
             num_val_batches += 1
@@ -39,10 +73,13 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
                     # evaluate.py:71-78 literally: the binary mask goes in coded {0,255}, postprocess_mask looks for class 2
                     # (finds none) and `processed // 255` is the prediction that is scored
                     coded = (pred * 255).to(torch.uint8)
-                    processed = (postprocess_mask(coded) // 255).float()
+                    processed_u8 = postprocess_mask(coded) // 255
+                    processed = processed_u8.float()
                     dp = dice_coeff(processed, mask_true, reduce_batch_first=False)
                     dice_post += dp
                     cur = torch.minimum(d, dp)                                                  # evaluate.py:85
+                if dump is not None:                                                            # evaluate.py:88-105
+                    dump.add(num_val_batches, pred.to(torch.uint8), "binary", processed_u8 if postprocess else None, "binary")
             else:
                 idx = ops.argmax_classes(mask_pred)                                             # evaluate.py:111
                 true_c = (mask_true == 2).float()
@@ -51,9 +88,14 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
                 if postprocess:
                     processed = postprocess_mask(idx.to(torch.uint8))                           # evaluate.py:125-134
                     dice_post += dice_coeff((processed == 2).float(), true_c, reduce_batch_first=False)
+                if dump is not None:                                                            # evaluate.py:146-164
+                    dump.add(num_val_batches, idx.to(torch.uint8), "classes", processed if postprocess else None,
+                             "postprocessed")
             dice_score += d
             min_dice = torch.minimum(min_dice, cur.float())
     net.train()
+    if dump is not None:
+        dump.close()                                            # every file is on disk before the metric is returned
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
         acc = torch.stack([dice_score, dice_post, torch.tensor(float(num_val_batches), device=device)])

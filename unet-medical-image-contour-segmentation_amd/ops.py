@@ -1754,3 +1754,57 @@ def threshold_mask(logits: torch.Tensor) -> torch.Tensor:
     out = torch.empty(v.shape, dtype=torch.float32, device=v.device)
     LIB.call("uh_threshold_mask", v.data_ptr(), v.numel(), out.data_ptr(), _stream())
     return out
+
+
+# ----------------------------------------------------------------------------- predict.py byte stages (csrc/predict_io.hip)
+def predict_prepare_u8(img_u8: torch.Tensor, out: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [B,H,W] decoded grey images -> float32 [B,1,H,W]: `/ 255` for every image that holds a byte > 1, the raw
+    0.0 / 1.0 otherwise (data_loading.py:86-87 decided per image, on the device)."""
+    _require_gpu(img_u8, "images")
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or not img_u8.is_contiguous():
+        raise RuntimeError(f"predict_prepare_u8 takes a contiguous uint8 [B,H,W] batch, got {img_u8.dtype} {tuple(img_u8.shape)}")
+    B, H, W = img_u8.shape
+    if out is None:
+        out = torch.empty(B, 1, H, W, dtype=torch.float32, device=img_u8.device)
+    if flags is None:
+        flags = torch.empty(B, dtype=torch.int32, device=img_u8.device)
+    if out.dtype != torch.float32 or out.numel() != B * H * W or not out.is_contiguous() or flags.numel() < B:
+        raise RuntimeError("predict_prepare_u8: output must be a contiguous float32 [B,1,H,W] and flags an int32 [B]")
+    LIB.call("uh_predict_prepare_u8", img_u8.data_ptr(), out.data_ptr(), flags.data_ptr(), B, H, W, _stream())
+    return out
+
+
+def logits_to_classes_u8(mask_pred: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`mask_pred.argmax(dim=1)` as uint8 [B,H,W] for logits [B,C,H,W] (fp32 or bf16; read through their NHWC view); the
+    int64 map of argmax_classes is not materialised."""
+    _require_gpu(mask_pred, "logits")
+    if mask_pred.dim() != 4 or mask_pred.shape[1] > 256:
+        raise RuntimeError(f"logits_to_classes_u8 expects [B,C<=256,H,W] logits, got {tuple(mask_pred.shape)}")
+    B, C, H, W = mask_pred.shape
+    v = mask_pred.permute(0, 2, 3, 1)
+    if v.dtype not in (torch.float32, torch.bfloat16):
+        v = v.float()
+    if not v.is_contiguous():
+        v = v.contiguous()
+    if out is None:
+        out = torch.empty(B, H, W, dtype=torch.uint8, device=v.device)
+    if out.dtype != torch.uint8 or out.numel() != B * H * W or not out.is_contiguous():
+        raise RuntimeError("logits_to_classes_u8: output must be a contiguous uint8 [B,H,W]")
+    LIB.call("uh_logits_to_classes_u8", v.data_ptr(), B * H * W, C, _dt(v), out.data_ptr(), _stream())
+    return out
+
+
+def classes_to_grey_u8(classes: torch.Tensor, lut: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = lut[classes] for a uint8 tensor and a 256-entry device table; `out=classes` recodes in place."""
+    _require_gpu(classes, "classes")
+    _require_gpu(lut, "lut")
+    if classes.dtype != torch.uint8 or not classes.is_contiguous():
+        raise RuntimeError("classes_to_grey_u8 takes a contiguous uint8 tensor")
+    if lut.dtype != torch.uint8 or lut.numel() != 256 or not lut.is_contiguous():
+        raise RuntimeError("classes_to_grey_u8: the table is a contiguous uint8 [256]")
+    if out is None:
+        out = torch.empty_like(classes)
+    if out.dtype != torch.uint8 or out.shape != classes.shape or not out.is_contiguous():
+        raise RuntimeError("classes_to_grey_u8: output must be a contiguous uint8 tensor of the input's shape")
+    LIB.call("uh_classes_to_grey_u8", classes.data_ptr(), out.data_ptr(), lut.data_ptr(), classes.numel(), _stream())
+    return out

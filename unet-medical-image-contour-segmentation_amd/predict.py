@@ -1,19 +1,39 @@
-"""Single-image inference of /root/reference/predict.py on the HIP path.
+"""Inference of /root/reference/predict.py on the HIP path.
 
     predict_img(model, full_img, device) -> np.ndarray[H, W] of class indices        predict.py:15-29
     mask_to_image(mask) -> PIL.Image (0 / 128 / 255 grey levels)                      predict.py:52-58
     preprocess_image(pil_img, scale=1.0) -> float32 [C, H, W]                         data_loading.py:65-91 (image branch)
+    BatchPredictor(model, batch=8, postprocess=True)(images) -> [uint8 [H, W] grey]   predict.py:120-135 for a list of images
+    python -m unet_amd.predict -m model.pth -i DIR [-o OUT]                           predict.py:31-152 (predict_cli.py)
 
-The forward runs the eval-mode kernels (BatchNorm running statistics folded into per-channel scale/shift),
-argmax is `uh_argmax_classes`.  The CLI / file handling / matplotlib parts of predict.py are outside the scope.
+predict_img is the reference's one-image call: the forward runs the eval-mode kernels (BatchNorm running statistics folded
+into per-channel scale/shift), argmax is `uh_argmax_classes`.  BatchPredictor is the same computation for a list of images
+of mixed sizes: grouped by size, batched, with the byte stages of csrc/predict_io.hip around the forward (`uh_predict_prepare_u8`,
+`uh_logits_to_classes_u8`, `uh_classes_to_grey_u8`), `uh_postprocess_masks` between them and one upload and one download per
+batch.  Its result for an image is, pixel for pixel, mask_to_image(postprocess_mask(predict_img(model, image, device))).
 """
 from __future__ import annotations
+
+from collections import OrderedDict
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from . import ops
+
+
+def _table(pairs) -> np.ndarray:
+    t = np.zeros(256, np.uint8)                  # np.zeros_like(mask): a code the reference does not name stays 0
+    for k, v in pairs:
+        t[k] = v
+    return t
+
+
+GREY_CLASSES = _table([(0, 0), (1, 128), (2, 255)])        # predict.py:52-58, evaluate.py:150-154
+GREY_POSTPROCESSED = _table([(0, 0), (2, 255)])            # evaluate.py:160-163: the post-processed multi-class map, 1 -> 0
+GREY_BINARY = _table([(0, 0), (1, 255)])                   # evaluate.py:96-97 (pred * 255) and :103-105
 
 
 def preprocess_image(pil_img, scale: float = 1.0) -> np.ndarray:
@@ -50,3 +70,273 @@ def mask_to_image(mask: np.ndarray):
     vis[mask == 1] = 128
     vis[mask == 2] = 255
     return Image.fromarray(vis)
+
+
+# ------------------------------------------------------------------------------------------ batches of one size
+class BatchPlanner:
+    """Groups a stream of (index, (H, W)) into batches of one size.  `add` returns the batches that became full; `flush`
+    the partial ones, in order of their oldest member.  No item is held back for more than `window` later indices: once
+    the stream has moved that far past the oldest waiting item, its group is released partial, so that a rare size at the
+    start of a folder does not keep every later result waiting in memory (results are written in index order)."""
+
+    def __init__(self, batch: int, window: Optional[int] = None):
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        self.batch = int(batch)
+        self.window = max(int(window), self.batch) if window is not None else None
+        self._groups: "OrderedDict[Tuple[int, int], List[int]]" = OrderedDict()
+
+    def add(self, index: int, size: Tuple[int, int]) -> List[Tuple[Tuple[int, int], List[int]]]:
+        size = (int(size[0]), int(size[1]))
+        g = self._groups.setdefault(size, [])
+        g.append(index)
+        out = []
+        if len(g) == self.batch:
+            out.append((size, self._groups.pop(size)))
+        while self.window is not None and self._groups:
+            oldest = min(self._groups, key=lambda k: self._groups[k][0])
+            if index - self._groups[oldest][0] < self.window:
+                break
+            out.append((oldest, self._groups.pop(oldest)))
+        return out
+
+    def flush(self) -> List[Tuple[Tuple[int, int], List[int]]]:
+        out = sorted(self._groups.items(), key=lambda kv: kv[1][0])
+        self._groups = OrderedDict()
+        return out
+
+
+def plan_batches(sizes: Sequence[Tuple[int, int]], batch: int, window: Optional[int] = None):
+    """[( (H, W), [indices] )] covering every index of `sizes` once, each batch of one size and at most `batch` long."""
+    planner = BatchPlanner(batch, window)
+    out = []
+    for i, s in enumerate(sizes):
+        out.extend(planner.add(i, s))
+    out.extend(planner.flush())
+    return out
+
+
+def _as_grey_array(img) -> np.ndarray:
+    a = img if isinstance(img, np.ndarray) else np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 2:
+        raise ValueError(f"BatchPredictor takes decoded 8-bit grey images (PIL 'L' or uint8 [H,W]), got {a.dtype} {a.shape}")
+    return a
+
+
+class BatchPredictor:
+    """`predictor(images)` -> one uint8 [H,W] grey-coded mask per image, in input order: what
+    mask_to_image(postprocess_mask(predict_img(model, image, device))) returns for that image (mask_to_image(predict_img(...))
+    with postprocess=False).  `predictor.classes(images)` returns the class maps instead.  Images may have mixed sizes; they
+    are grouped by (H, W) and run up to `batch` at a time.  A full batch of a size that has been seen before replays a
+    captured graph (at most MAX_GRAPHS are kept, least recently used first out); everything else runs un-graphed.
+
+    The result for an image does not depend on its neighbours or on `batch`: every kernel of the eval forward computes a
+    pixel from that image's data in a fixed order.  WHICH kernel runs, however, is chosen per launch in two places, and
+    the alternatives sum in different orders (logits differ by ~1e-4, a few argmax ties flip):
+      - the transposed convolution takes its MFMA GEMM only when B*h*w of its input is a multiple of 32 pixels (bf16; 16 in
+        fp32) and the SIMT kernel otherwise (uh_convt2x2_mfma_ok): 62 x 62 alone is not, eight of them are;
+      - conv3x3_fwd_dispatch splits the contraction over the two halves of a workgroup when a layer with 256+ input channels
+        has at most 256 (tile, 64-channel slab) pairs, and moves to 128-channel slabs from 512 (tile, slab) pairs: a
+        700 x 300 image has 18 tiles at the level of up1 (256 -> 128 channels), so 7 images split K and 8 do not.
+    `launch_lengths` evaluates both rules (the library's predicate, and a restatement of the dispatch rules) and only forms
+    launches in which every layer gets the kernel it gets for one image; a batch is cut into the fewest such launches,
+    down to one image per launch where nothing longer qualifies."""
+
+    MAX_GRAPHS = 4
+
+    def __init__(self, model: torch.nn.Module, batch: int = 8, postprocess: bool = True, amp: bool = True, device=None,
+                 min_area: int = 15000, morph_kernel_size: int = 3):
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        if getattr(model, "n_classes", None) == 1:
+            # predict.py:27 takes argmax(dim=1) of a one-channel tensor: all zeros.  Not reproduced.
+            raise ValueError("BatchPredictor needs a multi-class head: predict.py's argmax over one channel is all zeros. "
+                             "Binary (n_classes == 1) models are scored and dumped by unet_amd.evaluate(..., epoch_pred_dir=...)")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise RuntimeError("BatchPredictor needs an MI355X: the HIP path has no CPU fallback")
+        self.model = model.to(self.device).eval()
+        self.batch, self.postprocess, self.amp = int(batch), bool(postprocess), bool(amp)
+        self.min_area, self.ksize = int(min_area), int(morph_kernel_size)
+        self._lut = torch.from_numpy(GREY_CLASSES.copy()).to(self.device)
+        self._flags = torch.empty(self.batch, dtype=torch.int32, device=self.device)
+        self._graphs: "OrderedDict[Tuple[int, int, int], object]" = OrderedDict()
+        self._seen = set()
+        self._lengths: Dict[Tuple[int, int], List[int]] = {}
+        self._layer_levels = None
+        self._pin_in: Optional[torch.Tensor] = None
+        self._pin_out: Optional[torch.Tensor] = None
+        self.events = None                    # set to a list to collect (stage, start event, end event) per batch
+        self.graph_replays = 0
+
+    # ---------------------------------------------------------------- stages
+    def _mark(self, name, fn, *a, **kw):
+        if self.events is None:
+            return fn(*a, **kw)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = fn(*a, **kw)
+        e1.record()
+        self.events.append((name, e0, e1))
+        return r
+
+    def _pinned(self, which: str, nbytes: int) -> torch.Tensor:
+        buf = getattr(self, which)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            setattr(self, which, buf)
+        return buf[:nbytes]
+
+    def _upload(self, arrays: List[np.ndarray], H: int, W: int) -> torch.Tensor:
+        B = len(arrays)
+        stage = self._pinned("_pin_in", B * H * W).view(B, H, W)
+        host = stage.numpy()
+        for i, a in enumerate(arrays):
+            host[i] = a
+        dev = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        dev.copy_(stage, non_blocking=True)
+        return dev
+
+    @staticmethod
+    def _conv3x3_variant(B: int, h: int, w: int, cin: int, cout: int, bf16: bool) -> int:
+        """Which forward kernel conv3x3_fwd_dispatch (csrc/conv3x3.hip) gives a layer: its rules that look at the number
+        of 16 x 16 tiles, restated.  0 = not an MFMA shape (no rule depends on B)."""
+        es = 2 if bf16 else 4
+        if cout % 64 or cin % (64 // es):
+            return 0
+        if B * h * w * max(cin, cout) * es >= (1 << 31) - 4096:
+            return 5                                                   # past the 2 GiB buffer window: the older kernel
+        ntile = B * ((h + 15) // 16) * ((w + 15) // 16)
+        if cout % 128 == 0 and ntile * (cout // 128) >= 512:
+            return 1                                                   # 128-channel slabs
+        if bf16 and cin == 64:
+            return 2                                                   # register-resident filter
+        nchunk = cin // 32
+        if bf16 and cin % 32 == 0 and ntile * (cout // 64) <= 256 and nchunk >= 8 and nchunk % 2 == 0:
+            return 3                                                   # K split over the two halves of the workgroup
+        return 4
+
+    def _layers(self):
+        """(kind, module, pyramid levels it may sit at) for the layers whose kernel choice can depend on B."""
+        if self._layer_levels is None:
+            depth = getattr(self.model, "depth", None)
+            if depth is None:
+                depth = sum(1 for n, _ in self.model.named_children() if n.startswith("down"))
+            out = []
+            for name, m in self.model.named_modules():
+                is_t = isinstance(m, torch.nn.ConvTranspose2d)
+                if not is_t and not (isinstance(m, torch.nn.Conv2d) and tuple(m.kernel_size) == (3, 3)):
+                    continue
+                top = name.split(".")[0]
+                if top == "inc":
+                    levels = [0]
+                elif top.startswith("down") and top[4:].isdigit():
+                    levels = [int(top[4:])]
+                elif top.startswith("up") and top[2:].isdigit():
+                    # block j works at level depth - j; its transposed convolution reads the level below
+                    levels = [depth - int(top[2:]) + (1 if is_t else 0)]
+                else:
+                    levels = list(range(0, depth + 1))                 # unknown place: every level is checked
+                out.append(("convt" if is_t else "conv", m, levels))
+            self._layer_levels = out
+        return self._layer_levels
+
+    def launch_lengths(self, H: int, W: int) -> List[int]:
+        """The launch lengths B <= batch at which an H x W image is computed by the kernels it gets alone (1 always is)."""
+        key = (int(H), int(W))
+        if key not in self._lengths:
+            from ._lib import LIB, UH_BF16, UH_F32
+            dt = UH_BF16 if self.amp else UH_F32
+
+            def choice(B, kind, m, k):
+                h, w = H >> k, W >> k
+                if h < 1 or w < 1:
+                    return 0
+                if kind == "convt":
+                    return LIB.query("uh_convt2x2_mfma_ok", B, h, w, m.in_channels, m.out_channels, H >> (k - 1), W >> (k - 1), dt)
+                return self._conv3x3_variant(B, h, w, m.in_channels, m.out_channels, self.amp)
+
+            self._lengths[key] = [B for B in range(1, self.batch + 1)
+                                  if all(choice(B, kind, m, k) == choice(1, kind, m, k)
+                                         for kind, m, levels in self._layers() for k in levels if k >= (1 if kind == "convt" else 0))]
+        return self._lengths[key]
+
+    def _forward(self, x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+        from .inference import GraphedForward
+        full = self.launch_lengths(*size)[-1]                          # the longest launch this size allows
+        size = (x.shape[0],) + tuple(size)
+        if x.shape[0] == full and size in self._seen:
+            g = self._graphs.pop(size, None)
+            if g is None:
+                while len(self._graphs) >= self.MAX_GRAPHS:
+                    self._graphs.popitem(last=False)                  # least recently used
+                g = GraphedForward(self.model, x, amp=self.amp)
+            self._graphs[size] = g
+            self.graph_replays += 1
+            return g(x)
+        if x.shape[0] == full:
+            self._seen.add(size)
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.amp):
+            return self.model(x)
+
+    def run_batch(self, arrays: List[np.ndarray], grey: bool = True) -> np.ndarray:
+        """One batch of equally sized uint8 [H,W] images -> uint8 [B,H,W] on the host (grey-coded, or class indices), in as
+        few launches as launch_lengths allows."""
+        H, W = arrays[0].shape
+        lengths = self.launch_lengths(H, W)
+        if len(arrays) in lengths:
+            return self._launch(arrays, grey)
+        out, s = [], 0
+        while s < len(arrays):
+            b = max(v for v in lengths if v <= len(arrays) - s)
+            out.append(self._launch(arrays[s:s + b], grey))
+            s += b
+        return np.concatenate(out)
+
+    def _launch(self, arrays: List[np.ndarray], grey: bool) -> np.ndarray:
+        H, W = arrays[0].shape
+        B = len(arrays)
+        with torch.cuda.device(self.device):
+            img = self._mark("upload", self._upload, arrays, H, W)
+            x = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
+            flags = self._flags if B <= self._flags.numel() else torch.empty(B, dtype=torch.int32, device=self.device)
+            self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
+            logits = self._mark("forward", self._forward, x, (H, W))
+            if tuple(logits.shape[-2:]) != (H, W):
+                raise RuntimeError(f"the network returned {tuple(logits.shape[-2:])} for a {(H, W)} input")     # predict.py:26 is dead at scale 1
+            cls = self._mark("classes", ops.logits_to_classes_u8, logits)
+            if self.postprocess:
+                from .utils.post_process import _run as _postprocess_run
+                cls = self._mark("postprocess", _postprocess_run, cls, self.min_area, self.ksize)
+            if grey:
+                self._mark("grey", ops.classes_to_grey_u8, cls, self._lut, cls)
+            out = self._pinned("_pin_out", B * H * W).view(B, H, W)
+            self._mark("download", out.copy_, cls, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            return out.numpy().copy()
+
+    def _run(self, images, grey: bool) -> List[np.ndarray]:
+        arrays = [_as_grey_array(im) for im in images]
+        result: List[Optional[np.ndarray]] = [None] * len(arrays)
+        for _, members in plan_batches([a.shape for a in arrays], self.batch):
+            out = self.run_batch([arrays[i] for i in members], grey)
+            for k, i in enumerate(members):
+                result[i] = out[k]
+        return result
+
+    def __call__(self, images) -> List[np.ndarray]:
+        return self._run(images, True)
+
+    def classes(self, images) -> List[np.ndarray]:
+        return self._run(images, False)
+
+
+def main(argv=None) -> int:
+    """`python -m unet_amd.predict ...`: the reference's predict.py command line (predict_cli.py)."""
+    from .predict_cli import main as _main
+    return _main(argv)
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

@@ -1,0 +1,214 @@
+"""The reference's prediction command line, /root/reference/predict.py:31-152, on the HIP path:
+
+    python -m unet_amd.predict -m model.pth -i FILE_OR_DIR [-o OUT] [-n] [-v] [--no-postprocess]
+                               [--arch UNet] [-c 3] [--bilinear] [--no-amp] [-b 8] [--workers 8]
+
+Every image is predicted at its own size (scale 1).  The images of a folder are decoded by a thread pool, grouped by size,
+run through BatchPredictor in batches (prepare, eval forward, classes, post-processing and grey coding on the device, one
+upload and one download per batch) and encoded to PNG by the same pool while the next batch runs.
+
+Reference behaviour that is kept, awkward parts included:
+  - predict.py:33-38  the flags -m, -i (both required), -o, -v, -n, and -p, a store_true whose default is already True;
+                      --no-postprocess is the way to turn it off here;
+  - predict.py:61-68  a directory is walked recursively (os.walk order) for .png / .jpg / .jpeg, case-insensitive;
+  - predict.py:76-84  a missing input path or a directory without images: an error message and exit status 1;
+  - predict.py:93-98  .pt (TorchScript) models: REFUSED here with exit status 1, no TorchScript path exists on this port;
+  - predict.py:99-109 .pth: UNet(n_channels=1, n_classes=3, bilinear=False) by default (--arch / --classes / --bilinear
+                      select another network), a `mask_values` key is dropped before load_state_dict;
+  - predict.py:110-116 any other suffix, or a checkpoint that does not load: exit status 1;
+  - predict.py:122    every image is opened and converted to "L";
+  - predict.py:43-49  without -o the mask is written next to the input as <stem>.png, which overwrites a PNG input; with
+                      -o every mask goes flat into that directory as <stem>.png, so equal stems of different sub-directories
+                      collide and the later one in discovery order wins.  Files are written in discovery order whatever
+                      order the size groups finished in, so the winner is the reference's;
+  - predict.py:146-147 a file that fails is logged with its name and skipped, the others are written, exit status 0;
+  - predict.py:141-144 --viz needs matplotlib, imported lazily: where it is absent the command says so and exits 1 before
+                      any prediction is made.  The figure is a plain image / mask pair, not utils.plot_img_and_mask.
+There is no CPU fallback: without a GPU the command exits with status 2 (after the argument, input and model checks)."""
+from __future__ import annotations
+
+import argparse
+import logging
+import os
+import sys
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+from typing import List, Optional
+
+import numpy as np
+
+ARCHS = ("UNet", "UNet_S", "UNet_T", "UNet_SA")
+EXTENSIONS = (".png", ".jpg", ".jpeg")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Predict multi-class masks for an image or a directory of images")
+    # the reference's flags, short forms and defaults (predict.py:31-40)
+    p.add_argument("--model", "-m", required=True, help="Model weights (.pth state_dict)")
+    p.add_argument("--input", "-i", required=True, help="Input image file or directory (walked recursively)")
+    p.add_argument("--output", "-o", help="Output directory (default: <stem>.png next to each input, overwriting a PNG input)")
+    p.add_argument("--viz", "-v", action="store_true", default=False, help="Show each result (needs matplotlib)")
+    p.add_argument("--no-save", "-n", action="store_true", default=False, help="Do not write the masks")
+    p.add_argument("--postprocess", "-p", action="store_true", default=True, help="Apply post-processing (the default)")
+    # additions; the defaults are what predict.py hard-codes
+    p.add_argument("--no-postprocess", dest="postprocess", action="store_false", help="Write the raw argmax classes")
+    p.add_argument("--arch", choices=ARCHS, default="UNet", help="Network (predict.py:107 builds UNet)")
+    p.add_argument("--classes", "-c", type=int, default=3, help="Number of classes")
+    p.add_argument("--bilinear", action="store_true", default=False, help="Bilinear upsampling")
+    p.add_argument("--no-amp", dest="amp", action="store_false", default=True, help="Run the forward in fp32 (default: bf16 autocast)")
+    p.add_argument("--batch-size", "-b", dest="batch_size", type=int, default=8, help="Images of one size per device batch")
+    p.add_argument("--workers", type=int, default=8, help="Decode / encode threads")
+    return p
+
+
+def get_args(argv=None) -> argparse.Namespace:
+    return build_parser().parse_args(argv)
+
+
+def output_path(output: Optional[str], input_file: str) -> str:
+    """predict.py:43-49."""
+    base_name = os.path.splitext(os.path.basename(input_file))[0]
+    if output is None:
+        return os.path.join(os.path.dirname(input_file), f"{base_name}.png")
+    return os.path.join(output, f"{base_name}.png")
+
+
+def discover(input_dir: str) -> List[str]:
+    """predict.py:61-68: every .png / .jpg / .jpeg under input_dir, in os.walk order."""
+    image_files = []
+    for root, _, files in os.walk(input_dir):
+        for file in files:
+            if file.lower().endswith(EXTENSIONS):
+                image_files.append(os.path.join(root, file))
+    return image_files
+
+
+def decode(path: str) -> np.ndarray:
+    """predict.py:122: Image.open(path).convert('L'), as a uint8 [H,W] array."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("L"))
+
+
+def _show(plt, path, img, grey):
+    fig, ax = plt.subplots(1, 2)
+    ax[0].set_title(os.path.basename(path))
+    ax[0].imshow(img, cmap="gray")
+    ax[1].set_title("mask")
+    ax[1].imshow(grey, cmap="gray", vmin=0, vmax=255)
+    plt.show()
+
+
+def run(predictor, files: List[str], output: Optional[str], save: bool, workers: int, show=None, window: Optional[int] = None):
+    """Predicts `files` and writes the masks.  -> (written paths in write order, failed input paths)."""
+    from .predict import BatchPlanner
+    from .utils.png_writer import OrderedPngWriter
+    workers = max(1, int(workers))
+    failed: List[str] = []
+    planner = BatchPlanner(predictor.batch, window if window is not None else 16 * predictor.batch)
+    held = {}
+    with ThreadPoolExecutor(max_workers=workers, thread_name_prefix="predict-io") as pool:
+        writer = OrderedPngWriter(pool=pool)
+
+        def finish(members):
+            imgs = [held.pop(i) for i in members]
+            out = predictor.run_batch(imgs)
+            for k, i in enumerate(members):
+                if save:
+                    writer.submit(i, output_path(output, files[i]), out[k])
+                else:
+                    writer.skip(i)
+                if show is not None:
+                    show(files[i], imgs[k], out[k])
+
+        ahead = max(2 * predictor.batch, 2 * workers)             # decodes in flight beyond the one being waited for
+        pending = deque()
+        nxt = 0
+        for i in range(len(files)):
+            while nxt < len(files) and len(pending) < ahead:
+                pending.append(pool.submit(decode, files[nxt]))
+                nxt += 1
+            fut = pending.popleft()
+            logging.info("Predicting image %s", files[i])
+            try:
+                img = fut.result()
+            except Exception as e:                                # predict.py:146-147: logged with its name, the run goes on
+                logging.error("Error while processing image %s: %s", files[i], e)
+                failed.append(files[i])
+                writer.skip(i)
+                continue
+            held[i] = img
+            for _, members in planner.add(i, img.shape):
+                finish(members)
+        for _, members in planner.flush():
+            finish(members)
+        written = writer.close()
+    return written, failed
+
+
+def main(argv=None) -> int:
+    args = get_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(levelname)s: %(message)s")
+    # input (predict.py:76-86)
+    if os.path.isdir(args.input):
+        in_files = discover(args.input)
+        logging.info("Found %d image files in the directory", len(in_files))
+        if not in_files:
+            logging.error("No image file found in directory %s", args.input)
+            return 1
+    else:
+        if not os.path.isfile(args.input):
+            logging.error("Input file does not exist: %s", args.input)
+            return 1
+        in_files = [args.input]
+    if args.batch_size < 1 or args.workers < 1:
+        logging.error("--batch-size and --workers must be at least 1")
+        return 1
+    # model format (predict.py:93-116); checked before anything touches the device
+    if args.model.endswith(".pt"):
+        logging.error("TorchScript models (.pt) are not supported: %s. This port runs .pth state_dicts through its HIP "
+                      "kernels; there is no TorchScript path.", args.model)
+        return 1
+    if not args.model.endswith(".pth"):
+        logging.error("Unsupported model format: %s (only .pth state_dicts are supported)", args.model)
+        return 1
+    plt = None
+    if args.viz:
+        try:
+            import matplotlib.pyplot as plt                        # lazily: the package does not depend on it
+        except ImportError:
+            logging.error("--viz needs matplotlib, which is not installed; nothing was predicted")
+            return 1
+    import torch
+    from .checkpoint import load_checkpoint
+    from .train_cli import build_model
+    try:
+        if args.classes < 2:
+            raise ValueError("predict.py takes argmax(dim=1): it needs a multi-class head (--classes >= 2); binary models "
+                             "are scored and dumped by unet_amd.evaluate(..., epoch_pred_dir=...)")
+        model = build_model(args.arch, args.classes, args.bilinear)
+        load_checkpoint(model, args.model, device="cpu")              # mask_values dropped (predict.py:106-108)
+        model.eval()
+    except Exception as e:
+        logging.error("Failed to load the model %s: %s", args.model, e)
+        return 1
+    logging.info("Model loaded: %s, %d classes, %s upscaling", args.arch, args.classes,
+                 "bilinear" if args.bilinear else "transposed conv")
+    if not torch.cuda.is_available():
+        logging.error("predict: no GPU found. This port predicts on the MI355X through its HIP kernels and has no CPU path.")
+        return 2
+    from .predict import BatchPredictor
+    device = torch.device("cuda", torch.cuda.current_device())
+    logging.info("Using device %s", device)
+    predictor = BatchPredictor(model, batch=args.batch_size, postprocess=args.postprocess, amp=args.amp, device=device)
+    if args.output is not None and not args.no_save:
+        os.makedirs(args.output, exist_ok=True)                       # predict.py:48
+    show = (lambda path, img, grey: _show(plt, path, img, grey)) if plt is not None else None
+    written, failed = run(predictor, in_files, args.output, not args.no_save, args.workers, show)
+    logging.info("%d of %d images predicted, %d masks written%s", len(in_files) - len(failed), len(in_files), len(written),
+                 f", {len(failed)} failed" if failed else "")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

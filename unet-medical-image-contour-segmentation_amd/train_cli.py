@@ -2,6 +2,7 @@
 
     python -m unet_amd.train -e 5 -b 1 -l 1e-5 -s 0.5 -c 3 [--bilinear] [-f model.pth] [--no-amp]
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
+                             [--pred-dir DIR]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -11,6 +12,8 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     (train.py:174-187: it can fall mid-epoch or more than once per epoch), then lr = cosine_warm_restarts_lr(lr, dice);
   - checkpoint_dir/checkpoint_epoch{E}.pth when E > epochs / 2 and E % 5 == 0, with mask_values = train + val
     (train.py:208-216); model_epoch{epochs}.pth, a plain state_dict, in the working directory (train.py:220);
+  - --pred-dir DIR (default: off) passes DIR/epoch_{epoch} to evaluate as train.py:99-100 does with ./predictions: the
+    validation predictions of every evaluation are written there as grey-coded PNGs (evaluate.py:88-105, 146-164);
   - --load drops mask_values (train.py:275-280); -v is accepted and unused, as in the reference.
 Input batches come from DeviceBatchLoader: decode threads, pinned collation, rotation + BICUBIC / NEAREST rescale + /255
 + label remap on the device (csrc/data_rescale.hip, csrc/data_prep.hip), bit-identical to stacking ds[i].
@@ -53,6 +56,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--checkpoint-dir", default="./checkpoints", help="Where checkpoint_epoch{E}.pth files go")
     p.add_argument("--workers", type=int, default=8, help="Decode threads per loader")
     p.add_argument("--seed", type=int, default=None, help="Seeds model init and shuffling (default: unseeded)")
+    p.add_argument("--pred-dir", default=None,
+                   help="Write the validation predictions of every evaluation to DIR/epoch_{epoch} as PNGs (default: off)")
     return p
 
 
@@ -90,7 +95,7 @@ def build_model(name: str, n_classes: int, bilinear: bool):
 
 def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: int, learning_rate: float, amp: bool,
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
-                 train_loader=None, log=None) -> List[Dict]:
+                 train_loader=None, log=None, pred_dir: Optional[str] = None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating."""
@@ -124,7 +129,8 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
             if eval_due(global_step, n_train, batch_size):
                 torch.cuda.synchronize(device)
                 te = time.perf_counter()
-                val_score, val_post, val_min = evaluate(model, val_loader, device, amp)          # postprocess=True
+                epoch_pred_dir = os.path.join(pred_dir, f"epoch_{epoch}") if pred_dir else None  # train.py:99-100
+                val_score, val_post, val_min = evaluate(model, val_loader, device, amp, epoch_pred_dir)   # postprocess=True
                 lr = cosine_warm_restarts_lr(learning_rate, float(val_score))                    # scheduler.step(val_score)
                 stepper.optimizer.param_groups[0]["lr"] = lr
                 dice = (float(val_score), float(val_post), float(val_min))
@@ -179,7 +185,8 @@ def main(argv=None) -> int:
                  f"training items {n_train}, validation items {n_val}, scale {args.scale}, "
                  f"{'bf16 autocast' if args.amp else 'fp32'}, checkpoints in {args.checkpoint_dir}")
     run_training(model, device, train_set, val_set, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.lr,
-                 amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed, workers=args.workers, log=logging.info)
+                 amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed, workers=args.workers, log=logging.info,
+                 pred_dir=args.pred_dir)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")
