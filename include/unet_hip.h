@@ -80,6 +80,13 @@ int uh_conv3x3_stat_slabs(int B, int H, int W, int Cin, int Cout, int dt);
 /* 1 if uh_conv3x3_fwd will run this shape on the LDS-DMA MFMA kernel (16-byte aligned pointers assumed), i.e. if the
  * filter may be packed fragment-major (UH_WFRAG); dt = UH_F32 or UH_BF16. */
 int uh_conv3x3_wfrag_ok(int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, int dt);
+/* Which kernel uh_conv3x3_fwd (and, with the backward-data filter pack, backward-data) gives a call with dense pitches
+ * (ld0 = C0, ld1 = C1, ldy = Cout) and 16-byte aligned pointers; host only, no device touched.  dt = UH_F32, UH_BF16 or
+ * UH_F32X3.  0 = not an MFMA shape (stem or generic kernel), 1 = 128-channel slabs, 2 = register-resident filter, 3 = K split
+ * inside the workgroup, 4 = streaming filter, 5 = a tensor past the 2 GiB buffer window (the older MFMA kernel).  The kernels
+ * sum in different orders: a batch gives bit-identical per-image results only where every layer gets the same answer as for
+ * one image (BatchPredictor.launch_lengths).  UH_EINVAL for a bad shape or dtype. */
+int uh_conv3x3_fwd_kernel(int B, int H, int W, int C0, int C1, int Cout, int dt);
 int uh_conv3x3_fwd(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1,
                    const void* w, void* y, int ldy, int Cout, float* stat_partials,
                    int B, int H, int W, int dt, uh_stream stream);

@@ -538,29 +538,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_mfma(
 //     window of 3 rows); the filter fragments of the next column shift are prefetched under the current one;
 //   * BatchNorm (mean, M2) per tile and channel come straight from the accumulator registers + 4 shuffles.
 // =====================================================================================
-// Diagnostic builds (scratch/r5_mklib.py NAME -DUH_ABL_X=1, scratch/r5_ablate.sh): each switch removes ONE class of work from the
-// forward / backward-data kernel's tile loop -- results are garbage, launch times say what that work costs where it sits.
-//   UH_ABL_NOW     no filter-fragment loads inside the chunk loop       UH_ABL_NODMA   no halo DMA inside the loop
-//   UH_ABL_NOLDS   no pixel-fragment LDS reads (opaque stale registers) UH_ABL_NOMFMA  no MFMAs
-//   UH_ABL_NOSTORE no output stores                                     UH_ABL_NOSTATS no BatchNorm statistics
-#ifndef UH_ABL_NOW
-#define UH_ABL_NOW 0
-#endif
-#ifndef UH_ABL_NODMA
-#define UH_ABL_NODMA 0
-#endif
-#ifndef UH_ABL_NOLDS
-#define UH_ABL_NOLDS 0
-#endif
-#ifndef UH_ABL_NOMFMA
-#define UH_ABL_NOMFMA 0
-#endif
-#ifndef UH_ABL_NOSTORE
-#define UH_ABL_NOSTORE 0
-#endif
-#ifndef UH_ABL_NOSTATS
-#define UH_ABL_NOSTATS 0
-#endif
 constexpr int HALO2_BYTES = HALO_PIX * 64;   // 20736
 constexpr int HALO2_STRIDE = 6 * 4096;       // LDS bytes per halo buffer: six 4 KiB DMA rounds of 256 threads (the tail is padding)
 constexpr unsigned OOB_OFFSET = 0xF0000000u;
@@ -657,22 +634,16 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
     constexpr int BN = NBW * 64;
     constexpr int NPIECE = HALO_PIX * 4;     // 1296
     constexpr int NLOAD = 6;
-#ifndef UH_FWD_PF
-#define UH_FWD_PF 2
-#endif
     // LDS fragment prefetch distance in halo rows.  Two rows ahead (192 cycles of MFMA issue at NBW = 2 instead of 96): +0.3 % on
     // the train step in three interleaved rounds (856.5 -> 858.9 images/s, round 4); the register-resident-filter form has no four
     // registers to spare for it (it spills inside its MFMA stream at distance 2) and keeps one row.
-    constexpr int PF = WRES ? 1 : UH_FWD_PF;
+    constexpr int PF = WRES ? 1 : 2;
 
-#ifndef UH_WRES_TRI
-#define UH_WRES_TRI 1
-#endif
     // TRI (the register-resident-filter form): THREE halo buffers, the DMA runs two chunks = one whole tile ahead.  With 16 channels
     // per wave a chunk is 144 MFMAs, and the two column shifts a double-buffered DMA has to land under (96 MFMAs, ~1 us beside the
     // SIMD's other wave) are shorter than an HBM round trip under load: the 64 -> 64 layers at 512 x 512 waited at every chunk fence
     // (scratch/r4_bsum_bench.sh with the cached-input variant: 141 -> 115 us per launch).  72 KB per workgroup, two per CU.
-    constexpr bool TRI = WRES && !PRE && UH_WRES_TRI;
+    constexpr bool TRI = WRES && !PRE;
     __shared__ __attribute__((aligned(16))) unsigned char lds_all[(TRI ? 3 : KS * 2) * HALO2_STRIDE];
     // BatchNorm statistics of this workgroup's channels over ALL the tiles it processes, as pivot-shifted sums
     // S1 = sum (v - p), S2 = sum (v - p)^2 with p = one stored value of the channel (so that |mean - p| ~ std and the
@@ -697,13 +668,10 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
     const int nslab = Cout / BN;
     const int nlanes = gridDim.x / nslab;
     int tile_lane, slab;
-#ifndef UH_XCD_BLOCK
-#define UH_XCD_BLOCK 0      // experiment (round 5): 1 = an XCD owns a CONTIGUOUS range of tile lanes (horizontally adjacent tiles share its L2), 0 = lanes dealt round-robin
-#endif
     if ((nlanes & 7) == 0) {
         const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
         slab = jj % nslab;
-        tile_lane = UH_XCD_BLOCK ? xcd * (nlanes >> 3) + jj / nslab : (jj / nslab) * 8 + xcd;
+        tile_lane = (jj / nslab) * 8 + xcd;
     } else {
         slab = blockIdx.x / nlanes;
         tile_lane = blockIdx.x - slab * nlanes;
@@ -738,7 +706,6 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
     int rel0[NLOAD];
 #pragma unroll
     for (int k = 0; k < NLOAD; ++k) rel0[k] = REL_LIVE ? rel_of(tid, k) : 0;
-    bool abl_first_dma = true; (void)abl_first_dma;
     // tile the NEXT DMA reads from (scalars): image, top-left pixel, "halo inside the image"
     int d_b = 0, d_y0 = 0, d_x0 = 0;
     bool d_in = false;
@@ -754,9 +721,6 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
     // past the halo tile (and `live == false`: nothing left to fetch) read out of range, i.e. write zeros into the padding
     // of the buffer / into a buffer nobody reads.
     auto dma_chunk = [&](int c, int bufi, bool live) {
-#if UH_ABL_NODMA
-        if (!abl_first_dma) return;
-#endif
         const int cc = c * CK;
         const bool first = cc < C0;
         const int ld = first ? ld0 : ld1;
@@ -946,11 +910,7 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
             wA[r][n].v = wB[r][n].v = wC[r][n].v = u32x4{0u, 0u, 0u, 0u};
             wA[r][n].hi = wB[r][n].hi = wC[r][n].hi = wA[r][n].lo = wB[r][n].lo = wC[r][n].lo = u32x2{0u, 0u};
         }
-    bool abl_first = true; (void)abl_first;
     auto load_w = [&](WFrag (&dst)[3][NBW], int chunk, int sft) {      // the three row taps of column shift `sft`, chunk `chunk`
-#if UH_ABL_NOW
-        if (!abl_first) return;
-#endif
         const int64_t wsrc = (int64_t)chunk * CK + (int64_t)sft * Cin;
 #pragma unroll
         for (int r = 0; r < 3; ++r)
@@ -966,13 +926,7 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
         int lq = lane;
         if constexpr (!REL_LIVE) asm volatile("" : "+v"(lq));       // (same register shortage: the three column offsets are not kept either)
         const unsigned char* xcol = buf + ((lq & 15) + sft) * 64 + (((lq >> 4) ^ halo_swz((lq & 15) + sft)) << 4);
-#if UH_ABL_NOLDS
-        u32x4 abl_x = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-        asm volatile("" : "+v"(abl_x));
-        auto rd = [&](int k) { u32x4 v = abl_x; asm volatile("" : "+v"(v)); (void)xcol; return v; };
-#else
         auto rd = [&](int k) { return *reinterpret_cast<const u32x4*>(xcol + k * (HALO_W * 64)); };
-#endif
 #pragma unroll
         for (int k = 0; k < 2 + PF; ++k) xf[k] = rd(k);
 #pragma unroll
@@ -989,12 +943,8 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
 #pragma unroll
                 for (int n = 0; n < NBW; ++n) {
                     if constexpr (ES == 2) {
-#if UH_ABL_NOMFMA
-                        asm volatile("" : "+v"(acc[i][n]) : "v"(xf[i + r]), "v"(wget(r, n).v));
-#else
                         acc[i][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                             __builtin_bit_cast(bf16x8, wget(r, n).v), __builtin_bit_cast(bf16x8, xf[i + r]), acc[i][n], 0, 0, 0);
-#endif
                     } else if constexpr (SPLIT) {
                         const s16x4 wh = __builtin_bit_cast(s16x4, wget(r, n).hi);
                         const s16x4 wlo = __builtin_bit_cast(s16x4, wget(r, n).lo);
@@ -1051,7 +1001,6 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
         __builtin_amdgcn_sched_barrier(0);
     }
     chunk_fence(chunk_of(v_first), 0, true);
-    abl_first = false; abl_first_dma = false;
 
     for (; tile < ntile; tile += nlanes) {
         if (KS == 2 && tile != tile_lane) break;     // (one tile per workgroup: the host sizes the grid that way)
@@ -1217,13 +1166,9 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
             constexpr bool BQ2 = NBW == 1;              // two batches in flight (NBW = 2: one at a time -- no time difference in an A/B of the three schedules, fewest spills)
             if constexpr (BQ2) bq_load(bqA, 0);
             float p1[4] = {0.f, 0.f, 0.f, 0.f}, p2[4] = {0.f, 0.f, 0.f, 0.f};
-#ifndef UH_BSUM_PK
-#define UH_BSUM_PK 1
-#endif
             auto bq_sum = [&](const u32x2 (&src)[8], int bi) {
                 const int n = bi >> 1, i0 = (bi & 1) * 8;
                 const int c0 = ch(kg_o, n, 0);
-#if UH_BSUM_PK
                 // two channels at a time as packed fp32 pairs (the two halves of a q dword, accumulators j, j + 1 = an aligned
                 // register pair): v_pk_fma / v_pk_add for the mask argument, q - mean and both sums -- 10 VALU instructions per
                 // pair and row instead of 14, every channel's operations and their order unchanged (bit-identical sums)
@@ -1259,33 +1204,6 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
                     }
                     __builtin_amdgcn_sched_barrier(0);       // one channel pair at a time
                 }
-#else
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float sc = bs_tab[0 * BN + c0 + j], sh = bs_tab[1 * BN + c0 + j], mu = bs_tab[2 * BN + c0 + j];
-                    float s1 = (bi & 1) ? p1[j] : 0.f, s2 = (bi & 1) ? p2[j] : 0.f;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const unsigned pk = src[i][j >> 1];
-                        const float qv = __uint_as_float((j & 1) ? (pk & 0xffff0000u) : (pk << 16));
-                        const bool on = fmaf(qv, sc, sh) > 0.f;                  // the ReLU mask, as uh_bn_relu_apply decided it
-                        const float g = on ? acc[i0 + i][n][j] : 0.f;            // acc: already rounded to the stored type
-                        s1 += g;
-                        s2 = fmaf(g, qv - mu, s2);
-                    }
-                    if (bi & 1) {
-                        const float a1 = uh_row16_sum(s1), a2 = uh_row16_sum(s2);
-                        if (lx_o == 0) {
-                            S1[c0 + j] += a1;
-                            S2[c0 + j] += a2;
-                        }
-                    } else {
-                        p1[j] = s1;
-                        p2[j] = s2;
-                    }
-                    __builtin_amdgcn_sched_barrier(0);       // one channel at a time (left free, the scheduler interleaves all four: +40 registers)
-                }
-#endif
             };
 #pragma unroll
             for (int bi = 0; bi < BQB; ++bi) {
@@ -1326,7 +1244,7 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
         // offset is ADDED to the vector offset instead of riding in the scalar-offset operand: a 16-byte buffer store with a
         // scalar offset register reads its data over several cycles, and hipcc (ROCm 7.2) let the next VALU instruction
         // overwrite the first data register behind the last store of the loop (wrong bf16 pairs in 8 lanes of one row pair).
-        if (!UH_ABL_NOSTORE) {
+        {
             const int rbytes = W * ldy * ES;                                   // one image row of y
             const int sbase = ((b * H + y0) * W) * ldy * ES;                   // row 0 of the tile, column 0
             if constexpr (PERM2) {
@@ -1405,7 +1323,7 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
 
         // ---- BatchNorm statistics: pivot-shifted sums per lane, 4 DPP adds per channel, accumulated in LDS by the lane that
         // owns the channel's slot (the same lane every tile: no barrier, a wave only touches its own channels)
-        if (!BSUM && stats && !UH_ABL_NOSTATS) {
+        if (!BSUM && stats) {
             float* S1 = &wg_sum[0][0];          // slot = channel - co_blk: a wave touches its own channels only
             float* S2 = &wg_sum[1][0];
             float* PV = &wg_sum[2][0];
@@ -1965,47 +1883,114 @@ extern "C" int uh_conv3x3_stat_slabs(int B, int H, int W, int Cin, int Cout, int
     return B * ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
 }
 
-// UH_NO_WRES=1 (A/B runs): the 64-input-channel layers take the streaming-filter instantiation instead of the
-// register-resident one.  Read once per process, not per launch.
-static bool uh_no_wres() {
-    static const bool off = getenv("UH_NO_WRES") != nullptr;
-    return off;
-}
-
-// Which bf16 instantiation of conv3x3_fwd_mfma_v2 a plain call takes and how many tile lanes (= workgroups per channel slab =
-// statistics / partial rows written) it is launched with.  Mirrors the branches of conv3x3_fwd_dispatch below.
 // K split inside the workgroup (KS = 2, see the kernel): bf16, 16 channels per wave, at most one (tile, 64-channel slab) pair
 // per CU and an even number (>= 8) of 32-channel K-chunks.  UH_NO_KSPLIT=1 turns it off (A/B runs).
-// UH_WRES_WIDE=1 (experiment, round 5): 64 input channels and 128+ output channels (down1.0 forward, backward-data of up4.0 / up3.3)
-// take the register-resident-filter form, one launch of 64-channel slabs, instead of the 32-channel-per-wave streaming form
-static bool uh_wres_wide() {
-    static const bool on = getenv("UH_WRES_WIDE") != nullptr && getenv("UH_WRES_WIDE")[0] == '1';
-    return on;
-}
-
 static bool fwd_ksplit_ok(int ntile, int Cin, int Cout) {
     static const bool off = getenv("UH_NO_KSPLIT") != nullptr && getenv("UH_NO_KSPLIT")[0] == '1';
     const int nchunk = Cin / 32;
     return !off && Cin % 32 == 0 && Cout % 64 == 0 && (int64_t)ntile * (Cout / 64) <= 256 && nchunk >= 8 && nchunk % 2 == 0;
 }
-struct FwdSel { int nbw; bool wres; int slabs; int gx; int ks; };
-static FwdSel fwd_select(int ntile, int Cin, int Cout, bool bf16_plain, bool bsum = false) {
+
+// The kernel a forward / backward-data call takes; the values are what uh_conv3x3_fwd_kernel answers.
+enum FwdKernel {
+    FWD_SIMT = 0,        // not an MFMA shape: a stem kernel (Cin <= 4, one source) or conv3x3_fwd_generic
+    FWD_SLAB128 = 1,     // conv3x3_fwd_mfma_v2, NBW = 2: 128-channel slabs
+    FWD_WRES = 2,        // conv3x3_fwd_mfma_v2, WRES: the filter stays in registers (bf16, 64 input channels)
+    FWD_KSPLIT = 3,      // conv3x3_fwd_mfma_v2, KS = 2: few tiles, long contraction -- the two halves of an 8-wave workgroup
+                         // contract half of the K-chunks each, one tile per workgroup
+    FWD_STREAM = 4,      // conv3x3_fwd_mfma_v2, NBW = 1: 64-channel slabs, filter fragments streamed
+    FWD_LARGE = 5,       // conv3x3_fwd_mfma: a tensor or the filter pack past the 2 GiB window of a buffer descriptor
+};
+
+struct FwdPlan {
+    FwdKernel kernel;
+    int stem;                 // FWD_SIMT: 3 / 2 / 1 = conv3x3_fwd_stem_v3 / conv3x3_fwd_stem_v2 / conv3x3_fwd_stem, 0 = generic
+    int slabs, lanes;         // grid: output-channel slabs x tile lanes.  The conv3x3_fwd_mfma_v2 forms write one statistics /
+                              // partial row per tile lane, the other kernels one per tile (lanes = tiles)
+    int threads;              // workgroup size
+    bool split, pre, bsum;    // the call's family (see conv3x3_fwd_dispatch): bf16x3 products, BatchNorm+ReLU input, BatchNorm sums
+};
+
+// The one place that decides which kernel a forward / backward-data call gets and its grid: every entry point below and the
+// queries uh_conv3x3_fwd_kernel, uh_conv3x3_wfrag_ok and uh_conv3x3_dgrad_bnsum_rows take it from here.  es = element size;
+// ptrs16 = x0, x1, w and y are 16-byte aligned; y16 = y is.  The differences between the entry points are inputs: only plain
+// bf16 calls (no bf16x3 products, no narrow tensors) keep the filter in registers or split K, PRE never splits K, and BSUM runs
+// two workgroups per CU.
+static FwdPlan fwd_plan(int es, int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, bool ptrs16, bool y16,
+                        bool split, bool narrow, bool pre, bool bsum) {
+    const int ntile = B * ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
+    const int ck = 64 / es, Cin = C0 + C1;
+    FwdPlan p = {FWD_SIMT, 0, 1, ntile, 256, split, pre, bsum};
+    const bool mfma = C0 % ck == 0 && C1 % ck == 0 && Cout % 64 == 0 && ptrs16 && (ld0 * es) % 16 == 0 &&
+                      (C1 == 0 || (ld1 * es) % 16 == 0) && (ldy * es) % 16 == 0;
+    if (!mfma) {
+        const bool y_ok = y16 && (ldy * es) % 16 == 0;
+        if (Cin > 4 || C1 != 0) p.stem = 0;
+        else if (es == 2 && Cout == 64 && y_ok) { p.stem = 3; p.lanes = ntile < 1024 ? ntile : 1024; }
+        else p.stem = (Cout % (16 / es) == 0 && y_ok) ? 2 : 1;
+        return p;
+    }
+    // the LDS-DMA kernel addresses x0, x1, y and the filter pack through buffer descriptors (32-bit offsets)
+    const int64_t px = (int64_t)B * H * W, lim = (1ll << 31) - 4096;
+    if (px * ld0 * es >= lim || (C1 && px * ld1 * es >= lim) || px * ldy * es >= lim ||
+        (int64_t)Cout * 9 * Cin * (split ? 4 : es) >= lim) {
+        p.kernel = FWD_LARGE;
+        p.slabs = Cout % 128 == 0 ? Cout / 128 : Cout / 64;
+        return p;
+    }
+    // persistent workgroups: 2 (NBW = 2, WRES and BSUM: VGPR-bound) or 3 (NBW = 1) per CU, spread over the channel slabs; the
+    // number of tile lanes is rounded to a multiple of 8 for the XCD-aware mapping inside the kernel
     auto lanes_for = [&](int per_cu, int slabs) {
         int gx = (per_cu * 256 + slabs - 1) / slabs;
         gx = (gx + 7) & ~7;
-        if (gx > ntile) gx = ntile;
-        return gx;
+        return gx < ntile ? gx : ntile;
     };
-    FwdSel r;
-    r.ks = 1;
-    const bool wres_first = bf16_plain && Cin == 64 && !uh_no_wres() && uh_wres_wide();
-    if (!wres_first && Cout % 128 == 0 && (int64_t)ntile * (Cout / 128) >= 512) { r.nbw = 2; r.wres = false; r.slabs = Cout / 128; r.gx = lanes_for(2, r.slabs); }
-    else if (bf16_plain && Cin == 64 && !uh_no_wres()) { r.nbw = 1; r.wres = true; r.slabs = Cout / 64; r.gx = lanes_for(2, r.slabs); }
-    else {
-        r.nbw = 1; r.wres = false; r.slabs = Cout / 64; r.gx = lanes_for(bsum ? 2 : 3, r.slabs);
-        if (bf16_plain && fwd_ksplit_ok(ntile, Cin, Cout)) { r.ks = 2; r.gx = ntile; }      // one tile per (8-wave) workgroup
+    const bool bf16 = es == 2 && !split && !narrow;
+    if (Cout % 128 == 0 && (int64_t)ntile * (Cout / 128) >= 512) {
+        // 128-channel slabs halve the halo re-reads, but small feature maps need the extra workgroups
+        p.kernel = FWD_SLAB128; p.slabs = Cout / 128; p.lanes = lanes_for(2, p.slabs);
+    } else if (bf16 && Cin == 64) {
+        p.kernel = FWD_WRES; p.slabs = Cout / 64; p.lanes = lanes_for(2, p.slabs);      // (72 more VGPRs)
+    } else if (bf16 && !pre && fwd_ksplit_ok(ntile, Cin, Cout)) {
+        p.kernel = FWD_KSPLIT; p.slabs = Cout / 64; p.lanes = ntile; p.threads = 512;
+    } else {
+        p.kernel = FWD_STREAM; p.slabs = Cout / 64; p.lanes = lanes_for(bsum ? 2 : 3, p.slabs);
     }
-    return r;
+    return p;
+}
+
+// One conv3x3_fwd_mfma_v2 launch in the form p.kernel of one family; args = the kernel's arguments.  Only the combinations that
+// exist are instantiated: the register-resident filter and the K split are bf16 forms, and PRE has no K split.
+template <typename T, bool SPLIT, bool PRE, bool BSUM, typename... Args>
+static void fwd_v2_form(const FwdPlan& p, hipStream_t st, Args... args) {
+    constexpr bool BF16 = sizeof(T) == 2 && !SPLIT;
+    const dim3 grid(p.lanes * p.slabs), block(p.threads);
+    switch (p.kernel) {
+    case FWD_SLAB128: hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 2, SPLIT, false, PRE, BSUM>), grid, block, 0, st, args...); break;
+    case FWD_WRES:
+        if constexpr (BF16) hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, true, PRE, BSUM>), grid, block, 0, st, args...);
+        break;
+    case FWD_KSPLIT:
+        if constexpr (BF16 && !PRE) hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, false, false, BSUM, 2>), grid, block, 0, st, args...);
+        break;
+    case FWD_STREAM: hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, SPLIT, false, PRE, BSUM>), grid, block, 0, st, args...); break;
+    default: break;
+    }
+}
+
+// The families: fp32 and bf16 plain calls, bf16x3 products (fp32 tensors), PRE (bf16, UH_BUILD_PRE builds only), BSUM (bf16).
+template <typename T, typename... Args>
+static void fwd_v2_launch(const FwdPlan& p, hipStream_t st, Args... args) {
+    constexpr bool BF16 = sizeof(T) == 2;
+    if (p.split) {
+        if constexpr (!BF16) fwd_v2_form<T, true, false, false>(p, st, args...);
+    } else if (p.bsum) {
+        if constexpr (BF16) fwd_v2_form<T, false, false, true>(p, st, args...);
+    } else if (p.pre) {
+        if constexpr (BF16 && UH_BUILD_PRE) fwd_v2_form<T, false, true, false>(p, st, args...);
+    } else {
+        fwd_v2_form<T, false, false, false>(p, st, args...);
+    }
 }
 
 template <typename T>
@@ -2023,174 +2008,79 @@ static int conv3x3_fwd_dispatch(const T* x0, int C0, int ld0, const T* x1, int C
     // runs the separate scale/shift/ReLU pass
     *ep_done = false;
     constexpr int ES = sizeof(T);
-    constexpr int CK = 64 / ES;
     const int tilesX = (W + TILE - 1) / TILE, tilesY = (H + TILE - 1) / TILE;
-    const int ntile = B * tilesX * tilesY;
     const int Cin = C0 + C1;
-    const bool mfma_ok = (C0 % CK == 0) && (C1 % CK == 0) && (Cout % 64 == 0) && uh_aligned16(x0) &&
-                         (C1 == 0 || uh_aligned16(x1)) && uh_aligned16(w) && uh_aligned16(y) &&
-                         ((ld0 * ES) % 16 == 0) && (C1 == 0 || (ld1 * ES) % 16 == 0) && ((ldy * ES) % 16 == 0);
-    if (mfma_ok) {
-        const int64_t b0 = (int64_t)B * H * W * ld0 * ES, b1 = C1 ? (int64_t)B * H * W * ld1 * ES : 0;
-        // y and the filter pack are addressed through buffer descriptors as well (32-bit offsets)
-        const int64_t by = (int64_t)B * H * W * ldy * ES, bw = (int64_t)Cout * 9 * Cin * (split ? 4 : ES);
-        if (b0 < (1ll << 31) - 4096 && b1 < (1ll << 31) - 4096 && by < (1ll << 31) - 4096 && bw < (1ll << 31) - 4096) {
-            // 128-channel slabs halve the halo re-reads, but small feature maps need the extra workgroups
-            // persistent workgroups: 2 (NBW=2, VGPR-bound) or 3 (NBW=1) per CU, spread over the channel slabs; the
-            // number of tile lanes is rounded to a multiple of 8 for the XCD-aware mapping inside the kernel
-            auto lanes_for = [&](int per_cu, int slabs) {
-                int gx = (per_cu * 256 + slabs - 1) / slabs;
-                gx = (gx + 7) & ~7;
-                if (gx > ntile) gx = ntile;
-                return gx;
-            };
-            if (ep_scale && !(uh_aligned16(ep_scale) && uh_aligned16(ep_shift))) ep_scale = ep_shift = nullptr;   // 16-B loads
-            constexpr bool CAN_SPLIT = (ES == 4);
-            if (split && !CAN_SPLIT) { uh_set_error("conv3x3_fwd: bf16x3 needs fp32 tensors"); return UH_EINVAL; }
-            if (split && wfrag) { uh_set_error("conv3x3_fwd: bf16x3 filters are KRSC packs"); return UH_EINVAL; }
-            if (narrow && wfrag) { uh_set_error("conv3x3_fwd: narrow-tensor calls take KRSC packs"); return UH_EINVAL; }
-            if (pre) {
-#if !UH_BUILD_PRE
-                uh_set_error("conv3x3_fwd: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
-                return UH_EINVAL;
-#else
-                if constexpr (ES == 2) {
-                    if (split || narrow || C0 > PRE_MAX_C) { uh_set_error("conv3x3_fwd: the fused BatchNorm+ReLU input needs a plain bf16 call with at most %d channels in source 0; ask uh_conv3x3_pre_ok first", PRE_MAX_C); return UH_EINVAL; }
-                    const int wf = wfrag ? 1 : 0;
-                    if (Cout % 128 == 0 && (int64_t)ntile * (Cout / 128) >= 512) {
-                        int slabs = Cout / 128, gx = lanes_for(2, slabs);
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 2, false, false, true>), dim3(gx * slabs), dim3(256), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wf, pre_scale, pre_shift);
-                    } else if (C0 + C1 == 2 * CK && !uh_no_wres()) {
-                        int slabs = Cout / 64, gx = lanes_for(2, slabs);
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, true, true>), dim3(gx * slabs), dim3(256), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wf, pre_scale, pre_shift);
-                    } else {
-                        int slabs = Cout / 64, gx = lanes_for(3, slabs);
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, false, true>), dim3(gx * slabs), dim3(256), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wf, pre_scale, pre_shift);
-                    }
-                    UH_CHECK_LAUNCH("conv3x3_fwd_mfma_v2 (BatchNorm+ReLU input)");
-                    *ep_done = ep_scale != nullptr;
-                    return UH_OK;
-                } else {
-                    uh_set_error("conv3x3_fwd: the fused BatchNorm+ReLU input is a bf16 path; ask uh_conv3x3_pre_ok first");
-                    return UH_EINVAL;
-                }
-#endif
-            }
-            if (bsum) {
-                if constexpr (ES == 2) {
-                    const int64_t bq = (int64_t)B * H * W * bs_ld * ES;
-                    if (split || narrow || C1 != 0 || !stats || !bs_coef || bs_ld != ldy || !uh_aligned16(bs_y) || bq >= (1ll << 31) - 4096) {
-                        uh_set_error("uh_conv3x3_dgrad_bnsum: needs a plain single-source bf16 call and a 16-byte aligned BatchNorm input below 2 GiB; ask uh_conv3x3_dgrad_bnsum_rows first");
-                        return UH_EINVAL;
-                    }
-                    const FwdSel sel = fwd_select(ntile, Cin, Cout, true, true);
-                    const int wf = wfrag ? 1 : 0, grid = sel.gx * sel.slabs;
-                    if (sel.ks == 2)
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, false, false, true, 2>), dim3(grid), dim3(512), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, nullptr, nullptr, C0v, C1v, Coutv, wf,
-                                           nullptr, nullptr, bs_y, bs_ld, (unsigned)bq, bs_coef);
-                    else if (sel.nbw == 2)
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 2, false, false, false, true>), dim3(grid), dim3(256), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, nullptr, nullptr, C0v, C1v, Coutv, wf,
-                                           nullptr, nullptr, bs_y, bs_ld, (unsigned)bq, bs_coef);
-                    else if (sel.wres)
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, true, false, true>), dim3(grid), dim3(256), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, nullptr, nullptr, C0v, C1v, Coutv, wf,
-                                           nullptr, nullptr, bs_y, bs_ld, (unsigned)bq, bs_coef);
-                    else
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, false, false, true>), dim3(grid), dim3(256), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, nullptr, nullptr, C0v, C1v, Coutv, wf,
-                                           nullptr, nullptr, bs_y, bs_ld, (unsigned)bq, bs_coef);
-                    UH_CHECK_LAUNCH("conv3x3_fwd_mfma_v2 (backward-data + BatchNorm sums)");
-                    return UH_OK;
-                } else {
-                    uh_set_error("uh_conv3x3_dgrad_bnsum: bf16 only; ask uh_conv3x3_dgrad_bnsum_rows first");
-                    return UH_EINVAL;
-                }
-            }
-            const bool wres_first = ES == 2 && !split && !narrow && C0 + C1 == 2 * CK && !uh_no_wres() && uh_wres_wide();
-            if (!wres_first && Cout % 128 == 0 && (int64_t)ntile * (Cout / 128) >= 512) {
-                int slabs = Cout / 128, gx = lanes_for(2, slabs);
-                if (split) {
-                    if constexpr (CAN_SPLIT)
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 2, true>), dim3(gx * slabs), dim3(256), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wfrag ? 1 : 0);
-                } else
-                    hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 2>), dim3(gx * slabs), dim3(256), 0, st, x0, C0, ld0, x1,
-                                       C1, ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wfrag ? 1 : 0);
-            } else if (ES == 2 && !split && !narrow && C0 + C1 == 2 * CK && !uh_no_wres()) {
-                // 64 input channels: the filter stays in registers (2 workgroups per CU: 72 more VGPRs)
-                int slabs = Cout / 64, gx = lanes_for(2, slabs);
-                if constexpr (ES == 2)
-                    hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, true>), dim3(gx * slabs), dim3(256), 0, st, x0, C0, ld0, x1,
-                                       C1, ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wfrag ? 1 : 0);
-            } else {
-                int slabs = Cout / 64, gx = lanes_for(3, slabs);
-                if (split) {
-                    if constexpr (CAN_SPLIT)
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, true>), dim3(gx * slabs), dim3(256), 0, st, x0, C0, ld0, x1, C1, ld1,
-                                           w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wfrag ? 1 : 0);
-                } else if (ES == 2 && !narrow && fwd_ksplit_ok(ntile, Cin, Cout)) {
-                    // few tiles, long contraction: eight waves per workgroup, each half of them half of the K-chunks, one tile each
-                    if constexpr (ES == 2)
-                        hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, false, false, false, 2>), dim3(ntile * slabs), dim3(512), 0, st, x0, C0, ld0, x1,
-                                           C1, ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wfrag ? 1 : 0);
-                } else
-                    hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1>), dim3(gx * slabs), dim3(256), 0, st, x0, C0, ld0, x1,
-                                       C1, ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)b0, (unsigned)b1, (unsigned)by, ep_scale, ep_shift, C0v, C1v, Coutv, wfrag ? 1 : 0);
-            }
-            UH_CHECK_LAUNCH("conv3x3_fwd_mfma_v2");
-            *ep_done = ep_scale != nullptr;
-            return UH_OK;
+    const bool ptrs16 = uh_aligned16(x0) && (C1 == 0 || uh_aligned16(x1)) && uh_aligned16(w) && uh_aligned16(y);
+    const FwdPlan p = fwd_plan(ES, B, H, W, C0, C1, Cout, ld0, ld1, ldy, ptrs16, uh_aligned16(y), split, narrow, pre, bsum);
+    if (p.kernel != FWD_SIMT && p.kernel != FWD_LARGE) {
+        if (ep_scale && !(uh_aligned16(ep_scale) && uh_aligned16(ep_shift))) ep_scale = ep_shift = nullptr;   // 16-B loads
+        UH_REQUIRE(!split || ES == 4, "conv3x3_fwd: bf16x3 needs fp32 tensors");
+        UH_REQUIRE(!(split && wfrag), "conv3x3_fwd: bf16x3 filters are KRSC packs");
+        UH_REQUIRE(!(narrow && wfrag), "conv3x3_fwd: narrow-tensor calls take KRSC packs");
+        if (pre) {
+            UH_REQUIRE(UH_BUILD_PRE, "conv3x3_fwd: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
+            UH_REQUIRE(ES == 2, "conv3x3_fwd: the fused BatchNorm+ReLU input is a bf16 path; ask uh_conv3x3_pre_ok first");
+            UH_REQUIRE(!(split || narrow || C0 > PRE_MAX_C), "conv3x3_fwd: the fused BatchNorm+ReLU input needs a plain bf16 call with at most %d channels in source 0; ask uh_conv3x3_pre_ok first", PRE_MAX_C);
         }
-        if (pre) { uh_set_error("conv3x3_fwd: the fused BatchNorm+ReLU input needs the LDS-DMA MFMA kernel (tensors below 2 GiB); ask uh_conv3x3_pre_ok first"); return UH_EINVAL; }
-        if (bsum) { uh_set_error("uh_conv3x3_dgrad_bnsum: needs the LDS-DMA MFMA kernel (tensors below 2 GiB); ask uh_conv3x3_dgrad_bnsum_rows first"); return UH_EINVAL; }
-        if (wfrag) { uh_set_error("conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but this call cannot take the LDS-DMA MFMA kernel (a tensor of 2 GiB or more); ask uh_conv3x3_wfrag_ok first"); return UH_EINVAL; }
-        if (split) { uh_set_error("conv3x3_fwd: bf16x3 is implemented for tensors below 2 GiB only"); return UH_EINVAL; }
-        if (narrow) { uh_set_error("conv3x3_fwd: narrow tensors are implemented for tensors below 2 GiB only"); return UH_EINVAL; }
-        if (Cout % 128 == 0) {
-            hipLaunchKernelGGL((conv3x3_fwd_mfma<T, 4>), dim3(ntile, Cout / 128), dim3(256), 0, st, x0, C0, ld0, x1, C1,
-                               ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY);
-        } else {
-            hipLaunchKernelGGL((conv3x3_fwd_mfma<T, 2>), dim3(ntile, Cout / 64), dim3(256), 0, st, x0, C0, ld0, x1, C1,
-                               ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY);
+        const int64_t px = (int64_t)B * H * W, bq = bsum ? px * bs_ld * ES : 0;
+        if (bsum) {
+            UH_REQUIRE(ES == 2, "uh_conv3x3_dgrad_bnsum: bf16 only; ask uh_conv3x3_dgrad_bnsum_rows first");
+            UH_REQUIRE(!(split || narrow || C1 != 0 || !stats || !bs_coef || bs_ld != ldy || !uh_aligned16(bs_y) || bq >= (1ll << 31) - 4096),
+                       "uh_conv3x3_dgrad_bnsum: needs a plain single-source bf16 call and a 16-byte aligned BatchNorm input below 2 GiB; ask uh_conv3x3_dgrad_bnsum_rows first");
         }
+        // byte extents of x0, x1, y and q for the buffer descriptors (below 2 GiB: fwd_plan)
+        fwd_v2_launch<T>(p, st, x0, C0, ld0, x1, C1, ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)(px * ld0 * ES),
+                         (unsigned)(C1 ? px * ld1 * ES : 0), (unsigned)(px * ldy * ES), ep_scale, ep_shift, C0v, C1v, Coutv,
+                         wfrag ? 1 : 0, pre_scale, pre_shift, bs_y, bs_ld, (unsigned)bq, bs_coef);
+        UH_CHECK_LAUNCH(pre ? "conv3x3_fwd_mfma_v2 (BatchNorm+ReLU input)"
+                            : bsum ? "conv3x3_fwd_mfma_v2 (backward-data + BatchNorm sums)" : "conv3x3_fwd_mfma_v2");
+        *ep_done = ep_scale != nullptr;
+        return UH_OK;
+    }
+    if (p.kernel == FWD_LARGE) {
+        UH_REQUIRE(!pre, "conv3x3_fwd: the fused BatchNorm+ReLU input needs the LDS-DMA MFMA kernel (tensors below 2 GiB); ask uh_conv3x3_pre_ok first");
+        UH_REQUIRE(!bsum, "uh_conv3x3_dgrad_bnsum: needs the LDS-DMA MFMA kernel (tensors below 2 GiB); ask uh_conv3x3_dgrad_bnsum_rows first");
+        UH_REQUIRE(!wfrag, "conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but this call cannot take the LDS-DMA MFMA kernel (a tensor of 2 GiB or more); ask uh_conv3x3_wfrag_ok first");
+        UH_REQUIRE(!split, "conv3x3_fwd: bf16x3 is implemented for tensors below 2 GiB only");
+        UH_REQUIRE(!narrow, "conv3x3_fwd: narrow tensors are implemented for tensors below 2 GiB only");
+        if (Cout % 128 == 0)
+            hipLaunchKernelGGL((conv3x3_fwd_mfma<T, 4>), dim3(p.lanes, p.slabs), dim3(p.threads), 0, st, x0, C0, ld0, x1, C1,
+                               ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY);
+        else
+            hipLaunchKernelGGL((conv3x3_fwd_mfma<T, 2>), dim3(p.lanes, p.slabs), dim3(p.threads), 0, st, x0, C0, ld0, x1, C1,
+                               ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY);
         UH_CHECK_LAUNCH("conv3x3_fwd_mfma");
         return UH_OK;
     }
-    if (pre) { uh_set_error("conv3x3_fwd: the fused BatchNorm+ReLU input needs an MFMA-aligned shape; ask uh_conv3x3_pre_ok first"); return UH_EINVAL; }
-    if (bsum) { uh_set_error("uh_conv3x3_dgrad_bnsum: needs an MFMA-aligned shape; ask uh_conv3x3_dgrad_bnsum_rows first"); return UH_EINVAL; }
-    if (wfrag) { uh_set_error("conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but the shape / alignment is outside the MFMA path; ask uh_conv3x3_wfrag_ok first"); return UH_EINVAL; }
-    if (split) { uh_set_error("conv3x3_fwd: bf16x3 needs an MFMA-aligned shape (Cin %% 16 == 0, Cout %% 64 == 0, 16-byte strides)"); return UH_EINVAL; }
-    if (narrow) { uh_set_error("conv3x3_fwd: narrow tensors need padded counts that are MFMA-aligned and 16-byte strides"); return UH_EINVAL; }
-    if (Cin <= 4 && C1 == 0) {
-        constexpr int V = 16 / ES;
+    UH_REQUIRE(!pre, "conv3x3_fwd: the fused BatchNorm+ReLU input needs an MFMA-aligned shape; ask uh_conv3x3_pre_ok first");
+    UH_REQUIRE(!bsum, "uh_conv3x3_dgrad_bnsum: needs an MFMA-aligned shape; ask uh_conv3x3_dgrad_bnsum_rows first");
+    UH_REQUIRE(!wfrag, "conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but the shape / alignment is outside the MFMA path; ask uh_conv3x3_wfrag_ok first");
+    UH_REQUIRE(!split, "conv3x3_fwd: bf16x3 needs an MFMA-aligned shape (Cin %% 16 == 0, Cout %% 64 == 0, 16-byte strides)");
+    UH_REQUIRE(!narrow, "conv3x3_fwd: narrow tensors need padded counts that are MFMA-aligned and 16-byte strides");
+    if (p.stem == 3) {
         if constexpr (ES == 2) {
-            if (Cout == 64 && uh_aligned16(y) && (ldy * ES) % 16 == 0) {
-                int grid = ntile < 1024 ? ntile : 1024;
-                switch (Cin) {
-                    case 1: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 1>), dim3(grid), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
-                    case 2: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 2>), dim3(grid), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
-                    case 3: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 3>), dim3(grid), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
-                    default: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 4>), dim3(grid), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
-                }
-                UH_CHECK_LAUNCH("conv3x3_fwd_stem_v3");
-                *ep_done = ep_scale != nullptr;
-                return UH_OK;
+            switch (Cin) {
+                case 1: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 1>), dim3(p.lanes), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
+                case 2: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 2>), dim3(p.lanes), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
+                case 3: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 3>), dim3(p.lanes), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
+                default: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 4>), dim3(p.lanes), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
             }
+            UH_CHECK_LAUNCH("conv3x3_fwd_stem_v3");
+            *ep_done = ep_scale != nullptr;
         }
-        if (Cout % V == 0 && uh_aligned16(y) && (ldy * ES) % 16 == 0) {
-            int G = Cout / V, GB = G < 8 ? G : 8, CG = GB * V;
-            size_t sm = (size_t)(HALO_PIX * 4 + 36 * CG + CG + 256 * V) * sizeof(float);
-            hipLaunchKernelGGL(conv3x3_fwd_stem_v2<T>, dim3(ntile), dim3(256), sm, st, x0, Cin, ld0, w, y, ldy, Cout, stats,
-                               B, H, W, tilesX, tilesY);
-            UH_CHECK_LAUNCH("conv3x3_fwd_stem_v2");
-            return UH_OK;
-        }
-        hipLaunchKernelGGL(conv3x3_fwd_stem<T>, dim3(ntile), dim3(256), 0, st, x0, Cin, ld0, w, y, ldy, Cout, stats, B, H,
+        return UH_OK;
+    }
+    if (p.stem == 2) {
+        constexpr int V = 16 / ES;
+        int G = Cout / V, GB = G < 8 ? G : 8, CG = GB * V;
+        size_t sm = (size_t)(HALO_PIX * 4 + 36 * CG + CG + 256 * V) * sizeof(float);
+        hipLaunchKernelGGL(conv3x3_fwd_stem_v2<T>, dim3(p.lanes), dim3(256), sm, st, x0, Cin, ld0, w, y, ldy, Cout, stats,
+                           B, H, W, tilesX, tilesY);
+        UH_CHECK_LAUNCH("conv3x3_fwd_stem_v2");
+        return UH_OK;
+    }
+    if (p.stem == 1) {
+        hipLaunchKernelGGL(conv3x3_fwd_stem<T>, dim3(p.lanes), dim3(256), 0, st, x0, Cin, ld0, w, y, ldy, Cout, stats, B, H,
                            W, tilesX, tilesY);
         UH_CHECK_LAUNCH("conv3x3_fwd_stem");
         return UH_OK;
@@ -2200,7 +2090,7 @@ static int conv3x3_fwd_dispatch(const T* x0, int C0, int ld0, const T* x1, int C
                        C1, ld1, w, y, ldy, Cout, B, H, W);
     UH_CHECK_LAUNCH("conv3x3_fwd_generic");
     if (stats) {
-        hipLaunchKernelGGL(tile_stats_kernel<T>, dim3(ntile), dim3(256), 0, st, (const T*)y, ldy, Cout, stats, B, H, W,
+        hipLaunchKernelGGL(tile_stats_kernel<T>, dim3(p.lanes), dim3(256), 0, st, (const T*)y, ldy, Cout, stats, B, H, W,
                            tilesX, tilesY);
         UH_CHECK_LAUNCH("tile_stats_kernel");
     }
@@ -2232,14 +2122,19 @@ extern "C" int uh_conv3x3_fwd(const void* x0, int C0, int ld0, const void* x1, i
 // load instead of 16 half lines.
 extern "C" int uh_conv3x3_wfrag_ok(int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, int dt) {
     if (dt != UH_F32 && dt != UH_BF16) return 0;
-    const int es = dt == UH_BF16 ? 2 : 4, ck = 64 / es;
     if (B <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0) return 0;
-    if (C0 % ck || C1 % ck || Cout % 64) return 0;
-    if ((ld0 * es) % 16 || (C1 && (ld1 * es) % 16) || (ldy * es) % 16) return 0;
-    const int64_t px = (int64_t)B * H * W, lim = (1ll << 31) - 4096;
-    if (px * ld0 * es >= lim || (C1 && px * ld1 * es >= lim) || px * ldy * es >= lim) return 0;
-    if ((int64_t)Cout * 9 * (C0 + C1) * es >= lim) return 0;
-    return 1;
+    const FwdKernel k = fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, ld0, ld1, ldy, true, true, false, false, false,
+                                 false).kernel;
+    return k != FWD_SIMT && k != FWD_LARGE;
+}
+
+// Which kernel uh_conv3x3_fwd gives a call with dense pitches and 16-byte aligned pointers (FwdKernel): BatchPredictor only
+// batches images whose every layer gets the kernel it gets for one image.
+extern "C" int uh_conv3x3_fwd_kernel(int B, int H, int W, int C0, int C1, int Cout, int dt) {
+    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd_kernel: bad shape");
+    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_fwd_kernel: bad dtype %d", dt);
+    return fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, true, true, dt == UH_F32X3, false, false,
+                    false).kernel;
 }
 
 // Training forward whose input is the RAW output y_prev of the previous conv: the BatchNorm + ReLU between the two convs of a
@@ -2282,8 +2177,7 @@ extern "C" int uh_conv3x3_dgrad_bnsum_rows(int B, int H, int W, int Cdy, int Cdx
     if (dt != UH_BF16) return 0;
     if (!uh_conv3x3_wfrag_ok(B, H, W, Cdy, 0, Cdx, lddy, 0, lddx, dt)) return 0;
     if (ldq != lddx) return 0;                 // q is addressed with the offsets of the tensor being written
-    const int ntile = B * ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
-    return fwd_select(ntile, Cdy, Cdx, true, true).gx;
+    return fwd_plan(2, B, H, W, Cdy, 0, Cdx, lddy, 0, lddx, true, true, false, false, false, true).lanes;
 }
 
 extern "C" int uh_conv3x3_dgrad_bnsum(const void* dy, int Cdy, int lddy, const void* w_dgrad, void* dx, int lddx, int Cdx,
@@ -2937,13 +2831,9 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
         }
     };
 
-#ifndef UH_WGRAD_M16
-#define UH_WGRAD_M16 1      // 1: v_mfma_f32_16x16x32_bf16 (k = the 16 pixels of rows p and p+4), 0: v_mfma_f32_32x32x16_bf16 (k = one row)
-#endif
     const int l16 = lane & 15;
     const int rq = l16 >> 2, cp = l16 & 3;
     typedef __attribute__((ext_vector_type(8))) short s16x8;
-#if UH_WGRAD_M16
     // The chip holds a higher clock on the 16x16x32 shape than on 32x32x16 at equal cycles per FLOP (MI355X_MICROARCH.md,
     // DVFS give-back item 7), and this kernel runs at the power limit.  A wave's 32 x 32 (co, ci) block = 2 x 2 MFMA tiles;
     // the contraction index of one MFMA = 32 pixels = the 16 columns of tile rows p and p + 4 (so that the x operand of
@@ -2960,22 +2850,10 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
     const int rowsel = g4 >> 1, colh = g4 & 1;
     const int a_cbyte = (wr * 32 + cp * 4) * 2;        // + 32 bytes for the second 16-channel half (bit 5: below the swizzle bits)
     const int b_cbyte = (wc * 32 + cp * 4) * 2;
-#else
-    f32x16 acc[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[k][j] = 0.f;
-    const int grp = (lane >> 4) & 1;
-    const int kh = lane >> 5;
-    const int a_cbyte = (wr * 32 + grp * 16 + cp * 4) * 2;
-    const int b_cbyte = (wc * 32 + grp * 16 + cp * 4) * 2;
-#endif
     // Lane-constant LDS byte offsets of the two transposed reads of a fragment (pixels c, c+4 of a row); the halves
     // of a 128-byte pixel row are swapped by ((column >> 1) & 1), so 4 consecutive pixels hit 4 distinct bank groups.
     auto col_off = [&](int col, int cbyte) -> int { return col * PB + (cbyte ^ (((col >> 1) & 1) << 6)); };
     auto dcol_off = [&](int col, int cbyte) -> int { return col * DPB + (cbyte ^ (dswz(col) << 4)); };
-#if UH_WGRAD_M16
     const int d_lo = rowsel * 4 * (TILE * DPB) + dcol_off(colh * 8 + rq, a_cbyte);
     const int d_hi = rowsel * 4 * (TILE * DPB) + dcol_off(colh * 8 + rq + 4, a_cbyte);
     int x_lo[3], x_hi[3];
@@ -2984,15 +2862,6 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
         x_lo[s] = rowsel * 4 * (HALO_W * PB) + col_off(s + colh * 8 + rq, b_cbyte);
         x_hi[s] = rowsel * 4 * (HALO_W * PB) + col_off(s + colh * 8 + rq + 4, b_cbyte);
     }
-#else
-    const int d_lo = dcol_off(kh * 8 + rq, a_cbyte), d_hi = dcol_off(kh * 8 + rq + 4, a_cbyte);
-    int x_lo[3], x_hi[3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        x_lo[s] = col_off(s + kh * 8 + rq, b_cbyte);
-        x_hi[s] = col_off(s + kh * 8 + rq + 4, b_cbyte);
-    }
-#endif
 
     // PRE: lane l of every wave holds (scale, shift) of channel ci0 + l of source 0 (loaded -- and waited for -- before the first
     // asynchronous DMA is in flight, so that the compiler's own wait for these two loads cannot miscount)
@@ -3066,13 +2935,9 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
         s16x8 both = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
         return __builtin_bit_cast(bf16x8, both);
     };
-#ifndef UH_WGRAD_ROT
-#define UH_WGRAD_ROT 1      // 1: the tile loop is rotated (see below); 0: one barrier at the very end of a tile (round 3)
-#endif
-#if UH_WGRAD_M16
-    // (the consumer-side BatchNorm variants -- UH_BUILD_PRE -- keep the round-3 loop: their rewrite of the x image sits inside the
-    // fence, and inside the rotated MFMA stream it spills)
-    if constexpr (UH_WGRAD_ROT && !PRE) {
+    // (the consumer-side BatchNorm variants -- UH_BUILD_PRE -- keep the round-3 loop, one barrier at the very end of a tile: their
+    // rewrite of the x image sits inside the fence, and inside the rotated MFMA stream it spills)
+    if constexpr (!PRE) {
     // ROTATED tile loop.  A tile = six x row pairs a (fragments of pair a + 1 are fetched while pair a is multiplied; dy pair
     // p = a - r meets tap row r); the last LDS reads of a tile are those of pair 5, requested in front of pair 4's MFMAs.  The
     // end-of-tile fence (next tile's DMA landed, everyone done READING this buffer) therefore sits in front of pair 5's twelve
@@ -3143,20 +3008,13 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
         __builtin_amdgcn_sched_barrier(0);
         mma_pair(5);
     }
-    } else
-#endif
-    {
+    } else {
     if (t_begin < t_end) issue(t_begin, 0);
     tile_fence(t_begin, 0, t_begin < t_end);
     int bufi = 0;
     for (int tile = t_begin; tile < t_end; ++tile, bufi ^= 1) {
-#if !UH_WGRAD_M16
-        if (tile + 1 < t_end) issue(tile + 1, bufi ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-#endif
         const unsigned char* xs = lds + bufi * STAGE;
         const unsigned char* ds = xs + XBYTES;
-#if UH_WGRAD_M16
         // fully unrolled over the six x row pairs (a, a + 4): the fragments of pair a + 1 are fetched while pair a is
         // multiplied; dy pair p = a - r meets tap row r
         bf16x8 dfr[4][2];
@@ -3201,36 +3059,10 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
                 }
             }
         }
-#else
-        const bf16x8 zero8 = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        // fully unrolled over the 10 halo rows: row addresses are immediates, the dy fragments rotate by renaming,
-        // and the fragments of row hy+1 are fetched while row hy is multiplied
-        bf16x8 dfr[TH + 2];
-        bf16x8 xfr[TH + 2][3];
-        dfr[0] = tr_pair(ds, d_lo, d_hi);
-#pragma unroll
-        for (int s = 0; s < 3; ++s) xfr[0][s] = tr_pair(xs, x_lo[s], x_hi[s]);
-#pragma unroll
-        for (int hy = 0; hy < TH + 2; ++hy) {
-            if (hy + 1 < TH + 2) {
-                dfr[hy + 1] = (hy + 1 < TH) ? tr_pair(ds + (hy + 1) * (TILE * DPB), d_lo, d_hi) : zero8;
-#pragma unroll
-                for (int s = 0; s < 3; ++s) xfr[hy + 1][s] = tr_pair(xs + (hy + 1) * (HALO_W * PB), x_lo[s], x_hi[s]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-                    if (hy - r >= 0 && hy - r < TH)
-                        acc[r * 3 + s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dfr[hy - r], xfr[hy][s], acc[r * 3 + s], 0, 0, 0);
-        }
-#endif
         tile_fence(tile + 1, bufi ^ 1, tile + 1 < t_end);
     }
     }
 
-#if UH_WGRAD_M16
     if constexpr (SLAB16) {
         // ---- the workgroup's largest |partial| -> one power-of-two scale (the tile loop is over: LDS is scratch now; the only LDS
         // operations still in flight are the rotated loop's look-ahead reads, whose results nobody uses)
@@ -3276,9 +3108,7 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
                     }
         return;
     }
-#endif
     float* slab = slabs + (int64_t)split * Cout * 9 * Cin;
-#if UH_WGRAD_M16
     // acc[tap][h][hh][j] = dW[co0 + wr*32 + h*16 + (lane >> 4)*4 + j][tap][ci0 + wc*32 + hh*16 + (lane & 15)]
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
@@ -3292,16 +3122,6 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
                     const int ci = ci0 + wc * 32 + hh * 16 + (lane & 15);
                     slab[((int64_t)co * 9 + tap) * Cin + ci] = acc[tap][h][hh][j];
                 }
-#else
-    const int ci = ci0 + wc * 32 + (lane & 31);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            int co = co0 + wr * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-            slab[((int64_t)co * 9 + tap) * Cin + ci] = acc[tap][reg];
-        }
-#endif
 }
 
 __global__ void slab_reduce_scalar_kernel(const float* __restrict__ slabs, float* __restrict__ out, int64_t n, int nsplit) {
@@ -3596,12 +3416,9 @@ static WgradPlan wgrad_plan(int B, int H, int W, int Cin, int Cout, bool aligned
         p.kind = 0;
         p.tilesX = (W + TILE - 1) / TILE; p.tilesY = (H + TH - 1) / TH;
         p.ntile = B * p.tilesX * p.tilesY;
-        // UH_WGRAD_HALF_CU=1 (experiment): 4-wave workgroups, one per CU -- backward-weights then holds half of every CU and the
-        // kernels of the main stream can run beside it
-        static const bool half_cu = getenv("UH_WGRAD_HALF_CU") != nullptr;
-        if (wide && sizeof(T) == 2 && Cout % 128 == 0 && !half_cu) p.nwr = 4;
+        if (wide && sizeof(T) == 2 && Cout % 128 == 0) p.nwr = 4;
         int ctiles = (Cin / 64) * (Cout / (32 * p.nwr));
-        int total = (p.nwr == 4 || half_cu) ? 256 : 512;           // one 8-wave / two 4-wave workgroups per CU in flight (LDS)
+        int total = p.nwr == 4 ? 256 : 512;           // one 8-wave / two 4-wave workgroups per CU in flight (LDS)
         int want = (total + ctiles - 1) / ctiles;
         p.nsplit = want < 1 ? 1 : (want > p.ntile ? p.ntile : want);
     } else if (Cin <= 4) {
@@ -3687,7 +3504,7 @@ static int conv3x3_wgrad_dispatch(const T* dy, int lddy, const T* x0, int C0, in
     // block-scaled fp16-pair slabs: the bf16 LDS-DMA kernel's default (see SLAB16); the inverse scales follow the slabs in `ws`
     // (nsplit * n * 2 + nsplit * blocks * 4 bytes <= the nsplit * n * 4 the workspace is sized for)
     static const bool slab_f32 = getenv("UH_WGRAD_SLAB_F32") != nullptr && getenv("UH_WGRAD_SLAB_F32")[0] == '1';
-    const bool slab16 = ES == 2 && p.kind == 0 && dma && !slab_f32 && UH_WGRAD_M16 && uh_aligned16(dw);
+    const bool slab16 = ES == 2 && p.kind == 0 && dma && !slab_f32 && uh_aligned16(dw);
     if (p.kind == 0) {
         const int64_t npx = (int64_t)B * H * W;
         const int64_t ldmax = ld0 > ld1 ? ld0 : ld1;

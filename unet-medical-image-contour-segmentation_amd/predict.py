@@ -138,7 +138,7 @@ class BatchPredictor:
       - conv3x3_fwd_dispatch splits the contraction over the two halves of a workgroup when a layer with 256+ input channels
         has at most 256 (tile, 64-channel slab) pairs, and moves to 128-channel slabs from 512 (tile, slab) pairs: a
         700 x 300 image has 18 tiles at the level of up1 (256 -> 128 channels), so 7 images split K and 8 do not.
-    `launch_lengths` evaluates both rules (the library's predicate, and a restatement of the dispatch rules) and only forms
+    `launch_lengths` asks the library for both choices (uh_convt2x2_mfma_ok, uh_conv3x3_fwd_kernel) and only forms
     launches in which every layer gets the kernel it gets for one image; a batch is cut into the fewest such launches,
     down to one image per launch where nothing longer qualifies."""
 
@@ -197,25 +197,6 @@ class BatchPredictor:
         dev.copy_(stage, non_blocking=True)
         return dev
 
-    @staticmethod
-    def _conv3x3_variant(B: int, h: int, w: int, cin: int, cout: int, bf16: bool) -> int:
-        """Which forward kernel conv3x3_fwd_dispatch (csrc/conv3x3.hip) gives a layer: its rules that look at the number
-        of 16 x 16 tiles, restated.  0 = not an MFMA shape (no rule depends on B)."""
-        es = 2 if bf16 else 4
-        if cout % 64 or cin % (64 // es):
-            return 0
-        if B * h * w * max(cin, cout) * es >= (1 << 31) - 4096:
-            return 5                                                   # past the 2 GiB buffer window: the older kernel
-        ntile = B * ((h + 15) // 16) * ((w + 15) // 16)
-        if cout % 128 == 0 and ntile * (cout // 128) >= 512:
-            return 1                                                   # 128-channel slabs
-        if bf16 and cin == 64:
-            return 2                                                   # register-resident filter
-        nchunk = cin // 32
-        if bf16 and cin % 32 == 0 and ntile * (cout // 64) <= 256 and nchunk >= 8 and nchunk % 2 == 0:
-            return 3                                                   # K split over the two halves of the workgroup
-        return 4
-
     def _layers(self):
         """(kind, module, pyramid levels it may sit at) for the layers whose kernel choice can depend on B."""
         if self._layer_levels is None:
@@ -254,7 +235,7 @@ class BatchPredictor:
                     return 0
                 if kind == "convt":
                     return LIB.query("uh_convt2x2_mfma_ok", B, h, w, m.in_channels, m.out_channels, H >> (k - 1), W >> (k - 1), dt)
-                return self._conv3x3_variant(B, h, w, m.in_channels, m.out_channels, self.amp)
+                return LIB.query("uh_conv3x3_fwd_kernel", B, h, w, m.in_channels, 0, m.out_channels, dt)
 
             self._lengths[key] = [B for B in range(1, self.batch + 1)
                                   if all(choice(B, kind, m, k) == choice(1, kind, m, k)
