@@ -87,6 +87,16 @@ int uh_conv3x3_wfrag_ok(int B, int H, int W, int C0, int C1, int Cout, int ld0, 
  * sum in different orders: a batch gives bit-identical per-image results only where every layer gets the same answer as for
  * one image (BatchPredictor.launch_lengths).  UH_EINVAL for a bad shape or dtype. */
 int uh_conv3x3_fwd_kernel(int B, int H, int W, int C0, int C1, int Cout, int dt);
+/* The pinned plan (batch-invariant eval forward).  plan_B > 0: the kernel FORM is chosen as for a launch of plan_B images of this
+ * H x W, while tiles, grid, byte extents and the 2 GiB test (code 5) stay with the real B; where the launch's own form sums in the
+ * same order as the pinned one (uh_conv3x3_fwd_sum_class) the launch keeps its own.  plan_B = 0: the unpinned answers above.
+ * uh_conv3x3_fwd_kernel_plan = the code uh_conv3x3_fwd_affine_relu_plan(.., B, plan_B, ..) runs; uh_conv3x3_wfrag_ok_plan = may its
+ * filter be packed fragment-major (codes 1-4).  With plan_B = 1 every image of a batch is computed bit for bit as it is alone. */
+int uh_conv3x3_fwd_kernel_plan(int B, int plan_B, int H, int W, int C0, int C1, int Cout, int dt);
+int uh_conv3x3_wfrag_ok_plan(int B, int plan_B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, int dt);
+/* Summation class of a kernel code 0..5: codes of one class add a pixel's products in the same order and give the same bits
+ * (1, 2 and 4 -> 1; 0, 3 and 5 stand alone).  UH_EINVAL for another code. */
+int uh_conv3x3_fwd_sum_class(int kernel);
 int uh_conv3x3_fwd(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1,
                    const void* w, void* y, int ldy, int Cout, float* stat_partials,
                    int B, int H, int W, int dt, uh_stream stream);
@@ -136,6 +146,10 @@ int uh_stem_bn_relu_bwd_wgrad(const void* dz, int lddz, const void* x, int Cin, 
 int uh_conv3x3_fwd_affine_relu(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1,
                                const void* w, void* z, int ldz, int Cout, const float* scale,
                                const float* shift, int B, int H, int W, int dt, uh_stream stream);
+/* The same call under the pinned plan (see uh_conv3x3_fwd_kernel_plan): plan_B = 0 is uh_conv3x3_fwd_affine_relu. */
+int uh_conv3x3_fwd_affine_relu_plan(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1,
+                                    const void* w, void* z, int ldz, int Cout, const float* scale,
+                                    const float* shift, int B, int plan_B, int H, int W, int dt, uh_stream stream);
 /* conv backward-weights: dw[o][r][s][i] = sum_{b,h,w} dy[b,h,w,o] * x[b,h+r-1,w+s-1,i] (fp32 KRSC).
  * bf16 MFMA path: the per-split partial sums (fp32 accumulators) travel through `ws` as block-scaled fp16 -- 11 significant
  * bits, one power-of-two scale per workgroup block -- and are added in fp32 in a fixed order (deterministic); UH_WGRAD_SLAB_F32=1
@@ -188,6 +202,10 @@ int uh_pack_w3x3_padded(const float* w, int64_t sO, int64_t sI, int64_t sH, int6
 int uh_conv3x3_fwd_narrow(const void* x0, int C0, int C0v, int ld0, const void* x1, int C1, int C1v, int ld1,
                           const void* w, void* y, int ldy, int Cout, int Coutv, float* stat_partials,
                           const float* scale, const float* shift, int B, int H, int W, int dt, uh_stream stream);
+/* The same call under the pinned plan (see uh_conv3x3_fwd_kernel_plan): plan_B = 0 is uh_conv3x3_fwd_narrow. */
+int uh_conv3x3_fwd_narrow_plan(const void* x0, int C0, int C0v, int ld0, const void* x1, int C1, int C1v, int ld1,
+                               const void* w, void* y, int ldy, int Cout, int Coutv, float* stat_partials,
+                               const float* scale, const float* shift, int B, int plan_B, int H, int W, int dt, uh_stream stream);
 int uh_conv3x3_wgrad_narrow(const void* dy, int lddy, int Cout, int Coutv, const void* x0, int C0, int C0v, int ld0,
                             const void* x1, int C1, int C1v, int ld1, float* dw_krsc, void* ws, size_t ws_bytes,
                             int B, int H, int W, int dt, uh_stream stream);
@@ -329,6 +347,9 @@ int uh_convt2x2_wgrad(const void* dy, int lddy, const void* x, int ldx, float* d
  * uh_convt2x2_pack: reference weight [Cin][Cout][2][2] fp32 -> w_fwd [(q,co)][ci] and w_dgrad [ci][(q,co)]
  * (Cin*Cout*4 elements each, activation dtype), q = 2*r + s. */
 int uh_convt2x2_mfma_ok(int B, int h, int w_, int Cin, int Cout, int Ho, int Wo, int dt);
+/* Pinned twin: 1 iff a launch of plan_B images qualifies (then every multiple does) AND the real B fits the 2 GiB windows;
+ * plan_B = 0 is uh_convt2x2_mfma_ok(B, ..).  0 = run uh_convt2x2_fwd for the whole batch. */
+int uh_convt2x2_mfma_ok_plan(int B, int plan_B, int h, int w_, int Cin, int Cout, int Ho, int Wo, int dt);
 int uh_convt2x2_pack(const float* w, int Cin, int Cout, void* w_fwd, void* w_dgrad, int dt, uh_stream stream);
 int uh_convt2x2_fwd_mfma(const void* x, int ldx, const void* w_fwd, const float* bias, void* y, int ldy,
                          int B, int h, int w_, int Cin, int Cout, int Ho, int Wo, int pad_top, int pad_left,

@@ -6,11 +6,12 @@ For UNet_S(1,3) and UNet(1,3) (bf16, transposed-conv upscaling), on synthetic ph
   (a) the per-image loop a user of the package writes without BatchPredictor:
       mask_to_image(postprocess_mask(predict_img(model, img, device))) for every image;
   (b) unet_amd.BatchPredictor(model, batch=8) on the same list;
+  (c) unet_amd.BatchPredictor(model, batch=8, batch_invariant=True): every batch one launch under the pinned plan;
 on two workloads: 8 x 512x512 (one size, one batch) and a shuffled mixed set (512x512, 512x384, 1000x999, 300x700,
-`--per-size` of each).  Both legs run in this process on the same images, alternating, `--reps` times after a warm-up pass
-over every shape; a leg's time is a host clock around work that ends in a device synchronise (both legs end with their
-results on the host).  Reported: images/s from the median repetition, the min-max spread, and the ratio (b)/(a).
-Then the device time of every stage of one 8 x 512x512 batch from events on the stream, and (c) the command line end to
+`--per-size` of each).  The legs run in this process on the same images, alternating, `--reps` times after a warm-up pass
+over every shape; a leg's time is a host clock around work that ends in a device synchronise (all legs end with their
+results on the host).  Reported: images/s from the median repetition, the min-max spread, and the ratios (b)/(a), (c)/(b).
+Then the device time of every stage of one 8 x 512x512 batch from events on the stream (both predictors), and the command line end to
 end on a temporary folder (`python -m unet_amd.predict`, decode and PNG encode included; process start-up and model load
 are inside the figure and are also reported apart)."""
 import argparse
@@ -80,29 +81,38 @@ def run_model(name, reps, per_size):
     res = {"model": f"{name}(1,3)", "rows": []}
     for label, images in (("8x512x512", one), (f"mixed_{per_size}_each_of_4_sizes", mixed)):
         predictor = unet_amd.BatchPredictor(model, batch=8)
-        ref = per_image_loop(unet_amd, model, images, dev)            # warm-up of every shape, both legs
+        invariant = unet_amd.BatchPredictor(model, batch=8, batch_invariant=True)
+        ref = per_image_loop(unet_amd, model, images, dev)            # warm-up of every shape, all legs
         predictor(images)
         got = predictor(images)                                        # second pass: graphs captured
+        invariant(images)
+        got_c = invariant(images)
         same = all(np.array_equal(a, b) for a, b in zip(ref, got))
-        ta, tb = [], []
+        same_c = all(np.array_equal(a, b) for a, b in zip(ref, got_c))
+        ta, tb, tc = [], [], []
         for _ in range(reps):                                          # alternating
             ta.append(timed(lambda: per_image_loop(unet_amd, model, images, dev))[0])
             tb.append(timed(lambda: predictor(images))[0])
-        a, b = rates(len(images), ta), rates(len(images), tb)
+            tc.append(timed(lambda: invariant(images))[0])
+        a, b, c = rates(len(images), ta), rates(len(images), tb), rates(len(images), tc)
         row = {"workload": label, "images": len(images), "per_image_loop": a, "batch_predictor": b,
-               "ratio_b_over_a": b["images_per_s"] / a["images_per_s"], "outputs_equal": same,
+               "batch_predictor_invariant": c, "ratio_b_over_a": b["images_per_s"] / a["images_per_s"],
+               "ratio_c_over_b": c["images_per_s"] / b["images_per_s"], "outputs_equal": same, "outputs_equal_invariant": same_c,
                "foreground_share": float(np.mean([(g == 255).mean() for g in got])), "graph_replays": predictor.graph_replays,
-               "launch_lengths": {f"{h}x{w}": v for (h, w), v in predictor._lengths.items()}}
+               "graph_replays_invariant": invariant.graph_replays,
+               "launch_lengths": {f"{h}x{w}": v for (h, w), v in predictor._lengths.items()},
+               "launch_lengths_invariant": {f"{h}x{w}": v for (h, w), v in invariant._lengths.items()}}
         if label == "8x512x512":
-            predictor.events = []
-            for _ in range(reps):
-                predictor(images)
-            torch.cuda.synchronize()
-            st = {}
-            for stage, e0, e1 in predictor.events:
-                st[stage] = st.get(stage, 0.0) + e0.elapsed_time(e1) / reps
-            predictor.events = None
-            row["stage_ms_per_8_images"] = st
+            for key, pr in (("stage_ms_per_8_images", predictor), ("stage_ms_per_8_images_invariant", invariant)):
+                pr.events = []
+                for _ in range(reps):
+                    pr(images)
+                torch.cuda.synchronize()
+                st = {}
+                for stage, e0, e1 in pr.events:
+                    st[stage] = st.get(stage, 0.0) + e0.elapsed_time(e1) / reps
+                pr.events = None
+                row[key] = st
         res["rows"].append(row)
     return res
 
@@ -148,14 +158,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--per-size", type=int, default=16)
-    ap.add_argument("--cli-images", type=int, default=64)
+    ap.add_argument("--cli-images", type=int, default=64, help="0: leave the command-line leg out")
     ap.add_argument("--models", default="UNet_S,UNet")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("predict_bench.py needs an MI355X")
     out = {"metric": "predict_images_per_s", "device": torch.cuda.get_device_name(0), "amp": "bf16", "postprocess": True,
            "results": [run_model(m, args.reps, args.per_size) for m in args.models.split(",")]}
-    out["cli"] = run_cli(args.cli_images, max(2, args.reps // 2))
+    if args.cli_images > 0:
+        out["cli"] = run_cli(args.cli_images, max(2, args.reps // 2))
     print(json.dumps(out))
 
 

@@ -601,6 +601,9 @@ constexpr int PRE_MAX_C = 512;
 // second half (own halo double buffer each, same hand-counted pipeline), the two partial accumulator sets meet in LDS once
 // at the end (the halo buffers are free by then: nothing follows the only tile) and waves 0-3 run the epilogue unchanged --
 // two waves per SIMD, half the chain each.  Sums are added in a fixed order (first half + second half): deterministic.
+// Under the pinned plan (fwd_plan: plan_B) the form also runs launches far past that range -- a batch of images each of which
+// would get it alone, thousands of one-tile workgroups: nothing in it depends on the tile count (the block mapping below is a
+// bijection for any grid, the hand-over is per workgroup, eval launches write no statistics rows).
 template <typename T, int NBW, bool SPLIT = false, bool WRES = false, bool PRE = false, bool BSUM = false, int KS = 1>
 // (three workgroups per CU -- 168 registers -- for the 16-channel-per-wave form; its BSUM instantiation needs more than that for
 // the epilogue's batches and spilled 42 instructions per tile at 168: two per CU, like the other wide-register forms)
@@ -1884,11 +1887,12 @@ extern "C" int uh_conv3x3_stat_slabs(int B, int H, int W, int Cin, int Cout, int
 }
 
 // K split inside the workgroup (KS = 2, see the kernel): bf16, 16 channels per wave, at most one (tile, 64-channel slab) pair
-// per CU and an even number (>= 8) of 32-channel K-chunks.  UH_NO_KSPLIT=1 turns it off (A/B runs).
-static bool fwd_ksplit_ok(int ntile, int Cin, int Cout) {
+// per CU and an even number (>= 8) of 32-channel K-chunks.  UH_NO_KSPLIT=1 turns it off (A/B runs).  ntile = the tiles of the
+// launch the form is chosen for (the pinned plan asks for plan_B images and launches the real B).
+static bool fwd_ksplit_ok(int64_t ntile, int Cin, int Cout) {
     static const bool off = getenv("UH_NO_KSPLIT") != nullptr && getenv("UH_NO_KSPLIT")[0] == '1';
     const int nchunk = Cin / 32;
-    return !off && Cin % 32 == 0 && Cout % 64 == 0 && (int64_t)ntile * (Cout / 64) <= 256 && nchunk >= 8 && nchunk % 2 == 0;
+    return !off && Cin % 32 == 0 && Cout % 64 == 0 && ntile * (Cout / 64) <= 256 && nchunk >= 8 && nchunk % 2 == 0;
 }
 
 // The kernel a forward / backward-data call takes; the values are what uh_conv3x3_fwd_kernel answers.
@@ -1901,6 +1905,15 @@ enum FwdKernel {
     FWD_STREAM = 4,      // conv3x3_fwd_mfma_v2, NBW = 1: 64-channel slabs, filter fragments streamed
     FWD_LARGE = 5,       // conv3x3_fwd_mfma: a tensor or the filter pack past the 2 GiB window of a buffer descriptor
 };
+
+// Forms of one class add the products of a pixel in the same order and give the same bits: the conv3x3_fwd_mfma_v2 forms 1, 2
+// and 4 walk the K-chunks in ascending order, the three column shifts and the three row taps inside each, into one accumulator
+// per (pixel, channel) with the same MFMA and the same epilogue arithmetic -- they differ in how many channels a wave holds and
+// in where the filter fragments wait.  The K split (3) adds two half sums, the older kernel (5) and the SIMT kernels (0) have
+// loops of their own.  uh_conv3x3_fwd_sum_class exports the table; tests/test_gpu_batch_invariant.py holds it to the bits.
+static int fwd_sum_class(int kernel) {
+    return (kernel == FWD_SLAB128 || kernel == FWD_WRES || kernel == FWD_STREAM) ? FWD_SLAB128 : kernel;
+}
 
 struct FwdPlan {
     FwdKernel kernel;
@@ -1916,9 +1929,13 @@ struct FwdPlan {
 // ptrs16 = x0, x1, w and y are 16-byte aligned; y16 = y is.  The differences between the entry points are inputs: only plain
 // bf16 calls (no bf16x3 products, no narrow tensors) keep the filter in registers or split K, PRE never splits K, and BSUM runs
 // two workgroups per CU.
+// plan_B > 0 (the pinned plan of the eval forward): the kernel FORM is the one a launch of plan_B images of this H x W gets, or
+// the launch's own where the two add every pixel's products in the same order (fwd_sum_class); everything that sizes the launch
+// -- tiles, lanes, grid, the 2 GiB test -- stays with the real B.  plan_B = 0: the form of the real B.
 static FwdPlan fwd_plan(int es, int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, bool ptrs16, bool y16,
-                        bool split, bool narrow, bool pre, bool bsum) {
-    const int ntile = B * ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
+                        bool split, bool narrow, bool pre, bool bsum, int plan_B = 0) {
+    const int tiles1 = ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
+    const int ntile = B * tiles1;
     const int ck = 64 / es, Cin = C0 + C1;
     FwdPlan p = {FWD_SIMT, 0, 1, ntile, 256, split, pre, bsum};
     const bool mfma = C0 % ck == 0 && C1 % ck == 0 && Cout % 64 == 0 && ptrs16 && (ld0 * es) % 16 == 0 &&
@@ -1946,15 +1963,24 @@ static FwdPlan fwd_plan(int es, int B, int H, int W, int C0, int C1, int Cout, i
         return gx < ntile ? gx : ntile;
     };
     const bool bf16 = es == 2 && !split && !narrow;
-    if (Cout % 128 == 0 && (int64_t)ntile * (Cout / 128) >= 512) {
+    // the form a launch of nt tiles gets
+    auto form = [&](int64_t nt) {
         // 128-channel slabs halve the halo re-reads, but small feature maps need the extra workgroups
-        p.kernel = FWD_SLAB128; p.slabs = Cout / 128; p.lanes = lanes_for(2, p.slabs);
-    } else if (bf16 && Cin == 64) {
-        p.kernel = FWD_WRES; p.slabs = Cout / 64; p.lanes = lanes_for(2, p.slabs);      // (72 more VGPRs)
-    } else if (bf16 && !pre && fwd_ksplit_ok(ntile, Cin, Cout)) {
-        p.kernel = FWD_KSPLIT; p.slabs = Cout / 64; p.lanes = ntile; p.threads = 512;
-    } else {
-        p.kernel = FWD_STREAM; p.slabs = Cout / 64; p.lanes = lanes_for(bsum ? 2 : 3, p.slabs);
+        if (Cout % 128 == 0 && nt * (Cout / 128) >= 512) return FWD_SLAB128;
+        if (bf16 && Cin == 64) return FWD_WRES;
+        if (bf16 && !pre && fwd_ksplit_ok(nt, Cin, Cout)) return FWD_KSPLIT;
+        return FWD_STREAM;
+    };
+    p.kernel = form(ntile);
+    if (plan_B > 0 && plan_B != B) {
+        const FwdKernel pinned = form((int64_t)plan_B * tiles1);
+        if (fwd_sum_class(pinned) != fwd_sum_class(p.kernel)) p.kernel = pinned;
+    }
+    switch (p.kernel) {
+    case FWD_SLAB128: p.slabs = Cout / 128; p.lanes = lanes_for(2, p.slabs); break;
+    case FWD_WRES: p.slabs = Cout / 64; p.lanes = lanes_for(2, p.slabs); break;      // (72 more VGPRs)
+    case FWD_KSPLIT: p.slabs = Cout / 64; p.lanes = ntile; p.threads = 512; break;   // one tile per workgroup, at any tile count
+    default: p.slabs = Cout / 64; p.lanes = lanes_for(bsum ? 2 : 3, p.slabs); break;
     }
     return p;
 }
@@ -1999,7 +2025,7 @@ static int conv3x3_fwd_dispatch(const T* x0, int C0, int ld0, const T* x1, int C
                                 const float* ep_shift, bool* ep_done, bool split = false, int C0v = -1, int C1v = -1,
                                 int Coutv = -1, bool wfrag = false, const float* pre_scale = nullptr,
                                 const float* pre_shift = nullptr, const T* bs_y = nullptr, int bs_ld = 0,
-                                const float* bs_coef = nullptr) {
+                                const float* bs_coef = nullptr, int plan_B = 0) {
     const bool narrow = C0v >= 0;          // narrow tensors: only the LDS-DMA MFMA kernel implements the channel masks
     const bool pre = pre_scale != nullptr; // BatchNorm + ReLU of the producer applied to source 0 by this kernel's loader
     const bool bsum = bs_y != nullptr;     // backward-data + the BatchNorm-backward sums of the tensor it differentiates (stats = the partial rows)
@@ -2011,7 +2037,7 @@ static int conv3x3_fwd_dispatch(const T* x0, int C0, int ld0, const T* x1, int C
     const int tilesX = (W + TILE - 1) / TILE, tilesY = (H + TILE - 1) / TILE;
     const int Cin = C0 + C1;
     const bool ptrs16 = uh_aligned16(x0) && (C1 == 0 || uh_aligned16(x1)) && uh_aligned16(w) && uh_aligned16(y);
-    const FwdPlan p = fwd_plan(ES, B, H, W, C0, C1, Cout, ld0, ld1, ldy, ptrs16, uh_aligned16(y), split, narrow, pre, bsum);
+    const FwdPlan p = fwd_plan(ES, B, H, W, C0, C1, Cout, ld0, ld1, ldy, ptrs16, uh_aligned16(y), split, narrow, pre, bsum, plan_B);
     if (p.kernel != FWD_SIMT && p.kernel != FWD_LARGE) {
         if (ep_scale && !(uh_aligned16(ep_scale) && uh_aligned16(ep_shift))) ep_scale = ep_shift = nullptr;   // 16-B loads
         UH_REQUIRE(!split || ES == 4, "conv3x3_fwd: bf16x3 needs fp32 tensors");
@@ -2120,12 +2146,16 @@ extern "C" int uh_conv3x3_fwd(const void* x0, int C0, int ld0, const void* x1, i
 // Will uh_conv3x3_fwd take the LDS-DMA MFMA kernel for this call (pointers assumed 16-byte aligned)?  Only then may the
 // filter be packed fragment-major (dt | UH_WFRAG in uh_pack_w3x3 and in the conv call): 8 whole cache lines per fragment
 // load instead of 16 half lines.
-extern "C" int uh_conv3x3_wfrag_ok(int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, int dt) {
+extern "C" int uh_conv3x3_wfrag_ok_plan(int B, int plan_B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy,
+                                        int dt) {
     if (dt != UH_F32 && dt != UH_BF16) return 0;
-    if (B <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0) return 0;
+    if (B <= 0 || plan_B < 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0) return 0;
     const FwdKernel k = fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, ld0, ld1, ldy, true, true, false, false, false,
-                                 false).kernel;
+                                 false, plan_B).kernel;
     return k != FWD_SIMT && k != FWD_LARGE;
+}
+extern "C" int uh_conv3x3_wfrag_ok(int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, int dt) {
+    return uh_conv3x3_wfrag_ok_plan(B, 0, H, W, C0, C1, Cout, ld0, ld1, ldy, dt);
 }
 
 // Which kernel uh_conv3x3_fwd gives a call with dense pitches and 16-byte aligned pointers (FwdKernel): BatchPredictor only
@@ -2135,6 +2165,21 @@ extern "C" int uh_conv3x3_fwd_kernel(int B, int H, int W, int C0, int C1, int Co
     UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_fwd_kernel: bad dtype %d", dt);
     return fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, true, true, dt == UH_F32X3, false, false,
                     false).kernel;
+}
+
+// The same question for the pinned call: the kernel uh_conv3x3_fwd_affine_relu_plan(.., B, plan_B, ..) runs.  plan_B = 0 is
+// uh_conv3x3_fwd_kernel(B, ..).
+extern "C" int uh_conv3x3_fwd_kernel_plan(int B, int plan_B, int H, int W, int C0, int C1, int Cout, int dt) {
+    UH_REQUIRE(B > 0 && plan_B >= 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd_kernel_plan: bad shape");
+    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_fwd_kernel_plan: bad dtype %d", dt);
+    return fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, true, true, dt == UH_F32X3, false, false,
+                    false, plan_B).kernel;
+}
+
+// The summation class of a kernel code (fwd_sum_class): two codes with one class give bit-identical outputs.
+extern "C" int uh_conv3x3_fwd_sum_class(int kernel) {
+    UH_REQUIRE(kernel >= FWD_SIMT && kernel <= FWD_LARGE, "uh_conv3x3_fwd_sum_class: bad kernel code %d", kernel);
+    return fwd_sum_class(kernel);
 }
 
 // Training forward whose input is the RAW output y_prev of the previous conv: the BatchNorm + ReLU between the two convs of a
@@ -2203,9 +2248,12 @@ extern "C" int uh_conv3x3_dgrad_bnsum(const void* dy, int Cdy, int lddy, const v
 // Inference forward: z = max(conv(x, w) * scale + shift, 0) with the eval-mode BatchNorm coefficients of
 // uh_bn_eval_coeffs.  The MFMA and stem kernels apply them to the accumulators (no intermediate tensor, one
 // rounding); the fallback kernels are followed by the in-place uh_bn_relu_apply pass.
-extern "C" int uh_conv3x3_fwd_affine_relu(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1, const void* w,
-                                          void* z, int ldz, int Cout, const float* scale, const float* shift, int B,
-                                          int H, int W, int dt, uh_stream stream) {
+// uh_conv3x3_fwd_affine_relu_plan: the same call with the kernel form pinned to the one a launch of plan_B images gets (fwd_plan):
+// with plan_B = 1 every image of a batch comes out bit for bit as it does alone, at any B.
+extern "C" int uh_conv3x3_fwd_affine_relu_plan(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1, const void* w,
+                                               void* z, int ldz, int Cout, const float* scale, const float* shift, int B,
+                                               int plan_B, int H, int W, int dt, uh_stream stream) {
+    UH_REQUIRE(plan_B >= 0, "uh_conv3x3_fwd_affine_relu: bad plan length %d", plan_B);
     UH_REQUIRE(x0 && w && z && scale && shift, "uh_conv3x3_fwd_affine_relu: null pointer");
     UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd_affine_relu: bad shape");
     UH_REQUIRE(ld0 >= C0 && ldz >= Cout && (C1 == 0 || (x1 && ld1 >= C1)), "uh_conv3x3_fwd_affine_relu: bad strides");
@@ -2218,21 +2266,33 @@ extern "C" int uh_conv3x3_fwd_affine_relu(const void* x0, int C0, int ld0, const
     int rc;
     if (dt == UH_BF16)
         rc = conv3x3_fwd_dispatch<bf16_t>((const bf16_t*)x0, C0, ld0, (const bf16_t*)x1, C1, ld1, (const bf16_t*)w,
-                                          (bf16_t*)z, ldz, Cout, nullptr, B, H, W, st, scale, shift, &done, false, -1, -1, -1, wfrag);
+                                          (bf16_t*)z, ldz, Cout, nullptr, B, H, W, st, scale, shift, &done, false, -1, -1, -1, wfrag,
+                                          nullptr, nullptr, nullptr, 0, nullptr, plan_B);
     else
         rc = conv3x3_fwd_dispatch<float>((const float*)x0, C0, ld0, (const float*)x1, C1, ld1, (const float*)w, (float*)z,
-                                         ldz, Cout, nullptr, B, H, W, st, scale, shift, &done, dt == UH_F32X3, -1, -1, -1, wfrag);
+                                         ldz, Cout, nullptr, B, H, W, st, scale, shift, &done, dt == UH_F32X3, -1, -1, -1, wfrag,
+                                         nullptr, nullptr, nullptr, 0, nullptr, plan_B);
     if (rc != UH_OK || done) return rc;
     return uh_bn_relu_apply(z, ldz, scale, shift, z, ldz, (int64_t)B * H * W, Cout, dt == UH_BF16 ? UH_BF16 : UH_F32, stream);
+}
+
+extern "C" int uh_conv3x3_fwd_affine_relu(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1, const void* w,
+                                          void* z, int ldz, int Cout, const float* scale, const float* shift, int B,
+                                          int H, int W, int dt, uh_stream stream) {
+    return uh_conv3x3_fwd_affine_relu_plan(x0, C0, ld0, x1, C1, ld1, w, z, ldz, Cout, scale, shift, B, 0, H, W, dt, stream);
 }
 
 // Narrow tensors (small-width nets: 8..32 channels): the filter pack and the K loop use channel counts rounded up to the
 // MFMA granularity (C0 / C1 multiples of a 64-byte chunk, Cout multiple of 64) while x0 / x1 / y hold only C0v / C1v /
 // Coutv channels (multiples of a 16-byte piece) at their own pixel strides: nothing padded ever reaches HBM.
 // scale == NULL: plain forward (+ statistics, Cout columns per slab row); else the fused inference epilogue.
-extern "C" int uh_conv3x3_fwd_narrow(const void* x0, int C0, int C0v, int ld0, const void* x1, int C1, int C1v, int ld1,
-                                     const void* w, void* y, int ldy, int Cout, int Coutv, float* stat_partials,
-                                     const float* scale, const float* shift, int B, int H, int W, int dt, uh_stream stream) {
+// uh_conv3x3_fwd_narrow_plan: the same under the pinned plan (fwd_plan: plan_B).  A narrow call only ever chooses between the
+// streaming form and 128-channel slabs, which sum alike, so today the pin changes nothing here; it is taken for the day they differ.
+extern "C" int uh_conv3x3_fwd_narrow_plan(const void* x0, int C0, int C0v, int ld0, const void* x1, int C1, int C1v, int ld1,
+                                          const void* w, void* y, int ldy, int Cout, int Coutv, float* stat_partials,
+                                          const float* scale, const float* shift, int B, int plan_B, int H, int W, int dt,
+                                          uh_stream stream) {
+    UH_REQUIRE(plan_B >= 0, "uh_conv3x3_fwd_narrow: bad plan length %d", plan_B);
     UH_REQUIRE(x0 && w && y, "uh_conv3x3_fwd_narrow: null pointer");
     UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd_narrow: bad shape");
     UH_REQUIRE(C0v > 0 && C0v <= C0 && C1v >= 0 && C1v <= C1 && Coutv > 0 && Coutv <= Cout, "uh_conv3x3_fwd_narrow: bad valid counts");
@@ -2247,12 +2307,21 @@ extern "C" int uh_conv3x3_fwd_narrow(const void* x0, int C0, int C0v, int ld0, c
     int rc;
     if (dt == UH_BF16)
         rc = conv3x3_fwd_dispatch<bf16_t>((const bf16_t*)x0, C0, ld0, (const bf16_t*)x1, C1, ld1, (const bf16_t*)w, (bf16_t*)y,
-                                          ldy, Cout, stat_partials, B, H, W, st, scale, shift, &done, false, C0v, C1v, Coutv);
+                                          ldy, Cout, stat_partials, B, H, W, st, scale, shift, &done, false, C0v, C1v, Coutv,
+                                          false, nullptr, nullptr, nullptr, 0, nullptr, plan_B);
     else
         rc = conv3x3_fwd_dispatch<float>((const float*)x0, C0, ld0, (const float*)x1, C1, ld1, (const float*)w, (float*)y, ldy,
-                                         Cout, stat_partials, B, H, W, st, scale, shift, &done, dt == UH_F32X3, C0v, C1v, Coutv);
+                                         Cout, stat_partials, B, H, W, st, scale, shift, &done, dt == UH_F32X3, C0v, C1v, Coutv,
+                                         false, nullptr, nullptr, nullptr, 0, nullptr, plan_B);
     if (rc != UH_OK || !scale || done) return rc;
     return uh_bn_relu_apply(y, ldy, scale, shift, y, ldy, (int64_t)B * H * W, Coutv, dt == UH_BF16 ? UH_BF16 : UH_F32, stream);
+}
+
+extern "C" int uh_conv3x3_fwd_narrow(const void* x0, int C0, int C0v, int ld0, const void* x1, int C1, int C1v, int ld1,
+                                     const void* w, void* y, int ldy, int Cout, int Coutv, float* stat_partials,
+                                     const float* scale, const float* shift, int B, int H, int W, int dt, uh_stream stream) {
+    return uh_conv3x3_fwd_narrow_plan(x0, C0, C0v, ld0, x1, C1, C1v, ld1, w, y, ldy, Cout, Coutv, stat_partials, scale, shift, B, 0,
+                                      H, W, dt, stream);
 }
 
 // =====================================================================================

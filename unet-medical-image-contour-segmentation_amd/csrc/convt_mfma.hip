@@ -387,6 +387,16 @@ extern "C" int uh_convt2x2_mfma_ok(int B, int h, int w_, int Cin, int Cout, int 
     return 1;
 }
 
+// The pinned choice of the eval forward (ops.plan_images): the GEMM is taken iff a launch of plan_B images qualifies -- then
+// B * h * w is a multiple of the chunk for every B, and a column of the GEMM (one input pixel: its own K loop over Cin in a fixed
+// order, whichever 128-pixel tile it sits in) does not depend on the batch -- and the real launch fits the 2 GiB windows.
+// plan_B = 0: uh_convt2x2_mfma_ok(B, ..).
+extern "C" int uh_convt2x2_mfma_ok_plan(int B, int plan_B, int h, int w_, int Cin, int Cout, int Ho, int Wo, int dt) {
+    if (B <= 0 || plan_B < 0) return 0;
+    if (plan_B > 0 && !uh_convt2x2_mfma_ok(plan_B, h, w_, Cin, Cout, Ho, Wo, dt)) return 0;
+    return uh_convt2x2_mfma_ok(B, h, w_, Cin, Cout, Ho, Wo, dt);
+}
+
 extern "C" int uh_convt2x2_fwd_mfma(const void* x, int ldx, const void* w_fwd, const float* bias, void* y, int ldy, int B,
                                     int h, int w_, int Cin, int Cout, int Ho, int Wo, int pad_top, int pad_left, int dt,
                                     uh_stream stream) {

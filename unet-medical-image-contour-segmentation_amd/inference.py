@@ -8,13 +8,17 @@ import torch
 
 class GraphedForward:
     """`g = GraphedForward(model, example_images); logits = g(images)` -- same result as `model.eval()(images)`.
-    The returned tensor is the graph's static output buffer: copy it if it must survive the next call."""
+    The returned tensor is the graph's static output buffer: copy it if it must survive the next call.
+    `plan_images` > 0: warm-up and capture run under ops.plan_images(plan_images) -- the kernel choice is made on the host
+    while the graph is captured, so the replays keep it (1: every image is computed bit for bit as it is alone).  Outside
+    an instance built with it, an ops.plan_images block that is active at construction time is captured just the same."""
 
-    def __init__(self, model: torch.nn.Module, example: torch.Tensor, amp: bool = True, warmup: int = 3):
+    def __init__(self, model: torch.nn.Module, example: torch.Tensor, amp: bool = True, warmup: int = 3, plan_images: int = 0):
         if not example.is_cuda:
             raise RuntimeError("GraphedForward needs GPU tensors (no CPU fallback exists)")
         self.model = model.eval()
         self.amp = amp
+        self.plan_images = int(plan_images)
         self.static_in = example.detach().clone(memory_format=torch.preserve_format)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -29,6 +33,10 @@ class GraphedForward:
 
     def _forward(self, x):
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.amp):
+            if self.plan_images:
+                from . import ops
+                with ops.plan_images(self.plan_images):
+                    return self.model(x)
             return self.model(x)
 
     def __call__(self, images: torch.Tensor) -> torch.Tensor:

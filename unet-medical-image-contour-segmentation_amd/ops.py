@@ -5,6 +5,7 @@ stride may exceed C (channel slices of a wider buffer); the user-facing modules 
 logical NCHW views.  Everything here requires GPU tensors: there is no CPU fallback."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Optional, Tuple
@@ -172,10 +173,35 @@ def conv_dt(x: torch.Tensor, C0: int, C1: int, Cout: int, need_dx: bool) -> int:
 WFRAG = True
 
 
-def wfrag_ok(B: int, H: int, W: int, C0: int, C1: int, Cout: int, ld0: int, ld1: int, ldy: int, dt: int) -> bool:
-    """May the filter of this conv call be packed fragment-major?  (dt: UH_F32 / UH_BF16; bf16x3 packs are KRSC.)"""
+# Plan length of the eval forward (0 = off).  Under `with plan_images(1):` the eval-mode Conv->BN->ReLU and the transposed
+# convolution take, for a batch of B images, the kernel form ONE image of that size gets (uh_conv3x3_fwd_affine_relu_plan,
+# uh_convt2x2_mfma_ok_plan), so every image comes out bit for bit as it does alone, whatever B.  The choice is made on the
+# host when the call is enqueued: a graph captured under it keeps it.  Training-mode layers do not read it.
+PLAN_IMAGES = 0
+
+
+@contextlib.contextmanager
+def plan_images(n: int = 1):
+    """Pin the kernel choice of the eval forward to that of a launch of `n` images (0: the launch's own choice)."""
+    global PLAN_IMAGES
+    n = int(n)
+    if n < 0:
+        raise ValueError("plan_images: the plan length must be >= 0")
+    prev, PLAN_IMAGES = PLAN_IMAGES, n
+    try:
+        yield
+    finally:
+        PLAN_IMAGES = prev
+
+
+def wfrag_ok(B: int, H: int, W: int, C0: int, C1: int, Cout: int, ld0: int, ld1: int, ldy: int, dt: int,
+             plan: int = 0) -> bool:
+    """May the filter of this conv call be packed fragment-major?  (dt: UH_F32 / UH_BF16; bf16x3 packs are KRSC.)
+    `plan`: the call runs under the pinned plan of that length."""
     if not WFRAG or dt not in (UH_F32, UH_BF16):
         return False
+    if plan:
+        return bool(LIB.query("uh_conv3x3_wfrag_ok_plan", B, plan, H, W, C0, C1, Cout, ld0, ld1, ldy, dt))
     return bool(LIB.query("uh_conv3x3_wfrag_ok", B, H, W, C0, C1, Cout, ld0, ld1, ldy, dt))
 
 
@@ -663,7 +689,8 @@ class ConvBnReluFn(Function):
         cdt = conv_dt(x0, C0, C1, Cout, need_dx and training)
         # fragment-major filter packs where the LDS-DMA MFMA kernel runs (forward: this call; backward-data: the conv of dy
         # [B,H,W,Cout] with the transposed filter into dx [B,H,W,Cin])
-        frag_f = wfrag_ok(B, H, W, C0, C1, Cout, pixel_ld(x0), 0 if x1 is None else pixel_ld(x1), Cout, cdt)
+        plan = 0 if training else PLAN_IMAGES
+        frag_f = wfrag_ok(B, H, W, C0, C1, Cout, pixel_ld(x0), 0 if x1 is None else pixel_ld(x1), Cout, cdt, plan)
         frag_d = bool(need_dx and training) and wfrag_ok(B, H, W, Cout, 0, Cin, Cout, 0, Cin, cdt)
         if training:
             hit = WEIGHT_PACK.lookup(weight, x0.dtype, frag_f, frag_d) if (WEIGHT_PACK is not None and cdt != UH_F32X3) else None
@@ -695,9 +722,14 @@ class ConvBnReluFn(Function):
             # applied with the ReLU inside the conv epilogue; nothing is kept for a backward pass
             scale, shift = bn_eval_coeffs_cached(gamma, beta, running_mean, running_var, eps, Cout, Cout)
             z = torch.empty(B, H, W, Cout, dtype=x0.dtype, device=dev)
-            LIB.call("uh_conv3x3_fwd_affine_relu", x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1,
-                     pixel_ld(x1) if x1 is not None else 0, wf.data_ptr(), z.data_ptr(), Cout, Cout, scale.data_ptr(),
-                     shift.data_ptr(), B, H, W, cdt | (UH_WFRAG if frag_f else 0), _stream())
+            if plan:
+                LIB.call("uh_conv3x3_fwd_affine_relu_plan", x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1,
+                         pixel_ld(x1) if x1 is not None else 0, wf.data_ptr(), z.data_ptr(), Cout, Cout, scale.data_ptr(),
+                         shift.data_ptr(), B, plan, H, W, cdt | (UH_WFRAG if frag_f else 0), _stream())
+            else:
+                LIB.call("uh_conv3x3_fwd_affine_relu", x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1,
+                         pixel_ld(x1) if x1 is not None else 0, wf.data_ptr(), z.data_ptr(), Cout, Cout, scale.data_ptr(),
+                         shift.data_ptr(), B, H, W, cdt | (UH_WFRAG if frag_f else 0), _stream())
             ctx.training = False
             if tail != TAIL_NONE:
                 raise RuntimeError("ConvBnReluFn: fused tails are a training-mode path")
@@ -1151,8 +1183,13 @@ class ConvBnReluNarrowFn(Function):
             scale, shift = bn_eval_coeffs_cached(gamma, beta, running_mean, running_var, eps, Cout, Cop)
             z = torch.empty(B, H, W, Cout, dtype=x0.dtype, device=dev)
             with _Timed("conv3x3_fwd_narrow", flops):
-                LIB.call("uh_conv3x3_fwd_narrow", x0.data_ptr(), Cp0, C0m, ld0, _p(x1), Cp1, C1m, ld1, wf.data_ptr(),
-                         z.data_ptr(), Cout, Cop, Cout, None, scale.data_ptr(), shift.data_ptr(), B, H, W, cdt, _stream())
+                if PLAN_IMAGES:
+                    LIB.call("uh_conv3x3_fwd_narrow_plan", x0.data_ptr(), Cp0, C0m, ld0, _p(x1), Cp1, C1m, ld1, wf.data_ptr(),
+                             z.data_ptr(), Cout, Cop, Cout, None, scale.data_ptr(), shift.data_ptr(), B, PLAN_IMAGES, H, W, cdt,
+                             _stream())
+                else:
+                    LIB.call("uh_conv3x3_fwd_narrow", x0.data_ptr(), Cp0, C0m, ld0, _p(x1), Cp1, C1m, ld1, wf.data_ptr(),
+                             z.data_ptr(), Cout, Cop, Cout, None, scale.data_ptr(), shift.data_ptr(), B, H, W, cdt, _stream())
             ctx.training = False
             return z
         coef = torch.empty(4 * Cout, dtype=torch.float32, device=dev)
@@ -1358,7 +1395,7 @@ class ConvTranspose2x2PadFn(Function):
     (csrc/convt_mfma.hip) when the shape qualifies, else the LDS-tiled SIMT kernels of csrc/convt_1x1.hip."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, Ho: int, Wo: int):
+    def forward(ctx, x, weight, bias, Ho: int, Wo: int, training: bool = True):
         _require_gpu(x, "activation")
         x = dense_nhwc(x)
         B, h, w, Cin = x.shape
@@ -1368,7 +1405,10 @@ class ConvTranspose2x2PadFn(Function):
         pt, pl = _pad_geometry(h, w, Ho, Wo)
         y = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
         dt = _dt(x)
-        mfma = bool(LIB.query("uh_convt2x2_mfma_ok", B, h, w, Cin, Cout, Ho, Wo, dt))
+        if PLAN_IMAGES and not training:      # eval forward under plan_images: the choice one image gets
+            mfma = bool(LIB.query("uh_convt2x2_mfma_ok_plan", B, PLAN_IMAGES, h, w, Cin, Cout, Ho, Wo, dt))
+        else:
+            mfma = bool(LIB.query("uh_convt2x2_mfma_ok", B, h, w, Cin, Cout, Ho, Wo, dt))
         if mfma and dt == UH_F32 and FP32_MODE == "bf16x3":
             dt = UH_F32X3                    # split products on the bf16 matrix pipe (both operands split in registers)
         wd = None
@@ -1423,7 +1463,7 @@ class ConvTranspose2x2PadFn(Function):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
             LIB.call("uh_convt2x2_wgrad", dy.data_ptr(), pixel_ld(dy), x.data_ptr(), pixel_ld(x), dw.data_ptr(),
                      db.data_ptr(), ws.data_ptr(), nbytes, B, h, w, Cin, Cout, Ho, Wo, pt, pl, dt, _stream())
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None
 
 
 # ----------------------------------------------------------------------------- spatial attention

@@ -3,7 +3,8 @@
     predict_img(model, full_img, device) -> np.ndarray[H, W] of class indices        predict.py:15-29
     mask_to_image(mask) -> PIL.Image (0 / 128 / 255 grey levels)                      predict.py:52-58
     preprocess_image(pil_img, scale=1.0) -> float32 [C, H, W]                         data_loading.py:65-91 (image branch)
-    BatchPredictor(model, batch=8, postprocess=True)(images) -> [uint8 [H, W] grey]   predict.py:120-135 for a list of images
+    BatchPredictor(model, batch=8, postprocess=True, batch_invariant=False)(images) -> [uint8 [H, W] grey]
+                                                                                      predict.py:120-135 for a list of images
     python -m unet_amd.predict -m model.pth -i DIR [-o OUT]                           predict.py:31-152 (predict_cli.py)
 
 predict_img is the reference's one-image call: the forward runs the eval-mode kernels (BatchNorm running statistics folded
@@ -140,14 +141,21 @@ class BatchPredictor:
         700 x 300 image has 18 tiles at the level of up1 (256 -> 128 channels), so 7 images split K and 8 do not.
     `launch_lengths` asks the library for both choices (uh_convt2x2_mfma_ok, uh_conv3x3_fwd_kernel) and only forms
     launches in which every layer gets the kernel it gets for one image; a batch is cut into the fewest such launches,
-    down to one image per launch where nothing longer qualifies."""
+    down to one image per launch where nothing longer qualifies.
+
+    `batch_invariant=True` lifts the cutting: the forward runs under ops.plan_images(1), which pins every layer of a launch
+    to the kernel one image gets (uh_conv3x3_fwd_affine_relu_plan, uh_convt2x2_mfma_ok_plan), so a launch of any length
+    gives every image the bits it gets alone.  `launch_lengths` then asks the pinned queries and returns every B up to
+    `batch` that no real-B limit (a tensor past the 2 GiB window: another kernel) excludes.  The masks are those of the
+    default mode; only the number of launches differs."""
 
     MAX_GRAPHS = 4
 
     def __init__(self, model: torch.nn.Module, batch: int = 8, postprocess: bool = True, amp: bool = True, device=None,
-                 min_area: int = 15000, morph_kernel_size: int = 3):
+                 min_area: int = 15000, morph_kernel_size: int = 3, batch_invariant: bool = False):
         if batch < 1:
             raise ValueError("batch must be >= 1")
+        self.batch_invariant = bool(batch_invariant)
         if getattr(model, "n_classes", None) == 1:
             # predict.py:27 takes argmax(dim=1) of a one-channel tensor: all zeros.  Not reproduced.
             raise ValueError("BatchPredictor needs a multi-class head: predict.py's argmax over one channel is all zeros. "
@@ -228,14 +236,23 @@ class BatchPredictor:
         if key not in self._lengths:
             from ._lib import LIB, UH_BF16, UH_F32
             dt = UH_BF16 if self.amp else UH_F32
+            pin = 1 if getattr(self, "batch_invariant", False) else 0     # (tests build the object without __init__)
 
             def choice(B, kind, m, k):
                 h, w = H >> k, W >> k
                 if h < 1 or w < 1:
                     return 0
                 if kind == "convt":
+                    if pin and B > 1:
+                        return LIB.query("uh_convt2x2_mfma_ok_plan", B, pin, h, w, m.in_channels, m.out_channels, H >> (k - 1),
+                                         W >> (k - 1), dt)
                     return LIB.query("uh_convt2x2_mfma_ok", B, h, w, m.in_channels, m.out_channels, H >> (k - 1), W >> (k - 1), dt)
-                return LIB.query("uh_conv3x3_fwd_kernel", B, h, w, m.in_channels, 0, m.out_channels, dt)
+                if pin and B > 1:
+                    # the summation class of the kernel the pinned call runs: equal to one image's unless a real-B limit moved it
+                    code = LIB.query("uh_conv3x3_fwd_kernel_plan", B, pin, h, w, m.in_channels, 0, m.out_channels, dt)
+                    return LIB.query("uh_conv3x3_fwd_sum_class", code)
+                code = LIB.query("uh_conv3x3_fwd_kernel", B, h, w, m.in_channels, 0, m.out_channels, dt)
+                return LIB.query("uh_conv3x3_fwd_sum_class", code) if pin else code
 
             self._lengths[key] = [B for B in range(1, self.batch + 1)
                                   if all(choice(B, kind, m, k) == choice(1, kind, m, k)
@@ -251,13 +268,16 @@ class BatchPredictor:
             if g is None:
                 while len(self._graphs) >= self.MAX_GRAPHS:
                     self._graphs.popitem(last=False)                  # least recently used
-                g = GraphedForward(self.model, x, amp=self.amp)
+                g = GraphedForward(self.model, x, amp=self.amp, plan_images=1 if self.batch_invariant else 0)
             self._graphs[size] = g
             self.graph_replays += 1
             return g(x)
         if x.shape[0] == full:
             self._seen.add(size)
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.amp):
+            if self.batch_invariant:
+                with ops.plan_images(1):
+                    return self.model(x)
             return self.model(x)
 
     def run_batch(self, arrays: List[np.ndarray], grey: bool = True) -> np.ndarray:

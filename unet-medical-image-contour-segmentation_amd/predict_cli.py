@@ -1,11 +1,13 @@
 """The reference's prediction command line, /root/reference/predict.py:31-152, on the HIP path:
 
     python -m unet_amd.predict -m model.pth -i FILE_OR_DIR [-o OUT] [-n] [-v] [--no-postprocess]
-                               [--arch UNet] [-c 3] [--bilinear] [--no-amp] [-b 8] [--workers 8]
+                               [--arch UNet] [-c 3] [--bilinear] [--no-amp] [-b 8] [--workers 8] [--no-batch-invariant]
 
 Every image is predicted at its own size (scale 1).  The images of a folder are decoded by a thread pool, grouped by size,
 run through BatchPredictor in batches (prepare, eval forward, classes, post-processing and grey coding on the device, one
-upload and one download per batch) and encoded to PNG by the same pool while the next batch runs.
+upload and one download per batch) and encoded to PNG by the same pool while the next batch runs.  The forward is
+batch-invariant (BatchPredictor(batch_invariant=True)): a batch is one launch and every image gets the bits it gets alone;
+--no-batch-invariant cuts the batches instead, to the same files.
 
 Reference behaviour that is kept, awkward parts included:
   - predict.py:33-38  the flags -m, -i (both required), -o, -v, -n, and -p, a store_true whose default is already True;
@@ -58,6 +60,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--no-amp", dest="amp", action="store_false", default=True, help="Run the forward in fp32 (default: bf16 autocast)")
     p.add_argument("--batch-size", "-b", dest="batch_size", type=int, default=8, help="Images of one size per device batch")
     p.add_argument("--workers", type=int, default=8, help="Decode / encode threads")
+    p.add_argument("--batch-invariant", dest="batch_invariant", action="store_true", default=True,
+                   help="Pin every layer of a batch to the kernel one image gets, so that full batches run as one launch "
+                        "(the default; the masks are the same either way)")
+    p.add_argument("--no-batch-invariant", dest="batch_invariant", action="store_false",
+                   help="Cut every batch into launches in which each layer gets one image's kernel by itself")
     return p
 
 
@@ -200,7 +207,8 @@ def main(argv=None) -> int:
     from .predict import BatchPredictor
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info("Using device %s", device)
-    predictor = BatchPredictor(model, batch=args.batch_size, postprocess=args.postprocess, amp=args.amp, device=device)
+    predictor = BatchPredictor(model, batch=args.batch_size, postprocess=args.postprocess, amp=args.amp, device=device,
+                               batch_invariant=args.batch_invariant)
     if args.output is not None and not args.no_save:
         os.makedirs(args.output, exist_ok=True)                       # predict.py:48
     show = (lambda path, img, grey: _show(plt, path, img, grey)) if plt is not None else None

@@ -8,8 +8,9 @@ pixel stage on the device and one stream from the RAW upload to the contour poin
     stage 4  utils/png_denormalize.py crop + LANCZOS to the original size  uh_resample_lanczos_u8 (class -> grey table)
     stage 5  utils/mask2polygon.py    external contours -> JSON            uh_contours_count / uh_contours_emit
 
-    ContourPipeline(model, width, height, window_width, window_length, batch=8, postprocess=True)
+    ContourPipeline(model, width, height, window_width, window_length, batch=8, postprocess=True, batch_invariant=False)
     python -m unet_amd.seg_main --input-raw DIR -o ROOT --width W --height H -ww WW -wl WL -m model.pth [--keep-stages]
+                                [--batch-invariant]
 
 The reference chains five scripts by subprocess with a PNG encode / decode between them; the intermediate images here
 stay on the device unless --keep-stages asks for the reference's directories 1-4 (pixel-identical, the PNG encoders
@@ -37,11 +38,14 @@ from ._lib import LIB
 
 class ContourPipeline:
     """`pipe(raws)` -> one LabelMe dict (or None: no contour) per RAW image.  raws: uint16 [B,H,W] (numpy or a GPU tensor;
-    int16 bits accepted).  `pipe.run_batch(raws)` also returns the intermediate device tensors."""
+    int16 bits accepted).  `pipe.run_batch(raws)` also returns the intermediate device tensors ("logits" is the forward's
+    output buffer, which a graphed batch overwrites on its next run).
+    `batch_invariant=False`: every launch takes its own kernels, so logits (by ~1e-4; a tie may flip a class) depend on
+    `batch`.  True: the forward runs under ops.plan_images(1) and an image's logits are, bit for bit, those it gets alone."""
 
     def __init__(self, model: torch.nn.Module, width: int, height: int, window_width: int, window_length: int,
                  batch: int = 8, postprocess: bool = True, device=None, amp: bool = True, min_area: int = 15000,
-                 morph_kernel_size: int = 3):
+                 morph_kernel_size: int = 3, batch_invariant: bool = False):
         window_bounds(window_width, window_length)                      # refuses WW < 2
         self.geometry = letterbox_geometry(width, height)                # refuses an empty letterbox
         if batch < 1:
@@ -54,6 +58,7 @@ class ContourPipeline:
         self.ww, self.wl = int(window_width), int(window_length)
         self.batch, self.postprocess, self.amp = int(batch), bool(postprocess), amp
         self.min_area, self.ksize = int(min_area), int(morph_kernel_size)
+        self.batch_invariant = bool(batch_invariant)
         nw, nh, px, py = self.geometry
         self._plan_in = resample_plan(self.width, self.height, nw, nh, self.device)
         self._plan_out = resample_plan(nw, nh, self.width, self.height, self.device)
@@ -104,9 +109,12 @@ class ContourPipeline:
                  TARGET, 0, ops._stream())
         if B == self.batch:
             if self._graph is None:
-                self._graph = GraphedForward(self.model, x, amp=self.amp)
+                self._graph = GraphedForward(self.model, x, amp=self.amp, plan_images=1 if self.batch_invariant else 0)
             return self._graph(x)
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.amp):
+            if self.batch_invariant:
+                with ops.plan_images(1):
+                    return self.model(x)
             return self.model(x)
 
     def _unletterbox(self, classes):
@@ -125,7 +133,7 @@ class ContourPipeline:
             classes = self._mark("postprocess", _postprocess_run, classes, self.min_area, self.ksize)
         grey = self._mark("unletterbox", self._unletterbox, classes)
         contours = self._mark("contours", external_contours, grey)
-        return {"window": win, "canvas": canvas, "argmax": idx, "classes": classes, "grey": grey, "contours": contours}
+        return {"window": win, "canvas": canvas, "logits": logits, "argmax": idx, "classes": classes, "grey": grey, "contours": contours}
 
     def __call__(self, raws, stems: Optional[List[str]] = None):
         res = []
@@ -150,6 +158,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--model", "-m", required=True, help="model weights (.pth state_dict, UNet(1, 3, bilinear=False))")
     p.add_argument("--batch", type=int, default=8, help="images per device batch")
     p.add_argument("--keep-stages", action="store_true", help="also write the reference's directories 1-4")
+    p.add_argument("--batch-invariant", action="store_true",
+                   help="pin every layer to the kernel one image gets: the results do not depend on --batch")
     return p
 
 
@@ -179,7 +189,8 @@ def main(argv=None) -> int:
             os.makedirs(d, exist_ok=True)
     model = UNet(n_channels=1, n_classes=3, bilinear=False)
     load_checkpoint(model, args.model)                                  # mask_values dropped (predict.py:106-109)
-    pipe = ContourPipeline(model, args.width, args.height, args.window_width, args.window_length, batch=args.batch)
+    pipe = ContourPipeline(model, args.width, args.height, args.window_width, args.window_length, batch=args.batch,
+                           batch_invariant=args.batch_invariant)
     stems, raws = [], []
     for f in list_raws(args.input_raw):
         try:

@@ -211,7 +211,7 @@ class Up(nn.Module):
             return x1
         if self.bilinear:
             return ops.UpsampleBilinearPadFn.apply(x1, Ho, Wo)
-        return ops.ConvTranspose2x2PadFn.apply(x1, self.up.weight, self.up.bias, Ho, Wo)
+        return ops.ConvTranspose2x2PadFn.apply(x1, self.up.weight, self.up.bias, Ho, Wo, self.training)
 
     def nhwc(self, x1, x2, tail=None, upsampled: bool = False):
         """`upsampled`: x1 already is the up-sampled, padded tensor (its producer ran with tail=("up", Ho, Wo))."""
