@@ -473,6 +473,41 @@ size_t uh_postprocess_ws_bytes(int B, int H, int W);
 int uh_postprocess_masks(const uint8_t* mask, uint8_t* out, int B, int H, int W, int min_area,
                          int morph_kernel_size, void* ws, size_t ws_bytes, uh_stream stream);
 
+/* ---- contour-distance metrics on the device  (no counterpart in the reference; DESIGN.md section 3 "Contour metrics") ----
+ * For boolean H x W masks P (prediction) and T (truth):
+ *   border S(M)  pixels of M with one of their four edge neighbours outside M; outside the image counts as outside M
+ *   D_M[x]       min over q in S(M) of |x - q|^2, an exact integer in pixel units; 0xFFFFFFFF everywhere if S(M) is empty
+ *   R            sqrt(D_T[p]) for every p in S(P) together with sqrt(D_P[q]) for every q in S(T), one multiset
+ *   HD = max R, HD95 = numpy.percentile(R, 95) (linear interpolation), ASSD = mean R, IoU = |P & T| / |P | T|
+ *   both masks empty: HD = HD95 = ASSD = 0, IoU = 1.  Exactly one empty: the distances are NaN, undefined = 1, IoU = 0.
+ * Integer atomics only, fp64 sums in an order fixed by the image: the same bits on every call and in every batch.
+ * H, W <= 32768 (squared distances are kept in 31 bits), H * W < 2^31; UH_EINVAL otherwise.
+ * uh_mask_border_u8: out[b][y][x] = 1 on the border of (mask == cls), else 0.  DEVICE uint8 [B][H][W] both.
+ * uh_edt_sq_u8: out_u32[b][y][x] = squared distance to the nearest NON-ZERO pixel of feature_u8 (DEVICE uint8 [B][H][W]),
+ *   0xFFFFFFFF in an image without one.  Column scans, then a row pass over the row staged in LDS (W <= 4096; wider rows
+ *   are searched in global memory and need the larger workspace that uh_edt_sq_ws_bytes reports).
+ * uh_contour_metrics: P = (pred_u8 == cls_pred), T = (true_u8 == cls_true) per image of DEVICE uint8 [B][H][W] class maps;
+ *   records_out: DEVICE uh_contour_record[B].  ws: uh_contour_metrics_ws_bytes() bytes, 16-byte aligned; it holds the
+ *   per-image histogram over d^2 ((H-1)^2 + (W-1)^2 + 1 bins of uint32) and is cleared by the call. */
+typedef struct uh_contour_record {
+    uint32_t n_pred, n_true, n_inter, n_union;   /* |P|, |T|, |P & T|, |P | T| */
+    uint32_t n_border_pred, n_border_true;       /* |S(P)|, |S(T)| */
+    uint32_t n;                                  /* |R|: n_border_pred + n_border_true where defined, else 0 */
+    uint32_t max_d2;                             /* max d^2 over R */
+    uint32_t d2_lo, d2_hi;                       /* d^2 of the order statistics floor(v) and floor(v) + 1, v = 0.95 (n - 1) */
+    uint32_t undefined;                          /* 1: exactly one of the masks is empty */
+    uint32_t reserved;
+    double weight;                               /* v - floor(v): HD95 interpolates sqrt(d2_lo) .. sqrt(d2_hi) by it */
+    double sum_dist;                             /* sum over R of sqrt(d^2) */
+    double hd, hd95, assd, iou;
+} uh_contour_record;                             /* 96 bytes: 12 x uint32, then 6 x double */
+int uh_mask_border_u8(const uint8_t* mask, int cls, uint8_t* out, int B, int H, int W, uh_stream stream);
+size_t uh_edt_sq_ws_bytes(int B, int H, int W);
+int uh_edt_sq_u8(const uint8_t* feature_u8, uint32_t* out_u32, int B, int H, int W, void* ws, size_t ws_bytes, uh_stream stream);
+size_t uh_contour_metrics_ws_bytes(int B, int H, int W);
+int uh_contour_metrics(const uint8_t* pred_u8, const uint8_t* true_u8, int cls_pred, int cls_true, uh_contour_record* records_out,
+                       int B, int H, int W, void* ws, size_t ws_bytes, uh_stream stream);
+
 /* ---- input pipeline, device stage  (utils/data_loading.py:65-132, train.py:113-114) ---------------------------
  * What BasicDataset.__getitem__ does to a DECODED image / mask pair, for a whole batch in one pass:
  *   img_u8   DEVICE uint8 [B][Hin][Win][C] (C = 1..4, what np.asarray(PIL image) holds), or NULL (masks only)

@@ -7,6 +7,7 @@ from .utils.boundary_loss import boundary_loss  # noqa: F401
 from .utils.connected_component_loss import connected_component_loss  # noqa: F401
 from .train import FusedRMSprop, seg_loss, train_step, TrainStepper, GraphedTrainStepper  # noqa: F401
 from .evaluate import evaluate  # noqa: F401
+from .utils.contour_metrics import contour_metrics, ContourMetrics  # noqa: F401
 from .predict import predict_img, mask_to_image, preprocess_image, BatchPredictor, plan_batches  # noqa: F401
 from .checkpoint import save_checkpoint, load_checkpoint  # noqa: F401
 from .synthetic import ellipse_batch  # noqa: F401

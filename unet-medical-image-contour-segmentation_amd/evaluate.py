@@ -3,7 +3,10 @@ epilogue), device-side masks, raw Dice and -- with postprocess=True -- the Dice 
 which here runs on the device for the whole batch (the reference copies every image to the host for OpenCV).  With
 epoch_pred_dir the predictions are also written as grey-coded PNGs (evaluate.py:35-40, 88-105, 146-164): the coding is one
 table pass per batch on the device (uh_classes_to_grey_u8), the files are encoded and written by a background writer, and
-evaluate returns once they are on disk.  Without it nothing of that runs."""
+evaluate returns once they are on disk.  Without it nothing of that runs.  With `metrics` (a utils.contour_metrics.ContourMetrics)
+the scored masks of every batch also go through uh_contour_metrics (HD / HD95 / ASSD / IoU); the records stay on the device
+until the accumulator's result() is read.  Without it nothing of that runs either.
+`python -m unet_amd.evaluate -m CKPT --data-root DIR` scores a checkpoint without training (evaluate_cli.py)."""
 from __future__ import annotations
 
 import torch
@@ -45,11 +48,14 @@ class _PredDump:
 
 
 @torch.inference_mode()
-def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True, process_group=None):
+def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True, process_group=None, metrics=None):
     """evaluate.py:12-171.  `postprocess=True` is the reference's default (evaluate.py:13): the second return value is then
     the Dice after post-processing and the minimum is taken over min(raw, post-processed) per batch (evaluate.py:85).
     Batches are consumed lazily; under torch.distributed (every rank evaluating its shard of the validation set) the Dice
-    sums and batch counts are all-reduced so that every rank returns the metric of the whole set."""
+    sums and batch counts are all-reduced so that every rank returns the metric of the whole set.  `metrics`: an accumulator
+    that is updated with the contour-metric records of the raw and (postprocess=True) the post-processed masks of every
+    batch, P and T being exactly the masks whose Dice is taken, and all-reduced where the Dice sums are; the return value
+    is the same 3-tuple either way."""
     net.eval()
     num_val_batches = 0
     dice_score = torch.zeros((), dtype=torch.float32, device=device)
@@ -78,6 +84,11 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
                     dp = dice_coeff(processed, mask_true, reduce_batch_first=False)
                     dice_post += dp
                     cur = torch.minimum(d, dp)                                                  # evaluate.py:85
+                if metrics is not None:
+                    true_u8 = mask_true.to(torch.uint8).contiguous()
+                    metrics.update(ops.contour_metrics(pred.to(torch.uint8).contiguous(), true_u8, 1, 1), "raw")
+                    if postprocess:
+                        metrics.update(ops.contour_metrics(processed_u8.contiguous(), true_u8, 1, 1), "post")
                 if dump is not None:                                                            # evaluate.py:88-105
                     dump.add(num_val_batches, pred.to(torch.uint8), "binary", processed_u8 if postprocess else None, "binary")
             else:
@@ -88,6 +99,11 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
                 if postprocess:
                     processed = postprocess_mask(idx.to(torch.uint8))                           # evaluate.py:125-134
                     dice_post += dice_coeff((processed == 2).float(), true_c, reduce_batch_first=False)
+                if metrics is not None:
+                    true_u8 = mask_true.to(torch.uint8).contiguous()
+                    metrics.update(ops.contour_metrics(idx.to(torch.uint8).contiguous(), true_u8, 2, 2), "raw")
+                    if postprocess:
+                        metrics.update(ops.contour_metrics(processed.contiguous(), true_u8, 2, 2), "post")
                 if dump is not None:                                                            # evaluate.py:146-164
                     dump.add(num_val_batches, idx.to(torch.uint8), "classes", processed if postprocess else None,
                              "postprocessed")
@@ -102,8 +118,21 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
         dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=process_group)
         dist.all_reduce(min_dice, op=dist.ReduceOp.MIN, group=process_group)
         dice_score, dice_post, n = acc[0], acc[1], acc[2].clamp_min(1.0)
+        if metrics is not None:
+            metrics.all_reduce(process_group)
     else:
         n = max(num_val_batches, 1)
     if not postprocess:
         dice_post = dice_score                                                                  # evaluate.py:168-169
     return dice_score / n, dice_post / n, min_dice
+
+
+def main(argv=None) -> int:
+    """`python -m unet_amd.evaluate ...`: scores a checkpoint on a validation split (evaluate_cli.py)."""
+    from .evaluate_cli import main as _main
+    return _main(argv)
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

@@ -1848,3 +1848,57 @@ def classes_to_grey_u8(classes: torch.Tensor, lut: torch.Tensor, out: Optional[t
         raise RuntimeError("classes_to_grey_u8: output must be a contiguous uint8 tensor of the input's shape")
     LIB.call("uh_classes_to_grey_u8", classes.data_ptr(), out.data_ptr(), lut.data_ptr(), classes.numel(), _stream())
     return out
+
+
+# ----------------------------------------------------------------------------- contour metrics (csrc/contour_metrics.hip)
+CONTOUR_RECORD_DOUBLES = 12          # uh_contour_record: 12 x uint32 (= 6 doubles wide), then 6 x double
+_EDT_WS = {}
+_CONTOUR_WS = {}
+
+
+def _u8_batch(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    _require_gpu(t, what)
+    if t.dtype != torch.uint8 or t.dim() != 3 or not t.is_contiguous():
+        raise RuntimeError(f"{what} must be a contiguous uint8 [B,H,W] tensor, got {t.dtype} {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+def _cached_ws(cache: dict, query: str, B: int, H: int, W: int, device) -> torch.Tensor:
+    key = (B, H, W, device)
+    ws = cache.get(key)
+    if ws is None:
+        ws = cache[key] = torch.empty(max(LIB.query(query, B, H, W), 256), dtype=torch.uint8, device=device)
+    return ws
+
+
+def mask_border(mask_u8: torch.Tensor, cls: int) -> torch.Tensor:
+    """uint8 [B,H,W]: 1 on the pixels of (mask == cls) that have one of their four edge neighbours outside it (outside the
+    image counts as outside), 0 elsewhere."""
+    B, H, W = _u8_batch(mask_u8, "mask")
+    out = torch.empty_like(mask_u8)
+    LIB.call("uh_mask_border_u8", mask_u8.data_ptr(), int(cls), out.data_ptr(), B, H, W, _stream())
+    return out
+
+
+def edt_sq(feature_u8: torch.Tensor) -> torch.Tensor:
+    """Exact squared Euclidean distance of every pixel to the nearest non-zero pixel of its image: uint8 [B,H,W] ->
+    int64 [B,H,W] (4294967295 everywhere in an image without a non-zero pixel)."""
+    B, H, W = _u8_batch(feature_u8, "feature")
+    ws = _cached_ws(_EDT_WS, "uh_edt_sq_ws_bytes", B, H, W, feature_u8.device)
+    out = torch.empty(B, H, W, dtype=torch.int32, device=feature_u8.device)
+    LIB.call("uh_edt_sq_u8", feature_u8.data_ptr(), out.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), _stream())
+    return out.to(torch.int64) & 0xFFFFFFFF                         # torch has no arithmetic on uint32
+
+
+def contour_metrics(pred_u8: torch.Tensor, true_u8: torch.Tensor, cls_pred: int, cls_true: int) -> torch.Tensor:
+    """HD / HD95 / ASSD / IoU of (pred == cls_pred) against (true == cls_true) per image: the uh_contour_record table as a
+    float64 [B,12] tensor.  Columns 6..11 are weight, sum_dist, hd, hd95, assd, iou; `.view(torch.int32)[:, :12]` are the
+    integer fields (include/unet_hip.h).  Nothing is read back to the host."""
+    B, H, W = _u8_batch(pred_u8, "pred")
+    if _u8_batch(true_u8, "true") != (B, H, W) or true_u8.device != pred_u8.device:
+        raise RuntimeError(f"contour_metrics: pred {tuple(pred_u8.shape)} and true {tuple(true_u8.shape)} differ")
+    ws = _cached_ws(_CONTOUR_WS, "uh_contour_metrics_ws_bytes", B, H, W, pred_u8.device)
+    rec = torch.empty(B, CONTOUR_RECORD_DOUBLES, dtype=torch.float64, device=pred_u8.device)
+    LIB.call("uh_contour_metrics", pred_u8.data_ptr(), true_u8.data_ptr(), int(cls_pred), int(cls_true), rec.data_ptr(), B, H, W,
+             ws.data_ptr(), ws.numel(), _stream())
+    return rec

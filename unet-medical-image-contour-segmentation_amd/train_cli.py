@@ -2,7 +2,7 @@
 
     python -m unet_amd.train -e 5 -b 1 -l 1e-5 -s 0.5 -c 3 [--bilinear] [-f model.pth] [--no-amp]
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
-                             [--pred-dir DIR]
+                             [--pred-dir DIR] [--metrics]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -14,6 +14,8 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     (train.py:208-216); model_epoch{epochs}.pth, a plain state_dict, in the working directory (train.py:220);
   - --pred-dir DIR (default: off) passes DIR/epoch_{epoch} to evaluate as train.py:99-100 does with ./predictions: the
     validation predictions of every evaluation are written there as grey-coded PNGs (evaluate.py:88-105, 146-164);
+  - --metrics (default: off) also scores every evaluation's masks with the contour metrics (utils/contour_metrics.py) and
+    logs one line with HD95 / HD / ASSD / IoU, raw and post-processed, after the "Validation Dice score" line;
   - --load drops mask_values (train.py:275-280); -v is accepted and unused, as in the reference.
 Input batches come from DeviceBatchLoader: decode threads, pinned collation, rotation + BICUBIC / NEAREST rescale + /255
 + label remap on the device (csrc/data_rescale.hip, csrc/data_prep.hip), bit-identical to stacking ds[i].
@@ -58,6 +60,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=None, help="Seeds model init and shuffling (default: unseeded)")
     p.add_argument("--pred-dir", default=None,
                    help="Write the validation predictions of every evaluation to DIR/epoch_{epoch} as PNGs (default: off)")
+    p.add_argument("--metrics", action="store_true", default=False,
+                   help="Log HD95 / HD / ASSD / IoU of every evaluation after its Dice line (default: off)")
     return p
 
 
@@ -95,7 +99,7 @@ def build_model(name: str, n_classes: int, bilinear: bool):
 
 def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: int, learning_rate: float, amp: bool,
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
-                 train_loader=None, log=None, pred_dir: Optional[str] = None) -> List[Dict]:
+                 train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating."""
@@ -130,13 +134,21 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                 torch.cuda.synchronize(device)
                 te = time.perf_counter()
                 epoch_pred_dir = os.path.join(pred_dir, f"epoch_{epoch}") if pred_dir else None  # train.py:99-100
-                val_score, val_post, val_min = evaluate(model, val_loader, device, amp, epoch_pred_dir)   # postprocess=True
+                acc = None
+                if metrics:
+                    from .utils.contour_metrics import ContourMetrics, format_line
+                    acc = ContourMetrics()
+                val_score, val_post, val_min = evaluate(model, val_loader, device, amp, epoch_pred_dir, metrics=acc)  # postprocess=True
                 lr = cosine_warm_restarts_lr(learning_rate, float(val_score))                    # scheduler.step(val_score)
                 stepper.optimizer.param_groups[0]["lr"] = lr
                 dice = (float(val_score), float(val_post), float(val_min))
                 eval_s += time.perf_counter() - te
                 if log:
                     log(f"Validation Dice score: {dice[0]}  postprocessed: {dice[1]}  min: {dice[2]}")
+                if acc is not None:
+                    contour = acc.result()
+                    if log:
+                        log(format_line(contour))
         torch.cuda.synchronize(device)
         wall = time.perf_counter() - t0
         epoch_loss = 0.0
@@ -186,7 +198,7 @@ def main(argv=None) -> int:
                  f"{'bf16 autocast' if args.amp else 'fp32'}, checkpoints in {args.checkpoint_dir}")
     run_training(model, device, train_set, val_set, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.lr,
                  amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed, workers=args.workers, log=logging.info,
-                 pred_dir=args.pred_dir)
+                 pred_dir=args.pred_dir, metrics=args.metrics)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")
