@@ -539,6 +539,37 @@ int uh_batch_rescale_u8(const uint8_t* img_u8, int C, const uint8_t* mask_u8, co
                         const int* v_coef, int kv, int out_h, int row0, int nrows, const int* x_index, const int* y_index,
                         uint8_t* img_out, uint8_t* mask_out, void* ws, size_t ws_bytes, uh_stream stream);
 
+/* ---- training augmentation of a prepared batch  (no counterpart in the reference; DESIGN.md section 3 "Training
+ * augmentation").  One launch maps what uh_batch_prepare wrote to a new batch of the same shape and dtype:
+ *   image_in   DEVICE NHWC [B][H][W][ld_in >= C] in dt (UH_F32 / UH_BF16), C = 1..4, or NULL (labels only)
+ *   labels_in  DEVICE int64 [B][H][W], or NULL (images only)
+ *   params     DEVICE uh_augment_params [B], one row per item, built on the host (utils/augment.py):
+ *     m[6]       the inverse affine map in Q32 (value * 2^32, rounded to nearest): the source CENTRE coordinate of output
+ *                pixel (x, y) is  sx = m[0] (x + 0.5) + m[1] (y + 0.5) + m[2],  sy = m[3] (x + 0.5) + m[4] (y + 0.5) + m[5],
+ *                evaluated exactly in int64 and rounded to Q16 (half up); pixel i covers [i, i + 1).  Labels take the pixel
+ *                that contains (sx, sy); the image is bilinear at (sx - 0.5, sy - 0.5) with 16-bit weights, in fp32:
+ *                top = p00 + wx (p01 - p00), bot = p10 + wx (p11 - p10), v = top + wy (bot - top), no fused multiply-add,
+ *                a zero weight taking the pixel itself.  |m[i]| < 2^48 (addresses stay inside the image whatever the table holds).
+ *     gamma, contrast, brightness, noise_std   image only, after the geometry, in this order: v = clamp(v, 0, 1)^gamma,
+ *                v = (v - 0.5) contrast + 0.5, v = v + brightness, v = v + noise_std z, then clamp to [0, 1].  A stage whose
+ *                parameter is neutral (1, 1, 0, 0) is skipped; with all four neutral there is no clamp either.
+ *     key[2]     Philox4x32-10 key of the item's noise: element e = (y W + x) C + c takes normal number e & 3 of the block
+ *                with counter (e >> 2, 0, 0, 1); words (0, 1) and (2, 3) are Box-Muller pairs, radius from
+ *                u = (r + 0.5) 2^-32, angle 2 pi r 2^-32, cosine first.
+ *   border     UH_AUG_CLAMP: source indices are clamped to the image (image and labels);
+ *              UH_AUG_FILL: a source pixel outside the image is fill_image, a label outside is fill_label
+ *   image_out / labels_out   same shapes (pixel stride ld_out >= C), not the inputs.  bf16 is computed in fp32 and rounded once.
+ * H, W <= 16384 and H W C < 2^32. */
+enum { UH_AUG_CLAMP = 0, UH_AUG_FILL = 1 };
+typedef struct uh_augment_params {
+    int64_t m[6];
+    float gamma, contrast, brightness, noise_std;
+    uint32_t key[2];
+} uh_augment_params;                             /* 72 bytes: 6 x int64, 4 x float, 2 x uint32 */
+int uh_batch_augment(const void* image_in, int ld_in, const int64_t* labels_in, const uh_augment_params* params, void* image_out,
+                     int ld_out, int64_t* labels_out, int B, int H, int W, int C, int dt, int border, float fill_image,
+                     int fill_label, uh_stream stream);
+
 /* ---- RAW -> contour pipeline, non-inference stages  (seg_main.py; utils/raw2png.py, png_normalize.py, png_denormalize.py,
  * mask2polygon.py).  Batched over B images of one geometry.
  *

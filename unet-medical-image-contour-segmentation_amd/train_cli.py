@@ -2,7 +2,7 @@
 
     python -m unet_amd.train -e 5 -b 1 -l 1e-5 -s 0.5 -c 3 [--bilinear] [-f model.pth] [--no-amp]
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
-                             [--pred-dir DIR] [--metrics]
+                             [--pred-dir DIR] [--metrics] [--augment [SPEC]]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -16,6 +16,9 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     validation predictions of every evaluation are written there as grey-coded PNGs (evaluate.py:88-105, 146-164);
   - --metrics (default: off) also scores every evaluation's masks with the contour metrics (utils/contour_metrics.py) and
     logs one line with HD95 / HD / ASSD / IoU, raw and post-processed, after the "Validation Dice score" line;
+  - --augment [SPEC] (default: off) passes every TRAINING batch through the seeded device augmentation of utils/augment.py
+    (csrc/augment.hip): flips, rotation, scale, shift, brightness, contrast, gamma, noise, drawn per (seed, epoch, item);
+    bare --augment is the preset 'default', SPEC is e.g. "flip,rotate=15,scale=0.1,noise=0.01".  Validation is never augmented;
   - --load drops mask_values (train.py:275-280); -v is accepted and unused, as in the reference.
 Input batches come from DeviceBatchLoader: decode threads, pinned collation, rotation + BICUBIC / NEAREST rescale + /255
 + label remap on the device (csrc/data_rescale.hip, csrc/data_prep.hip), bit-identical to stacking ds[i].
@@ -62,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Write the validation predictions of every evaluation to DIR/epoch_{epoch} as PNGs (default: off)")
     p.add_argument("--metrics", action="store_true", default=False,
                    help="Log HD95 / HD / ASSD / IoU of every evaluation after its Dice line (default: off)")
+    p.add_argument("--augment", nargs="?", const="default", default=None, metavar="SPEC",
+                   help="Augment the training batches on the device: a preset name or e.g. 'flip,rotate=15,scale=0.1,"
+                        "translate=0.05,brightness=0.1,contrast=0.1,gamma=0.2,noise=0.01' (bare flag: 'default'; default: off)")
     return p
 
 
@@ -99,10 +105,13 @@ def build_model(name: str, n_classes: int, bilinear: bool):
 
 def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: int, learning_rate: float, amp: bool,
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
-                 train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False) -> List[Dict]:
+                 train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
+                 augment=None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
-    images over the epoch's wall time without its evaluations) and the seconds spent evaluating."""
+    images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
+    `augment`: an AugmentConfig, a spec string or a BatchAugment for the TRAIN loader (a config is seeded with the loader's
+    seed: `seed`, or the loader's own draw when unseeded); the validation loader never gets one."""
     from .evaluate import evaluate
     from .checkpoint import save_checkpoint
     from .train import TrainStepper, cosine_warm_restarts_lr
@@ -111,6 +120,13 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     if train_loader is None:
         train_loader = DeviceBatchLoader(train_set, batch_size, shuffle=True, drop_last=False, seed=seed, workers=workers,
                                          device=device)
+    if augment is not None:
+        from .utils.augment import BatchAugment
+        if not isinstance(augment, BatchAugment):
+            augment = BatchAugment(augment, train_loader.seed)
+        train_loader.augment = augment
+        if log:
+            log(f"Training augmentation (seed {augment.seed}): {augment.config.spec()}")
     val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
     stepper = TrainStepper(model, lr=learning_rate, amp=amp)
     lr = learning_rate
@@ -180,6 +196,10 @@ def main(argv=None) -> int:
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info(f"Using device {device}")
     root = Path(args.data_root)
+    augment = None
+    if args.augment is not None:
+        from .utils.augment import AugmentConfig
+        augment = AugmentConfig.parse(args.augment)                           # a bad spec fails before anything is loaded
     train_set = BasicDataset(root / "imgs" / "train", root / "masks" / "train", args.scale)
     val_set = BasicDataset(root / "imgs" / "val", root / "masks" / "val", args.scale)
     if args.seed is not None:
@@ -198,7 +218,7 @@ def main(argv=None) -> int:
                  f"{'bf16 autocast' if args.amp else 'fp32'}, checkpoints in {args.checkpoint_dir}")
     run_training(model, device, train_set, val_set, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.lr,
                  amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed, workers=args.workers, log=logging.info,
-                 pred_dir=args.pred_dir, metrics=args.metrics)
+                 pred_dir=args.pred_dir, metrics=args.metrics, augment=augment)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")

@@ -228,10 +228,12 @@ class DeviceBatchLoader:
     the decode threads (raw_item's default; kept for comparison).  `epoch_order(e)` is the item order of epoch e (0-based,
     one epoch per iteration): a seeded permutation when shuffle, else range(len(ds)); `orders` records every epoch served.
     A dataset that does not decode to 8-bit (raw_item raises TypeError: .npy / float images) is served through ds[i] and
-    the host tensors are moved to the device; that is logged once."""
+    the host tensors are moved to the device; that is logged once.
+    `augment`: a utils.augment.BatchAugment; every batch (the host-item fallback too) is passed through it on the device
+    with the 0-based epoch number and the batch's dataset indices.  None (the default) changes nothing."""
 
     def __init__(self, ds, batch_size: int = 1, shuffle: bool = False, drop_last: bool = False, seed=None, workers: int = 8,
-                 device=None, prefetch: int = 2, host_rescale: bool = False):
+                 device=None, prefetch: int = 2, host_rescale: bool = False, augment=None):
         if batch_size < 1 or workers < 1 or prefetch < 1:
             raise ValueError("DeviceBatchLoader: batch_size, workers and prefetch must be positive")
         self.ds, self.batch_size, self.shuffle, self.drop_last = ds, int(batch_size), bool(shuffle), bool(drop_last)
@@ -242,6 +244,7 @@ class DeviceBatchLoader:
         self.host_items = False           # set once raw_item has refused the dataset (TypeError)
         self._switch = threading.Lock()
         self.host_rescale = bool(host_rescale)     # True: Pillow rescales in the decode threads (the earlier path; benchmarks)
+        self.augment = augment
 
     def epoch_order(self, epoch: int) -> List[int]:
         n = len(self.ds)
@@ -282,7 +285,8 @@ class DeviceBatchLoader:
 
     def __iter__(self):
         from concurrent.futures import ThreadPoolExecutor
-        order = self.epoch_order(self.epoch)
+        epoch = self.epoch
+        order = self.epoch_order(epoch)
         self.epoch += 1
         self.orders.append(order)
         batches = self.batches_of(order)
@@ -293,17 +297,21 @@ class DeviceBatchLoader:
 
             pending = [submit(idx) for idx in batches[:self.prefetch + 1]]
             nxt = len(pending)
+            served = 0
             while pending:
                 batch = pending.pop(0).result()
+                idx = batches[served]
+                served += 1
                 if nxt < len(batches):
                     pending.append(submit(batches[nxt]))
                     nxt += 1
                 if "image_u8" in batch:
-                    yield prepare_batch_device(batch["image_u8"], batch["mask_u8"], batch["turns"], device=dev,
+                    out = prepare_batch_device(batch["image_u8"], batch["mask_u8"], batch["turns"], device=dev,
                                                scale=batch["scale"])
                 else:
-                    yield {"image": batch["image"].to(dev, non_blocking=True, memory_format=torch.channels_last),
+                    out = {"image": batch["image"].to(dev, non_blocking=True, memory_format=torch.channels_last),
                            "mask": batch["mask"].to(dev, non_blocking=True)}
+                yield out if self.augment is None else self.augment(out, epoch, idx)
 
 
 class CarvanaDataset(BasicDataset):
