@@ -87,6 +87,20 @@ int uh_conv3x3_wfrag_ok(int B, int H, int W, int C0, int C1, int Cout, int ld0, 
  * sum in different orders: a batch gives bit-identical per-image results only where every layer gets the same answer as for
  * one image (BatchPredictor.launch_lengths).  UH_EINVAL for a bad shape or dtype. */
 int uh_conv3x3_fwd_kernel(int B, int H, int W, int C0, int C1, int Cout, int dt);
+/* The same question for backward-weights: the launch plan uh_conv3x3_wgrad (narrow = 0) or uh_conv3x3_wgrad_narrow (narrow = 1)
+ * gives a call with dense pitches (ld0 = C0, ld1 = C1, lddy = Cout) and 16-byte aligned pointers; host only.  out[0..7] (HOST
+ * memory) = { kernel, nsplit, grid.x, grid.y, threads, slab format, reduce kernel, reduce blocks }.
+ * kernel: 0 = conv3x3_wgrad_generic (no workspace, no reduction), 1 / 2 / 3 = conv3x3_wgrad_stem / _stem_v2 / _stem_v3 (at most 4
+ * input channels in one source; v3: bf16 with 64 output channels), 4 = conv3x3_wgrad_mfma (fp32, bf16x3, or bf16 with a tensor
+ * past the 2 GiB buffer window), 5 / 6 = the bf16 LDS-DMA kernel conv3x3_wgrad_mfma_v2 with 64- / 128-row output-channel tiles.
+ * nsplit = the pixel ranges, one slab of Cout * 9 * (C0 + C1) partial sums each in the workspace (0 for kernel 0).
+ * slab format: 0 = fp32, 1 = block-scaled fp16 pairs (kernels 5 and 6 unless UH_WGRAD_SLAB_F32=1).
+ * reduce kernel: 0 = none, 1 = scalar (the result is no multiple of 4 floats; in a call, also where dw_krsc or ws is off 16
+ * bytes), 2 = 16-byte pieces, 3 = many splits of a small result (uh_stem_bn_relu_bwd_wgrad only: never in this answer),
+ * 4 = fp16 pairs; reduce blocks = its workgroups, the row's block count in uh_slab_reduce_batched's table.
+ * A narrow or bf16x3 (UH_F32X3) call exists on the MFMA path only: for those the answer describes a call only where kernel >= 4,
+ * any other shape is refused by the call itself.  UH_EINVAL for a bad shape or dtype or out == NULL. */
+int uh_conv3x3_wgrad_plan(int B, int H, int W, int C0, int C1, int Cout, int dt, int narrow, int64_t* out);
 /* The pinned plan (batch-invariant eval forward).  plan_B > 0: the kernel FORM is chosen as for a launch of plan_B images of this
  * H x W, while tiles, grid, byte extents and the 2 GiB test (code 5) stay with the real B; where the launch's own form sums in the
  * same order as the pinned one (uh_conv3x3_fwd_sum_class) the launch keeps its own.  plan_B = 0: the unpinned answers above.

@@ -159,11 +159,74 @@ def _conv_case(dtype, B, H, W, C0, C1, Cout, tol_f32=2e-5):
     dwk = torch.empty(Cout * 9 * Cin, dtype=torch.float32, device=dev)
     ops.conv3x3_wgrad(dyg, x0, x1, dwk)
     dwn = dwk.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2)
+    assert rel(dwn, dwref) < _wgrad_tol(dtype), f"wgrad {rel(dwn, dwref):.3e}"
+
+
+def _wgrad_tol(dtype):
     # inputs are exact in both; fp32: only the accumulation order differs.  bf16: the per-split partial sums travel to the reduce
     # kernel as block-scaled fp16 (conv3x3_wgrad_mfma_v2<.., SLAB16>: 2^-12 per partial) and are added in fp32; the reference's
     # autocast backward rounds the TOTAL to bf16, 2^-9 = 2e-3 of each element
-    tolw = 2e-5 if dtype == torch.float32 else 1e-3
-    assert rel(dwn, dwref) < tolw, f"wgrad {rel(dwn, dwref):.3e}"
+    return 2e-5 if dtype == torch.float32 else 1e-3
+
+
+# One smallest shape per backward-weights kernel (the codes of uh_conv3x3_wgrad_plan; code 4 on bf16, a tensor past 2 GiB, is
+# test_gpu_large.py's)
+WGRAD_PLAN_CASES = [
+    pytest.param(0, torch.bfloat16, (2, 12, 14, 8, 8, 16), id="0-generic-bf16"),
+    pytest.param(0, torch.float32, (2, 12, 14, 8, 8, 16), id="0-generic-fp32"),
+    pytest.param(1, torch.float32, (2, 20, 20, 3, 0, 6), id="1-stem-fp32"),
+    pytest.param(2, torch.float32, (2, 20, 20, 3, 0, 64), id="2-stem_v2-fp32"),
+    pytest.param(3, torch.bfloat16, (3, 19, 33, 1, 0, 64), id="3-stem_v3-bf16"),
+    pytest.param(4, torch.float32, (2, 17, 23, 64, 64, 64), id="4-mfma-fp32"),
+    pytest.param(5, torch.bfloat16, (2, 17, 23, 64, 64, 64), id="5-dma64-bf16"),
+    pytest.param(6, torch.bfloat16, (1, 16, 16, 128, 0, 256), id="6-dma128-bf16"),
+]
+
+
+@pytest.mark.parametrize("code,dtype,shape", WGRAD_PLAN_CASES)
+def test_conv3x3_wgrad_takes_the_planned_kernel_and_defers_to_the_same_bits(code, dtype, shape):
+    """uh_conv3x3_wgrad_plan names the kernel; uh_conv3x3_wgrad meets the float64 gradient within _conv_case's bounds; and, where
+    the kernel leaves slabs, uh_conv3x3_wgrad_partials + uh_slab_reduce_batched give the bits of the call that reduces at once."""
+    import ctypes
+    from unet_amd import ops
+    from unet_amd._lib import LIB
+    dev = _dev()
+    B, H, W, C0, C1, Cout = shape
+    Cin = C0 + C1
+    g = torch.Generator().manual_seed(B * 1000 + H * 10 + C0 + Cout)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    dy = torch.randn(B, Cout, H, W, generator=g)
+    if dtype == torch.bfloat16:
+        x, dy = x.bfloat16().float(), dy.bfloat16().float()
+    wd = torch.zeros(Cout, Cin, 3, 3, dtype=torch.float64, requires_grad=True)
+    (dwref,) = torch.autograd.grad(F.conv2d(x.double(), wd, padding=1), [wd], dy.double())
+    x0 = _nhwc(x[:, :C0], dtype, dev)                            # dense pitches, as the query assumes
+    x1 = _nhwc(x[:, C0:], dtype, dev) if C1 else None
+    dyg = _nhwc(dy, dtype, dev)
+    dt = ops._dt(dyg)
+    plan = (ctypes.c_int64 * 8)()
+    LIB.call("uh_conv3x3_wgrad_plan", B, H, W, C0, C1, Cout, dt, 0, ctypes.addressof(plan))
+    assert plan[0] == code, list(plan)
+
+    dwk = torch.empty(Cout * 9 * Cin, dtype=torch.float32, device=dev)
+    ops.conv3x3_wgrad(dyg, x0, x1, dwk)
+    err = float((dwk.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).double().cpu() - dwref).abs().max() / dwref.abs().max())
+    assert err < _wgrad_tol(dtype), f"wgrad {err:.3e}"
+    if plan[1] == 0:
+        return                                                   # no slabs, nothing to defer
+    nbytes = LIB.query("uh_conv3x3_wgrad_ws_bytes", B, H, W, Cin, Cout, dt)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dw2 = torch.full_like(dwk, float("nan"))
+    desc = (ctypes.c_int64 * 8)()
+    LIB.call("uh_conv3x3_wgrad_partials", dyg.data_ptr(), Cout, x0.data_ptr(), C0, C0, ops._p(x1), C1, C1, dw2.data_ptr(), Cout,
+             ws.data_ptr(), nbytes, B, H, W, dt, ctypes.addressof(desc), ops._stream())
+    if desc[3]:                                                  # (a result that is no multiple of 4 floats is reduced at once)
+        assert [desc[3], desc[4], desc[6]] == [plan[1], plan[5], plan[7]], (list(desc), list(plan))
+        table = torch.tensor([[desc[0], desc[1], desc[2], desc[3], desc[4], desc[5], 0, desc[7]]], dtype=torch.int64, device=dev)
+        LIB.call("uh_slab_reduce_batched", table.data_ptr(), 1, desc[6], ops._stream())
+    else:
+        assert plan[6] == 1, list(plan)
+    assert torch.equal(dw2, dwk)
 
 
 @pytest.mark.parametrize("dtype,noise", [(torch.float32, 1e-3), (torch.bfloat16, 0.25)])

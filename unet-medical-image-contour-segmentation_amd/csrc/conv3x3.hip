@@ -2019,128 +2019,160 @@ static void fwd_v2_launch(const FwdPlan& p, hipStream_t st, Args... args) {
     }
 }
 
+// What a call of either direction carries from its entry point to its dispatch.  An entry point names the fields it sets; a
+// field left at its default keeps that family switched off.
+struct ConvCall {
+    const void *x0 = nullptr, *x1 = nullptr;                     // the sources (x1: C1 > 0)
+    int C0 = 0, ld0 = 0, C1 = 0, ld1 = 0, Cout = 0, B = 0, H = 0, W = 0;
+    int dt = UH_F32;                                             // UH_F32X3 = bf16x3 products on fp32 tensors; set by conv_check
+    bool wfrag = false;                                          // forward: the filter pack is fragment-major; set by conv_check
+    int C0v = -1, C1v = -1, Coutv = -1;                          // narrow tensors: the valid channel counts
+    const float *pre_scale = nullptr, *pre_shift = nullptr;      // PRE: BatchNorm + ReLU of the producer applied to source 0 by the loader
+    hipStream_t st = nullptr;
+};
+struct FwdCall : ConvCall {
+    const void* w = nullptr;                                     // the filter pack
+    void* y = nullptr; int ldy = 0, plan_B = 0;                  // plan_B: the pinned plan (fwd_plan)
+    float* stats = nullptr;                                      // BatchNorm statistics rows (BSUM: the partial rows)
+    const float *ep_scale = nullptr, *ep_shift = nullptr;        // inference epilogue z = max(conv * scale + shift, 0); ep_done (out):
+    bool ep_done = false;                                        // the kernel applied it, else the caller runs the separate pass
+    const void* bs_y = nullptr;                                  // BSUM (uh_conv3x3_dgrad_bnsum): what BatchNorm normalised, its pitch
+    int bs_ld = 0; const float* bs_coef = nullptr;               // and its [scale | shift | mean | rstd]
+};
+
+// The argument checks the entry points share, under the entry point's name fn.  ptrs = the direction's own pointers are set, ldo =
+// the pitch of its Cout-channel tensor.  CK_WFRAG: dt may carry UH_WFRAG (forward calls with full tensors).
+enum { CK_BF16_ONLY = 1, CK_NARROW = 2, CK_WFRAG = 4 };
+static int conv_check(const char* fn, ConvCall& c, bool ptrs, int ldo, int dt, int flags = 0) {
+    const bool narrow = (flags & CK_NARROW) != 0;
+    UH_REQUIRE(c.x0 && ptrs, "%s: null pointer", fn);
+    UH_REQUIRE(c.B > 0 && c.H > 0 && c.W > 0 && c.C0 > 0 && c.C1 >= 0 && c.Cout > 0, "%s: bad shape", fn);
+    UH_REQUIRE(!narrow || (c.C0v > 0 && c.C0v <= c.C0 && c.C1v >= 0 && c.C1v <= c.C1 && c.Coutv > 0 && c.Coutv <= c.Cout),
+               "%s: bad valid counts", fn);
+    UH_REQUIRE(c.ld0 >= (narrow ? c.C0v : c.C0) && ldo >= (narrow ? c.Coutv : c.Cout) &&
+               (c.C1 == 0 || (c.x1 && c.ld1 >= (narrow ? c.C1v : c.C1))), "%s: bad strides", fn);
+    UH_REQUIRE((int64_t)c.B * c.H * c.W < (1ll << 31), "%s: pixel count overflows int32", fn);
+    c.wfrag = (flags & CK_WFRAG) && (dt & UH_WFRAG);
+    if (flags & CK_WFRAG) dt &= ~UH_WFRAG;
+    UH_REQUIRE(!(flags & CK_BF16_ONLY) || dt == UH_BF16, "%s: bf16 only (dtype %d)", fn, dt);
+    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "%s: bad dtype %d", fn, dt);
+    const int vec = dt == UH_BF16 ? 8 : 4;
+    UH_REQUIRE(!narrow || (c.C0v % vec == 0 && c.C1v % vec == 0 && c.Coutv % vec == 0),
+               "%s: valid counts must be multiples of a 16-byte piece", fn);
+    c.dt = dt;
+    return UH_OK;
+}
+
 template <typename T>
-static int conv3x3_fwd_dispatch(const T* x0, int C0, int ld0, const T* x1, int C1, int ld1, const T* w, T* y, int ldy,
-                                int Cout, float* stats, int B, int H, int W, hipStream_t st, const float* ep_scale,
-                                const float* ep_shift, bool* ep_done, bool split = false, int C0v = -1, int C1v = -1,
-                                int Coutv = -1, bool wfrag = false, const float* pre_scale = nullptr,
-                                const float* pre_shift = nullptr, const T* bs_y = nullptr, int bs_ld = 0,
-                                const float* bs_coef = nullptr, int plan_B = 0) {
-    const bool narrow = C0v >= 0;          // narrow tensors: only the LDS-DMA MFMA kernel implements the channel masks
-    const bool pre = pre_scale != nullptr; // BatchNorm + ReLU of the producer applied to source 0 by this kernel's loader
-    const bool bsum = bs_y != nullptr;     // backward-data + the BatchNorm-backward sums of the tensor it differentiates (stats = the partial rows)
-    if (!narrow) { C0v = C0; C1v = C1; Coutv = Cout; }
-    // ep_scale/ep_shift (inference): kernels that apply them in their epilogue set *ep_done; for the others the caller
-    // runs the separate scale/shift/ReLU pass
-    *ep_done = false;
+static int conv3x3_fwd_dispatch(FwdCall& c) {
+    const T *x0 = (const T*)c.x0, *x1 = (const T*)c.x1, *w = (const T*)c.w, *bs_y = (const T*)c.bs_y;
+    T* y = (T*)c.y;
+    const float *ep_scale = c.ep_scale, *ep_shift = c.ep_shift;     // (dropped below where the epilogue cannot load them)
+    const bool split = c.dt == UH_F32X3, narrow = c.C0v >= 0, pre = c.pre_scale != nullptr, bsum = bs_y != nullptr;
+    const int C0v = narrow ? c.C0v : c.C0, C1v = narrow ? c.C1v : c.C1, Coutv = narrow ? c.Coutv : c.Cout;
+    c.ep_done = false;
     constexpr int ES = sizeof(T);
-    const int tilesX = (W + TILE - 1) / TILE, tilesY = (H + TILE - 1) / TILE;
-    const int Cin = C0 + C1;
-    const bool ptrs16 = uh_aligned16(x0) && (C1 == 0 || uh_aligned16(x1)) && uh_aligned16(w) && uh_aligned16(y);
-    const FwdPlan p = fwd_plan(ES, B, H, W, C0, C1, Cout, ld0, ld1, ldy, ptrs16, uh_aligned16(y), split, narrow, pre, bsum, plan_B);
+    const int tilesX = (c.W + TILE - 1) / TILE, tilesY = (c.H + TILE - 1) / TILE;
+    const int Cin = c.C0 + c.C1;
+    const bool ptrs16 = uh_aligned16(x0) && (c.C1 == 0 || uh_aligned16(x1)) && uh_aligned16(w) && uh_aligned16(y);
+    const FwdPlan p = fwd_plan(ES, c.B, c.H, c.W, c.C0, c.C1, c.Cout, c.ld0, c.ld1, c.ldy, ptrs16, uh_aligned16(y), split, narrow, pre, bsum, c.plan_B);
     if (p.kernel != FWD_SIMT && p.kernel != FWD_LARGE) {
         if (ep_scale && !(uh_aligned16(ep_scale) && uh_aligned16(ep_shift))) ep_scale = ep_shift = nullptr;   // 16-B loads
         UH_REQUIRE(!split || ES == 4, "conv3x3_fwd: bf16x3 needs fp32 tensors");
-        UH_REQUIRE(!(split && wfrag), "conv3x3_fwd: bf16x3 filters are KRSC packs");
-        UH_REQUIRE(!(narrow && wfrag), "conv3x3_fwd: narrow-tensor calls take KRSC packs");
+        UH_REQUIRE(!(split && c.wfrag), "conv3x3_fwd: bf16x3 filters are KRSC packs");
+        UH_REQUIRE(!(narrow && c.wfrag), "conv3x3_fwd: narrow-tensor calls take KRSC packs");
         if (pre) {
             UH_REQUIRE(UH_BUILD_PRE, "conv3x3_fwd: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
             UH_REQUIRE(ES == 2, "conv3x3_fwd: the fused BatchNorm+ReLU input is a bf16 path; ask uh_conv3x3_pre_ok first");
-            UH_REQUIRE(!(split || narrow || C0 > PRE_MAX_C), "conv3x3_fwd: the fused BatchNorm+ReLU input needs a plain bf16 call with at most %d channels in source 0; ask uh_conv3x3_pre_ok first", PRE_MAX_C);
+            UH_REQUIRE(!(split || narrow || c.C0 > PRE_MAX_C), "conv3x3_fwd: the fused BatchNorm+ReLU input needs a plain bf16 call with at most %d channels in source 0; ask uh_conv3x3_pre_ok first", PRE_MAX_C);
         }
-        const int64_t px = (int64_t)B * H * W, bq = bsum ? px * bs_ld * ES : 0;
+        const int64_t px = (int64_t)c.B * c.H * c.W, bq = bsum ? px * c.bs_ld * ES : 0;
         if (bsum) {
             UH_REQUIRE(ES == 2, "uh_conv3x3_dgrad_bnsum: bf16 only; ask uh_conv3x3_dgrad_bnsum_rows first");
-            UH_REQUIRE(!(split || narrow || C1 != 0 || !stats || !bs_coef || bs_ld != ldy || !uh_aligned16(bs_y) || bq >= (1ll << 31) - 4096),
+            UH_REQUIRE(!(split || narrow || c.C1 != 0 || !c.stats || !c.bs_coef || c.bs_ld != c.ldy || !uh_aligned16(bs_y) || bq >= (1ll << 31) - 4096),
                        "uh_conv3x3_dgrad_bnsum: needs a plain single-source bf16 call and a 16-byte aligned BatchNorm input below 2 GiB; ask uh_conv3x3_dgrad_bnsum_rows first");
         }
         // byte extents of x0, x1, y and q for the buffer descriptors (below 2 GiB: fwd_plan)
-        fwd_v2_launch<T>(p, st, x0, C0, ld0, x1, C1, ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY, (unsigned)(px * ld0 * ES),
-                         (unsigned)(C1 ? px * ld1 * ES : 0), (unsigned)(px * ldy * ES), ep_scale, ep_shift, C0v, C1v, Coutv,
-                         wfrag ? 1 : 0, pre_scale, pre_shift, bs_y, bs_ld, (unsigned)bq, bs_coef);
+        fwd_v2_launch<T>(p, c.st, x0, c.C0, c.ld0, x1, c.C1, c.ld1, w, y, c.ldy, c.Cout, c.stats, c.B, c.H, c.W, tilesX, tilesY, (unsigned)(px * c.ld0 * ES),
+                         (unsigned)(c.C1 ? px * c.ld1 * ES : 0), (unsigned)(px * c.ldy * ES), ep_scale, ep_shift, C0v, C1v, Coutv,
+                         c.wfrag ? 1 : 0, c.pre_scale, c.pre_shift, bs_y, c.bs_ld, (unsigned)bq, c.bs_coef);
         UH_CHECK_LAUNCH(pre ? "conv3x3_fwd_mfma_v2 (BatchNorm+ReLU input)"
                             : bsum ? "conv3x3_fwd_mfma_v2 (backward-data + BatchNorm sums)" : "conv3x3_fwd_mfma_v2");
-        *ep_done = ep_scale != nullptr;
+        c.ep_done = ep_scale != nullptr;
         return UH_OK;
     }
     if (p.kernel == FWD_LARGE) {
         UH_REQUIRE(!pre, "conv3x3_fwd: the fused BatchNorm+ReLU input needs the LDS-DMA MFMA kernel (tensors below 2 GiB); ask uh_conv3x3_pre_ok first");
         UH_REQUIRE(!bsum, "uh_conv3x3_dgrad_bnsum: needs the LDS-DMA MFMA kernel (tensors below 2 GiB); ask uh_conv3x3_dgrad_bnsum_rows first");
-        UH_REQUIRE(!wfrag, "conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but this call cannot take the LDS-DMA MFMA kernel (a tensor of 2 GiB or more); ask uh_conv3x3_wfrag_ok first");
+        UH_REQUIRE(!c.wfrag, "conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but this call cannot take the LDS-DMA MFMA kernel (a tensor of 2 GiB or more); ask uh_conv3x3_wfrag_ok first");
         UH_REQUIRE(!split, "conv3x3_fwd: bf16x3 is implemented for tensors below 2 GiB only");
         UH_REQUIRE(!narrow, "conv3x3_fwd: narrow tensors are implemented for tensors below 2 GiB only");
-        if (Cout % 128 == 0)
-            hipLaunchKernelGGL((conv3x3_fwd_mfma<T, 4>), dim3(p.lanes, p.slabs), dim3(p.threads), 0, st, x0, C0, ld0, x1, C1,
-                               ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY);
+        if (c.Cout % 128 == 0)
+            hipLaunchKernelGGL((conv3x3_fwd_mfma<T, 4>), dim3(p.lanes, p.slabs), dim3(p.threads), 0, c.st, x0, c.C0, c.ld0, x1, c.C1,
+                               c.ld1, w, y, c.ldy, c.Cout, c.stats, c.B, c.H, c.W, tilesX, tilesY);
         else
-            hipLaunchKernelGGL((conv3x3_fwd_mfma<T, 2>), dim3(p.lanes, p.slabs), dim3(p.threads), 0, st, x0, C0, ld0, x1, C1,
-                               ld1, w, y, ldy, Cout, stats, B, H, W, tilesX, tilesY);
+            hipLaunchKernelGGL((conv3x3_fwd_mfma<T, 2>), dim3(p.lanes, p.slabs), dim3(p.threads), 0, c.st, x0, c.C0, c.ld0, x1, c.C1,
+                               c.ld1, w, y, c.ldy, c.Cout, c.stats, c.B, c.H, c.W, tilesX, tilesY);
         UH_CHECK_LAUNCH("conv3x3_fwd_mfma");
         return UH_OK;
     }
     UH_REQUIRE(!pre, "conv3x3_fwd: the fused BatchNorm+ReLU input needs an MFMA-aligned shape; ask uh_conv3x3_pre_ok first");
     UH_REQUIRE(!bsum, "uh_conv3x3_dgrad_bnsum: needs an MFMA-aligned shape; ask uh_conv3x3_dgrad_bnsum_rows first");
-    UH_REQUIRE(!wfrag, "conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but the shape / alignment is outside the MFMA path; ask uh_conv3x3_wfrag_ok first");
+    UH_REQUIRE(!c.wfrag, "conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but the shape / alignment is outside the MFMA path; ask uh_conv3x3_wfrag_ok first");
     UH_REQUIRE(!split, "conv3x3_fwd: bf16x3 needs an MFMA-aligned shape (Cin %% 16 == 0, Cout %% 64 == 0, 16-byte strides)");
     UH_REQUIRE(!narrow, "conv3x3_fwd: narrow tensors need padded counts that are MFMA-aligned and 16-byte strides");
     if (p.stem == 3) {
         if constexpr (ES == 2) {
             switch (Cin) {
-                case 1: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 1>), dim3(p.lanes), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
-                case 2: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 2>), dim3(p.lanes), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
-                case 3: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 3>), dim3(p.lanes), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
-                default: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 4>), dim3(p.lanes), dim3(256), 0, st, x0, ld0, w, y, ldy, stats, B, H, W, tilesX, tilesY, ep_scale, ep_shift); break;
+                case 1: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 1>), dim3(p.lanes), dim3(256), 0, c.st, x0, c.ld0, w, y, c.ldy, c.stats, c.B, c.H, c.W, tilesX, tilesY, ep_scale, ep_shift); break;
+                case 2: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 2>), dim3(p.lanes), dim3(256), 0, c.st, x0, c.ld0, w, y, c.ldy, c.stats, c.B, c.H, c.W, tilesX, tilesY, ep_scale, ep_shift); break;
+                case 3: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 3>), dim3(p.lanes), dim3(256), 0, c.st, x0, c.ld0, w, y, c.ldy, c.stats, c.B, c.H, c.W, tilesX, tilesY, ep_scale, ep_shift); break;
+                default: hipLaunchKernelGGL((conv3x3_fwd_stem_v3<T, 4>), dim3(p.lanes), dim3(256), 0, c.st, x0, c.ld0, w, y, c.ldy, c.stats, c.B, c.H, c.W, tilesX, tilesY, ep_scale, ep_shift); break;
             }
             UH_CHECK_LAUNCH("conv3x3_fwd_stem_v3");
-            *ep_done = ep_scale != nullptr;
+            c.ep_done = ep_scale != nullptr;
         }
         return UH_OK;
     }
     if (p.stem == 2) {
         constexpr int V = 16 / ES;
-        int G = Cout / V, GB = G < 8 ? G : 8, CG = GB * V;
+        int G = c.Cout / V, GB = G < 8 ? G : 8, CG = GB * V;
         size_t sm = (size_t)(HALO_PIX * 4 + 36 * CG + CG + 256 * V) * sizeof(float);
-        hipLaunchKernelGGL(conv3x3_fwd_stem_v2<T>, dim3(p.lanes), dim3(256), sm, st, x0, Cin, ld0, w, y, ldy, Cout, stats,
-                           B, H, W, tilesX, tilesY);
+        hipLaunchKernelGGL(conv3x3_fwd_stem_v2<T>, dim3(p.lanes), dim3(256), sm, c.st, x0, Cin, c.ld0, w, y, c.ldy, c.Cout, c.stats,
+                           c.B, c.H, c.W, tilesX, tilesY);
         UH_CHECK_LAUNCH("conv3x3_fwd_stem_v2");
         return UH_OK;
     }
     if (p.stem == 1) {
-        hipLaunchKernelGGL(conv3x3_fwd_stem<T>, dim3(p.lanes), dim3(256), 0, st, x0, Cin, ld0, w, y, ldy, Cout, stats, B, H,
-                           W, tilesX, tilesY);
+        hipLaunchKernelGGL(conv3x3_fwd_stem<T>, dim3(p.lanes), dim3(256), 0, c.st, x0, Cin, c.ld0, w, y, c.ldy, c.Cout, c.stats, c.B, c.H,
+                           c.W, tilesX, tilesY);
         UH_CHECK_LAUNCH("conv3x3_fwd_stem");
         return UH_OK;
     }
-    int64_t total = (int64_t)B * H * W * Cout;
-    hipLaunchKernelGGL(conv3x3_fwd_generic<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x0, C0, ld0, x1,
-                       C1, ld1, w, y, ldy, Cout, B, H, W);
+    int64_t total = (int64_t)c.B * c.H * c.W * c.Cout;
+    hipLaunchKernelGGL(conv3x3_fwd_generic<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.st, x0, c.C0, c.ld0, x1,
+                       c.C1, c.ld1, w, y, c.ldy, c.Cout, c.B, c.H, c.W);
     UH_CHECK_LAUNCH("conv3x3_fwd_generic");
-    if (stats) {
-        hipLaunchKernelGGL(tile_stats_kernel<T>, dim3(p.lanes), dim3(256), 0, st, (const T*)y, ldy, Cout, stats, B, H, W,
+    if (c.stats) {
+        hipLaunchKernelGGL(tile_stats_kernel<T>, dim3(p.lanes), dim3(256), 0, c.st, (const T*)y, c.ldy, c.Cout, c.stats, c.B, c.H, c.W,
                            tilesX, tilesY);
         UH_CHECK_LAUNCH("tile_stats_kernel");
     }
     return UH_OK;
 }
 
+// The shared argument checks, then the dispatch in the element type the dtype names.
+static int conv3x3_fwd_call(const char* fn, FwdCall& c, int dt, int flags = CK_WFRAG) {
+    if (const int rc = conv_check(fn, c, c.w && c.y, c.ldy, dt, flags)) return rc;
+    return c.dt == UH_BF16 ? conv3x3_fwd_dispatch<bf16_t>(c) : conv3x3_fwd_dispatch<float>(c);
+}
+
 extern "C" int uh_conv3x3_fwd(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1, const void* w, void* y,
                               int ldy, int Cout, float* stat_partials, int B, int H, int W, int dt, uh_stream stream) {
-    UH_REQUIRE(x0 && w && y, "uh_conv3x3_fwd: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd: bad shape");
-    UH_REQUIRE(ld0 >= C0 && ldy >= Cout && (C1 == 0 || (x1 && ld1 >= C1)), "uh_conv3x3_fwd: bad strides");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_fwd: pixel count overflows int32");
-    const bool wfrag = (dt & UH_WFRAG) != 0;          // the filter pack is fragment-major (uh_pack_w3x3 with the same flag)
-    dt &= ~UH_WFRAG;
-    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_fwd: bad dtype %d", dt);
-    hipStream_t st = (hipStream_t)stream;
-    bool done;
-    if (dt == UH_BF16)
-        return conv3x3_fwd_dispatch<bf16_t>((const bf16_t*)x0, C0, ld0, (const bf16_t*)x1, C1, ld1, (const bf16_t*)w,
-                                            (bf16_t*)y, ldy, Cout, stat_partials, B, H, W, st, nullptr, nullptr, &done, false,
-                                            -1, -1, -1, wfrag);
-    return conv3x3_fwd_dispatch<float>((const float*)x0, C0, ld0, (const float*)x1, C1, ld1, (const float*)w, (float*)y,
-                                       ldy, Cout, stat_partials, B, H, W, st, nullptr, nullptr, &done, dt == UH_F32X3, -1, -1,
-                                       -1, wfrag);
+    FwdCall c;
+    c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.x1 = x1; c.C1 = C1; c.ld1 = ld1; c.w = w; c.y = y; c.ldy = ldy; c.Cout = Cout;
+    c.stats = stat_partials; c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream;
+    return conv3x3_fwd_call("uh_conv3x3_fwd", c, dt);
 }
 
 // Will uh_conv3x3_fwd take the LDS-DMA MFMA kernel for this call (pointers assumed 16-byte aligned)?  Only then may the
@@ -2198,19 +2230,14 @@ extern "C" int uh_conv3x3_pre_ok(int B, int H, int W, int C0, int Cout, int ld0,
 extern "C" int uh_conv3x3_fwd_pre(const void* x0, int C0, int ld0, const float* pre_scale, const float* pre_shift, const void* w,
                                   void* y, int ldy, int Cout, float* stat_partials, int B, int H, int W, int dt,
                                   uh_stream stream) {
-    UH_REQUIRE(x0 && w && y && pre_scale && pre_shift, "uh_conv3x3_fwd_pre: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && Cout > 0, "uh_conv3x3_fwd_pre: bad shape");
-    UH_REQUIRE(ld0 >= C0 && ldy >= Cout, "uh_conv3x3_fwd_pre: bad strides");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_fwd_pre: pixel count overflows int32");
-    const bool wfrag = (dt & UH_WFRAG) != 0;
-    dt &= ~UH_WFRAG;
-    UH_REQUIRE(dt == UH_BF16, "uh_conv3x3_fwd_pre: bf16 only (dtype %d)", dt);
+    UH_REQUIRE(pre_scale && pre_shift, "uh_conv3x3_fwd_pre: null pointer");
+    FwdCall c;
+    c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.w = w; c.y = y; c.ldy = ldy; c.Cout = Cout; c.stats = stat_partials;
+    c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream; c.pre_scale = pre_scale; c.pre_shift = pre_shift;
+    if (const int rc = conv_check("uh_conv3x3_fwd_pre", c, c.w && c.y, c.ldy, dt, CK_BF16_ONLY | CK_WFRAG)) return rc;
     UH_REQUIRE(UH_BUILD_PRE, "uh_conv3x3_fwd_pre: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
-    UH_REQUIRE(uh_conv3x3_pre_ok(B, H, W, C0, Cout, ld0, ldy, dt), "uh_conv3x3_fwd_pre: shape outside the fused path (uh_conv3x3_pre_ok)");
-    bool done;
-    return conv3x3_fwd_dispatch<bf16_t>((const bf16_t*)x0, C0, ld0, nullptr, 0, 0, (const bf16_t*)w, (bf16_t*)y, ldy, Cout,
-                                        stat_partials, B, H, W, (hipStream_t)stream, nullptr, nullptr, &done, false, -1, -1, -1,
-                                        wfrag, pre_scale, pre_shift);
+    UH_REQUIRE(uh_conv3x3_pre_ok(B, H, W, C0, Cout, ld0, ldy, c.dt), "uh_conv3x3_fwd_pre: shape outside the fused path (uh_conv3x3_pre_ok)");
+    return conv3x3_fwd_dispatch<bf16_t>(c);
 }
 
 // Backward-data of the second conv of a DoubleConv together with the first half of the BatchNorm backward of the layer in
@@ -2228,21 +2255,17 @@ extern "C" int uh_conv3x3_dgrad_bnsum_rows(int B, int H, int W, int Cdy, int Cdx
 extern "C" int uh_conv3x3_dgrad_bnsum(const void* dy, int Cdy, int lddy, const void* w_dgrad, void* dx, int lddx, int Cdx,
                                       const void* q, int ldq, const float* coef, float* partials, int B, int H, int W, int dt,
                                       uh_stream stream) {
-    UH_REQUIRE(dy && w_dgrad && dx && q && coef && partials, "uh_conv3x3_dgrad_bnsum: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && Cdy > 0 && Cdx > 0, "uh_conv3x3_dgrad_bnsum: bad shape");
-    UH_REQUIRE(lddy >= Cdy && lddx >= Cdx && ldq >= Cdx, "uh_conv3x3_dgrad_bnsum: bad strides");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_dgrad_bnsum: pixel count overflows int32");
-    const bool wfrag = (dt & UH_WFRAG) != 0;
-    dt &= ~UH_WFRAG;
-    UH_REQUIRE(dt == UH_BF16, "uh_conv3x3_dgrad_bnsum: bf16 only (dtype %d)", dt);
+    UH_REQUIRE(q && coef && partials, "uh_conv3x3_dgrad_bnsum: null pointer");
+    FwdCall c;
+    c.x0 = dy; c.C0 = Cdy; c.ld0 = lddy; c.w = w_dgrad; c.y = dx; c.ldy = lddx; c.Cout = Cdx; c.stats = partials;
+    c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream; c.bs_y = q; c.bs_ld = ldq; c.bs_coef = coef;
+    if (const int rc = conv_check("uh_conv3x3_dgrad_bnsum", c, c.w && c.y, c.ldy, dt, CK_BF16_ONLY | CK_WFRAG)) return rc;
+    UH_REQUIRE(ldq >= Cdx, "uh_conv3x3_dgrad_bnsum: bad strides");
     UH_REQUIRE(uh_aligned16(dy) && uh_aligned16(w_dgrad) && uh_aligned16(dx) && uh_aligned16(q) && uh_aligned16(coef),
                "uh_conv3x3_dgrad_bnsum: pointers must be 16-byte aligned");
-    UH_REQUIRE(uh_conv3x3_dgrad_bnsum_rows(B, H, W, Cdy, Cdx, lddy, lddx, ldq, dt) > 0,
+    UH_REQUIRE(uh_conv3x3_dgrad_bnsum_rows(B, H, W, Cdy, Cdx, lddy, lddx, ldq, c.dt) > 0,
                "uh_conv3x3_dgrad_bnsum: shape outside the fused path (uh_conv3x3_dgrad_bnsum_rows)");
-    bool done;
-    return conv3x3_fwd_dispatch<bf16_t>((const bf16_t*)dy, Cdy, lddy, nullptr, 0, 0, (const bf16_t*)w_dgrad, (bf16_t*)dx, lddx, Cdx,
-                                        partials, B, H, W, (hipStream_t)stream, nullptr, nullptr, &done, false, -1, -1, -1, wfrag,
-                                        nullptr, nullptr, (const bf16_t*)q, ldq, coef);
+    return conv3x3_fwd_dispatch<bf16_t>(c);
 }
 
 // Inference forward: z = max(conv(x, w) * scale + shift, 0) with the eval-mode BatchNorm coefficients of
@@ -2254,26 +2277,13 @@ extern "C" int uh_conv3x3_fwd_affine_relu_plan(const void* x0, int C0, int ld0, 
                                                void* z, int ldz, int Cout, const float* scale, const float* shift, int B,
                                                int plan_B, int H, int W, int dt, uh_stream stream) {
     UH_REQUIRE(plan_B >= 0, "uh_conv3x3_fwd_affine_relu: bad plan length %d", plan_B);
-    UH_REQUIRE(x0 && w && z && scale && shift, "uh_conv3x3_fwd_affine_relu: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd_affine_relu: bad shape");
-    UH_REQUIRE(ld0 >= C0 && ldz >= Cout && (C1 == 0 || (x1 && ld1 >= C1)), "uh_conv3x3_fwd_affine_relu: bad strides");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_fwd_affine_relu: pixel count overflows int32");
-    const bool wfrag = (dt & UH_WFRAG) != 0;
-    dt &= ~UH_WFRAG;
-    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_fwd_affine_relu: bad dtype %d", dt);
-    hipStream_t st = (hipStream_t)stream;
-    bool done = false;
-    int rc;
-    if (dt == UH_BF16)
-        rc = conv3x3_fwd_dispatch<bf16_t>((const bf16_t*)x0, C0, ld0, (const bf16_t*)x1, C1, ld1, (const bf16_t*)w,
-                                          (bf16_t*)z, ldz, Cout, nullptr, B, H, W, st, scale, shift, &done, false, -1, -1, -1, wfrag,
-                                          nullptr, nullptr, nullptr, 0, nullptr, plan_B);
-    else
-        rc = conv3x3_fwd_dispatch<float>((const float*)x0, C0, ld0, (const float*)x1, C1, ld1, (const float*)w, (float*)z,
-                                         ldz, Cout, nullptr, B, H, W, st, scale, shift, &done, dt == UH_F32X3, -1, -1, -1, wfrag,
-                                         nullptr, nullptr, nullptr, 0, nullptr, plan_B);
-    if (rc != UH_OK || done) return rc;
-    return uh_bn_relu_apply(z, ldz, scale, shift, z, ldz, (int64_t)B * H * W, Cout, dt == UH_BF16 ? UH_BF16 : UH_F32, stream);
+    UH_REQUIRE(scale && shift, "uh_conv3x3_fwd_affine_relu: null pointer");
+    FwdCall c;
+    c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.x1 = x1; c.C1 = C1; c.ld1 = ld1; c.w = w; c.y = z; c.ldy = ldz; c.Cout = Cout;
+    c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream; c.ep_scale = scale; c.ep_shift = shift; c.plan_B = plan_B;
+    const int rc = conv3x3_fwd_call("uh_conv3x3_fwd_affine_relu", c, dt);
+    if (rc != UH_OK || c.ep_done) return rc;
+    return uh_bn_relu_apply(z, ldz, scale, shift, z, ldz, (int64_t)B * H * W, Cout, c.dt == UH_BF16 ? UH_BF16 : UH_F32, stream);
 }
 
 extern "C" int uh_conv3x3_fwd_affine_relu(const void* x0, int C0, int ld0, const void* x1, int C1, int ld1, const void* w,
@@ -2293,27 +2303,13 @@ extern "C" int uh_conv3x3_fwd_narrow_plan(const void* x0, int C0, int C0v, int l
                                           const float* scale, const float* shift, int B, int plan_B, int H, int W, int dt,
                                           uh_stream stream) {
     UH_REQUIRE(plan_B >= 0, "uh_conv3x3_fwd_narrow: bad plan length %d", plan_B);
-    UH_REQUIRE(x0 && w && y, "uh_conv3x3_fwd_narrow: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd_narrow: bad shape");
-    UH_REQUIRE(C0v > 0 && C0v <= C0 && C1v >= 0 && C1v <= C1 && Coutv > 0 && Coutv <= Cout, "uh_conv3x3_fwd_narrow: bad valid counts");
-    UH_REQUIRE(ld0 >= C0v && ldy >= Coutv && (C1 == 0 || (x1 && ld1 >= C1v)), "uh_conv3x3_fwd_narrow: bad strides");
     UH_REQUIRE((scale == nullptr) == (shift == nullptr), "uh_conv3x3_fwd_narrow: scale and shift come together");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_fwd_narrow: pixel count overflows int32");
-    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_fwd_narrow: bad dtype %d", dt);
-    const int vec = dt == UH_BF16 ? 8 : 4;
-    UH_REQUIRE(C0v % vec == 0 && C1v % vec == 0 && Coutv % vec == 0, "uh_conv3x3_fwd_narrow: valid counts must be multiples of a 16-byte piece");
-    hipStream_t st = (hipStream_t)stream;
-    bool done = false;
-    int rc;
-    if (dt == UH_BF16)
-        rc = conv3x3_fwd_dispatch<bf16_t>((const bf16_t*)x0, C0, ld0, (const bf16_t*)x1, C1, ld1, (const bf16_t*)w, (bf16_t*)y,
-                                          ldy, Cout, stat_partials, B, H, W, st, scale, shift, &done, false, C0v, C1v, Coutv,
-                                          false, nullptr, nullptr, nullptr, 0, nullptr, plan_B);
-    else
-        rc = conv3x3_fwd_dispatch<float>((const float*)x0, C0, ld0, (const float*)x1, C1, ld1, (const float*)w, (float*)y, ldy,
-                                         Cout, stat_partials, B, H, W, st, scale, shift, &done, dt == UH_F32X3, C0v, C1v, Coutv,
-                                         false, nullptr, nullptr, nullptr, 0, nullptr, plan_B);
-    if (rc != UH_OK || !scale || done) return rc;
+    FwdCall c;
+    c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.x1 = x1; c.C1 = C1; c.ld1 = ld1; c.w = w; c.y = y; c.ldy = ldy; c.Cout = Cout;
+    c.stats = stat_partials; c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream; c.ep_scale = scale; c.ep_shift = shift;
+    c.C0v = C0v; c.C1v = C1v; c.Coutv = Coutv; c.plan_B = plan_B;
+    const int rc = conv3x3_fwd_call("uh_conv3x3_fwd_narrow", c, dt, CK_NARROW);
+    if (rc != UH_OK || !scale || c.ep_done) return rc;
     return uh_bn_relu_apply(y, ldy, scale, shift, y, ldy, (int64_t)B * H * W, Coutv, dt == UH_BF16 ? UH_BF16 : UH_F32, stream);
 }
 
@@ -3473,201 +3469,229 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_generic(const T* __restrict
 // =====================================================================================
 // host dispatch: wgrad
 // =====================================================================================
-struct WgradPlan { int kind; int nsplit; int tilesX, tilesY, ntile; int nwr; };   // kind 0 = mfma, 1 = stem, 2 = generic
+// The kernel a backward-weights call takes; the values are what uh_conv3x3_wgrad_plan answers.
+enum WgradKernel {
+    WG_GENERIC = 0,      // conv3x3_wgrad_generic: no workspace, no reduce
+    WG_STEM = 1,         // conv3x3_wgrad_stem
+    WG_STEM_V2 = 2,      // conv3x3_wgrad_stem_v2
+    WG_STEM_V3 = 3,      // conv3x3_wgrad_stem_v3 (bf16, Cout == 64: 72 accumulators per lane)
+    WG_MFMA = 4,         // conv3x3_wgrad_mfma: fp32, bf16x3, or bf16 past a buffer descriptor's 2 GiB
+    WG_DMA64 = 5,        // conv3x3_wgrad_mfma_v2, NWR = 2
+    WG_DMA128 = 6,       // conv3x3_wgrad_mfma_v2, NWR = 4
+};
 
-// wide = the bf16 LDS-DMA kernel with 128-row output-channel tiles (8 waves, one workgroup per CU) may be used
-template <typename T>
-static WgradPlan wgrad_plan(int B, int H, int W, int Cin, int Cout, bool aligned, bool wide) {
-    constexpr int TH = WgradCfg<T>::TH;
-    WgradPlan p;
-    p.nwr = 2;
-    if (aligned && Cin % 64 == 0 && Cout % 64 == 0) {
-        p.kind = 0;
-        p.tilesX = (W + TILE - 1) / TILE; p.tilesY = (H + TH - 1) / TH;
-        p.ntile = B * p.tilesX * p.tilesY;
-        if (wide && sizeof(T) == 2 && Cout % 128 == 0) p.nwr = 4;
-        int ctiles = (Cin / 64) * (Cout / (32 * p.nwr));
-        int total = p.nwr == 4 ? 256 : 512;           // one 8-wave / two 4-wave workgroups per CU in flight (LDS)
-        int want = (total + ctiles - 1) / ctiles;
-        p.nsplit = want < 1 ? 1 : (want > p.ntile ? p.ntile : want);
-    } else if (Cin <= 4) {
-        p.kind = 1;
+// The closing reduction over the pixel splits, dw[n] = the sum of nsplit slabs, in the one form both of its consumers take:
+// slab_reduce_launch runs it now, conv3x3_wgrad_dispatch writes it down as a row of uh_slab_reduce_batched's table.
+enum SlabReduceKernel { SR_NONE = 0, SR_SCALAR = 1, SR_VEC = 2, SR_TALL = 3, SR_F16PAIR = 4 };
+struct SlabReduce {
+    SlabReduceKernel kernel;
+    int64_t n, blocks;         // floats of the result; workgroups of the launch
+    int nsplit, row, coblk;    // row = 9 * Cin floats of a filter row; fp16 pairs: coblk filter rows per scale block (the writer's tile)
+};
+
+// vec16 = dw and the slabs are 16-byte aligned.  tall = the caller takes slab_reduce_tall_kernel where it fits: only
+// uh_stem_bn_relu_bwd_wgrad does.  The kernels add the splits in different orders, so a caller keeps the choice it was tested with.
+static SlabReduce slab_reduce_plan(int64_t n, int nsplit, int row, int coblk, bool f16pair, bool vec16, bool tall) {
+    SlabReduce r = {SR_SCALAR, n, (n + 255) / 256, nsplit, row, coblk};        // n % 4 != 0 or a pointer off 16 bytes
+    if (f16pair) { r.kernel = SR_F16PAIR; r.blocks = uh_slab16_blocks(n / 2, nsplit); }
+    else if (n % 4 == 0 && vec16 && tall && n <= 4096 && nsplit >= 256) { r.kernel = SR_TALL; r.blocks = (n / 4 + 3) / 4; }
+    else if (n % 4 == 0 && vec16) { r.kernel = SR_VEC; r.blocks = (n / 4 + 63) / 64; }
+    return r;
+}
+
+static int slab_reduce_launch(const SlabReduce& r, const void* slabs, float* dw, hipStream_t st) {
+    const dim3 grid((unsigned)r.blocks), block(256);
+    if (r.kernel == SR_F16PAIR)
+        hipLaunchKernelGGL(slab_reduce_f16pair_kernel, grid, block, 0, st, (const unsigned*)slabs, dw, r.n / 2, r.row, r.nsplit, r.coblk);
+    else if (r.kernel != SR_NONE)
+        hipLaunchKernelGGL(r.kernel == SR_SCALAR ? slab_reduce_scalar_kernel : r.kernel == SR_TALL ? slab_reduce_tall_kernel : slab_reduce_kernel,
+                           grid, block, 0, st, (const float*)slabs, dw, r.n, r.nsplit);
+    UH_CHECK_LAUNCH(r.kernel == SR_F16PAIR ? "slab_reduce_f16pair_kernel" : "slab_reduce_kernel");
+    return UH_OK;
+}
+
+struct WgradPlan {
+    WgradKernel kernel;
+    int tilesX, tilesY;           // pixel tiles: 16 wide x 8 tall on the MFMA path, 16 x 16 for the stem kernels
+    int nsplit;                   // pixel ranges, one slab of Cout * 9 * Cin partial sums each
+    dim3 grid;
+    int threads;                  // workgroup size
+    bool slab16, pre;             // the slabs are block-scaled fp16 pairs (see SLAB16), else fp32; the call has a BatchNorm+ReLU input
+    SlabReduce reduce;
+};
+struct WgradAlign { bool ptrs, dy, dw, ws; };      // 16-byte aligned: dy, x0 and x1 together; dy; the result; the workspace
+static const WgradAlign WG_ALIGNED = {true, true, true, true};
+static size_t wgrad_slab_bytes(const WgradPlan& p) { return (size_t)p.nsplit * p.reduce.n * sizeof(float); }
+
+// The one place that decides which kernel a backward-weights call gets, its grid, its slabs and their reduction: every entry
+// point below and the queries uh_conv3x3_wgrad_plan and uh_conv3x3_wgrad_ws_bytes take it from here.  es = element size.  Of the
+// families only `narrow` decides anything: a narrow call keeps the 64-row tile.
+static WgradPlan wgrad_plan(int es, int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int lddy, WgradAlign a16,
+                            bool narrow, bool pre) {
+    static const bool slab_f32 = getenv("UH_WGRAD_SLAB_F32") != nullptr && getenv("UH_WGRAD_SLAB_F32")[0] == '1';
+    static_assert(WgradCfg<bf16_t>::TH == WgradCfg<float>::TH, "one pixel-tile height for both element types");
+    const int Cin = C0 + C1;
+    const int64_t n = (int64_t)Cout * 9 * Cin;
+    WgradPlan p = {WG_GENERIC, 0, 0, 0, dim3(Cout * 9), 256, false, pre, {SR_NONE, n, 0, 0, 9 * Cin, 0}};
+    const bool dy_ok = a16.dy && (lddy * es) % 16 == 0;
+    int nwr = 2;
+    if (a16.ptrs && dy_ok && (ld0 * es) % 16 == 0 && (C1 == 0 || (ld1 * es) % 16 == 0) && C0 % 64 == 0 && Cin % 64 == 0 && Cout % 64 == 0) {
+        p.tilesX = (W + TILE - 1) / TILE; p.tilesY = (H + WgradCfg<float>::TH - 1) / WgradCfg<float>::TH;
+        const int ntile = B * p.tilesX * p.tilesY;
+        // the bf16 LDS-DMA kernel (and with it the 128-row tile) needs every tensor addressable through a buffer descriptor
+        const int64_t px = (int64_t)B * H * W, lim = (1ll << 31) - 4096;
+        const bool dma = es == 2 && px * (ld0 > ld1 ? ld0 : ld1) * 2 < lim && px * lddy * 2 < lim;
+        if (dma && !narrow && Cout % 128 == 0) nwr = 4;
+        p.kernel = !dma ? WG_MFMA : nwr == 4 ? WG_DMA128 : WG_DMA64;
+        const int ctiles = (Cin / 64) * (Cout / (32 * nwr));
+        const int want = ((nwr == 4 ? 256 : 512) + ctiles - 1) / ctiles;      // one 8-wave / two 4-wave workgroups per CU in flight (LDS)
+        p.nsplit = want < 1 ? 1 : (want > ntile ? ntile : want);
+        p.grid = dim3(p.nsplit, ctiles); p.threads = 128 * nwr;
+        // block-scaled fp16-pair slabs: the LDS-DMA kernel's default; the inverse scales follow the slabs in the workspace
+        // (nsplit * n * 2 + nsplit * blocks * 4 bytes <= the nsplit * n * 4 the workspace is sized for)
+        p.slab16 = dma && a16.dw && !slab_f32;
+    } else if (Cin <= 4 && C1 == 0) {
         p.tilesX = (W + TILE - 1) / TILE; p.tilesY = (H + TILE - 1) / TILE;
-        p.ntile = B * p.tilesX * p.tilesY;
-        int want = 1024;
-        p.nsplit = want > p.ntile ? p.ntile : want;
-    } else {
-        p.kind = 2; p.nsplit = 0; p.tilesX = p.tilesY = p.ntile = 0;
-    }
+        const int ntile = B * p.tilesX * p.tilesY;
+        p.nsplit = 1024 > ntile ? ntile : 1024;
+        if (es == 2 && Cout == 64 && dy_ok) { p.kernel = WG_STEM_V3; p.grid = dim3(p.nsplit, Cin); }
+        else if (Cout % (16 / es) == 0 && dy_ok) { p.kernel = WG_STEM_V2; p.grid = dim3(p.nsplit, 1, Cin); }
+        else { p.kernel = WG_STEM; p.grid = dim3(p.nsplit, (Cout + 63) / 64); }
+    } else
+        return p;
+    p.reduce = slab_reduce_plan(n, p.nsplit, 9 * Cin, 32 * nwr, p.slab16, a16.dw && a16.ws, false);
     return p;
 }
 
 extern "C" size_t uh_conv3x3_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int dt) {
-    // alignment is unknown here: size for the slab paths (the generic path needs no workspace)
-    WgradPlan p = (dt == UH_BF16) ? wgrad_plan<bf16_t>(B, H, W, Cin, Cout, true, false) : wgrad_plan<float>(B, H, W, Cin, Cout, true, false);
-    if (p.kind == 2) return 16;
-    size_t n = (size_t)p.nsplit * Cout * 9 * Cin * sizeof(float) + 16;
-    if (dt == UH_BF16) {      // the wide-tile plan of the LDS-DMA kernel may use a different split count: the larger of the two
-        WgradPlan q = wgrad_plan<bf16_t>(B, H, W, Cin, Cout, true, true);
-        size_t m = (size_t)q.nsplit * Cout * 9 * Cin * sizeof(float) + 16;
-        if (m > n) n = m;
-    }
-    return n;
+    // alignment and the family are unknown here: dense pitches, everything aligned, the larger of the 128- and 64-row tile plans
+    const int es = dt == UH_BF16 ? 2 : 4;
+    const size_t wide = wgrad_slab_bytes(wgrad_plan(es, B, H, W, Cin, 0, Cout, Cin, 0, Cout, WG_ALIGNED, false, false));
+    const size_t narrow = wgrad_slab_bytes(wgrad_plan(es, B, H, W, Cin, 0, Cout, Cin, 0, Cout, WG_ALIGNED, true, false));
+    return (wide > narrow ? wide : narrow) + 16;
 }
 
+extern "C" int uh_conv3x3_wgrad_plan(int B, int H, int W, int C0, int C1, int Cout, int dt, int narrow, int64_t* out) {
+    UH_REQUIRE(out && B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_wgrad_plan: null pointer or bad shape");
+    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_wgrad_plan: bad dtype %d", dt);
+    const WgradPlan p = wgrad_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, WG_ALIGNED, narrow != 0, false);
+    out[0] = p.kernel; out[1] = p.nsplit; out[2] = p.grid.x; out[3] = p.grid.y; out[4] = p.threads; out[5] = p.slab16 ? 1 : 0;
+    out[6] = p.reduce.kernel; out[7] = p.reduce.blocks;
+    return UH_OK;
+}
+
+// One conv3x3_wgrad_mfma_v2 launch in the tile and the slab format the plan names; args = the kernel's arguments.  Only the
+// instantiations that exist: bf16, and the PRE forms in UH_BUILD_PRE builds.
+template <typename T, typename... Args>
+static void wgrad_v2_launch(const WgradPlan& p, hipStream_t st, Args... args) {
+    auto form = [&](auto pre) {
+        constexpr bool PRE = decltype(pre)::value;
+        const dim3 block(p.threads);
+        switch ((p.kernel == WG_DMA128 ? 2 : 0) + (p.slab16 ? 1 : 0)) {      // the 128-row tile, fp16-pair slabs
+        case 3: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 4, PRE, true>), p.grid, block, 0, st, args...); break;
+        case 2: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 4, PRE, false>), p.grid, block, 0, st, args...); break;
+        case 1: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 2, PRE, true>), p.grid, block, 0, st, args...); break;
+        default: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 2, PRE, false>), p.grid, block, 0, st, args...); break;
+        }
+    };
+    if (p.pre) {
+        if constexpr (UH_BUILD_PRE) form(std::true_type{});
+    } else
+        form(std::false_type{});
+}
+
+struct WgradCall : ConvCall {
+    const void* dy = nullptr; int lddy = 0;
+    float* dw = nullptr;
+    void* ws = nullptr; size_t ws_bytes = 0;      // the workspace of the slabs
+    int64_t* defer = nullptr;    // uh_conv3x3_wgrad_partials: the slab reduction is NOT launched; defer[0..7] describes it as a row of
+                                 // uh_slab_reduce_batched's table (defer[3] = 0: the path taken has no such row, dw is final)
+};
+
 template <typename T>
-static int conv3x3_wgrad_dispatch(const T* dy, int lddy, const T* x0, int C0, int ld0, const T* x1, int C1, int ld1,
-                                  float* dw, int Cout, void* ws, size_t ws_bytes, int B, int H, int W, hipStream_t st,
-                                  bool split = false, int C0v = -1, int C1v = -1, int Coutv = -1,
-                                  const float* pre_scale = nullptr, const float* pre_shift = nullptr, int64_t* defer = nullptr) {
-    // defer != NULL (uh_conv3x3_wgrad_partials): the slab reduction is NOT launched; defer[0..7] describes it as a row of
-    // uh_slab_reduce_batched's table (defer[3] = 0: the path taken has no slabs, dw is final)
+static int conv3x3_wgrad_dispatch(const WgradCall& c) {
+    const T *dy = (const T*)c.dy, *x0 = (const T*)c.x0, *x1 = (const T*)c.x1;
+    float* slabs = (float*)c.ws;
     constexpr int ES = sizeof(T);
-    const int Cin = C0 + C1;
-    const bool narrow = C0v >= 0;                 // tensors hold fewer channels than the filter is padded to
-    const bool pre = pre_scale != nullptr;        // x0 = raw conv output, BatchNorm + ReLU applied by the loader (bf16 DMA kernel only)
-    if (!narrow) { C0v = C0; C1v = C1; Coutv = Cout; }
-    const bool aligned = uh_aligned16(dy) && uh_aligned16(x0) && (C1 == 0 || uh_aligned16(x1)) && (lddy * ES) % 16 == 0 &&
-                         (ld0 * ES) % 16 == 0 && (C1 == 0 || (ld1 * ES) % 16 == 0) && (C0 % 64 == 0);
-    // the bf16 LDS-DMA kernel (and with it the 128-row tile) needs every tensor addressable through a buffer descriptor
-    bool dma = false;
-    if constexpr (ES == 2) {
-        const int64_t npx_ = (int64_t)B * H * W;
-        const int64_t ldmax_ = ld0 > ld1 ? ld0 : ld1;
-        dma = npx_ * ldmax_ * 2 < (1ll << 31) - 4096 && npx_ * lddy * 2 < (1ll << 31) - 4096;
-    }
-    WgradPlan p = wgrad_plan<T>(B, H, W, Cin, Cout, aligned, dma && !narrow);
-    if (p.kind == 1 && C1 != 0) p.kind = 2;
-    if (narrow && p.kind != 0) {
-        uh_set_error("uh_conv3x3_wgrad_narrow: needs the MFMA path (padded channel counts multiples of 64, 16-byte strides)");
-        return UH_EINVAL;
-    }
-    if (split && p.kind != 0) {
-        uh_set_error("uh_conv3x3_wgrad: bf16x3 needs an MFMA-aligned shape (channel counts multiples of 64, 16-byte strides)");
-        return UH_EINVAL;
-    }
-#if !UH_BUILD_PRE
-    if (pre) {
-        uh_set_error("uh_conv3x3_wgrad_pre: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
-        return UH_EINVAL;
-    }
-#endif
-    if (pre && !(ES == 2 && p.kind == 0 && dma && !narrow && !split)) {
-        uh_set_error("uh_conv3x3_wgrad_pre: needs the bf16 LDS-DMA kernel (64-aligned channels, tensors below 2 GiB); ask uh_conv3x3_pre_ok first");
-        return UH_EINVAL;
-    }
-    if (defer)
-        for (int k = 0; k < 8; ++k) defer[k] = 0;
-    if (p.kind == 2) {
-        hipLaunchKernelGGL(conv3x3_wgrad_generic<T>, dim3(Cout * 9), dim3(256), 0, st, dy, lddy, x0, C0, ld0, x1, C1, ld1,
-                           dw, Cout, B, H, W);
-        UH_CHECK_LAUNCH("conv3x3_wgrad_generic");
-        return UH_OK;
-    }
-    size_t need = (size_t)p.nsplit * Cout * 9 * Cin * sizeof(float);
-    if (ws_bytes < need || !ws) {
-        uh_set_error("uh_conv3x3_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
+    const int Cin = c.C0 + c.C1;
+    const bool split = c.dt == UH_F32X3, narrow = c.C0v >= 0, pre = c.pre_scale != nullptr;
+    const int C0v = narrow ? c.C0v : c.C0, C1v = narrow ? c.C1v : c.C1, Coutv = narrow ? c.Coutv : c.Cout;
+    const WgradAlign a16 = {uh_aligned16(dy) && uh_aligned16(x0) && (c.C1 == 0 || uh_aligned16(x1)), uh_aligned16(dy), uh_aligned16(c.dw),
+                            uh_aligned16(slabs)};
+    const WgradPlan p = wgrad_plan(ES, c.B, c.H, c.W, c.C0, c.C1, c.Cout, c.ld0, c.ld1, c.lddy, a16, narrow, pre);
+    const bool mfma = p.kernel >= WG_MFMA, dma = p.kernel >= WG_DMA64;
+    UH_REQUIRE(!narrow || mfma, "uh_conv3x3_wgrad_narrow: needs the MFMA path (padded channel counts multiples of 64, 16-byte strides)");
+    UH_REQUIRE(!split || mfma, "uh_conv3x3_wgrad: bf16x3 needs an MFMA-aligned shape (channel counts multiples of 64, 16-byte strides)");
+    UH_REQUIRE(!pre || UH_BUILD_PRE, "uh_conv3x3_wgrad_pre: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
+    UH_REQUIRE(!pre || (dma && !narrow && !split), "uh_conv3x3_wgrad_pre: needs the bf16 LDS-DMA kernel (64-aligned channels, tensors below 2 GiB); ask uh_conv3x3_pre_ok first");
+    for (int k = 0; c.defer && k < 8; ++k) c.defer[k] = 0;
+    if (p.kernel != WG_GENERIC && (c.ws_bytes < wgrad_slab_bytes(p) || !c.ws)) {
+        uh_set_error("uh_conv3x3_wgrad: workspace %zu < %zu bytes", c.ws_bytes, wgrad_slab_bytes(p));
         return UH_EWORKSPACE;
     }
-    float* slabs = (float*)ws;
-    // block-scaled fp16-pair slabs: the bf16 LDS-DMA kernel's default (see SLAB16); the inverse scales follow the slabs in `ws`
-    // (nsplit * n * 2 + nsplit * blocks * 4 bytes <= the nsplit * n * 4 the workspace is sized for)
-    static const bool slab_f32 = getenv("UH_WGRAD_SLAB_F32") != nullptr && getenv("UH_WGRAD_SLAB_F32")[0] == '1';
-    const bool slab16 = ES == 2 && p.kind == 0 && dma && !slab_f32 && uh_aligned16(dw);
-    if (p.kind == 0) {
-        const int64_t npx = (int64_t)B * H * W;
-        const int64_t ldmax = ld0 > ld1 ? ld0 : ld1;
-        if constexpr (ES == 2) {
-            if (dma) {
-                // byte extents of the (sliced) source views as seen from their base pointers
-                unsigned xb = (unsigned)(npx * ldmax * 2), db = (unsigned)(npx * lddy * 2);
-#define UH_LAUNCH_WGRAD_V2(NWR_, PRE_, S16_)                                                                                      \
-    hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, NWR_, PRE_, S16_>), dim3(p.nsplit, (Cin / 64) * (Cout / (32 * NWR_))),           \
-                       dim3(128 * NWR_), 0, st, dy, lddy, x0, C0, ld0, x1, C1, ld1, slabs, Cout, B, H, W, p.tilesX, p.tilesY,      \
-                       p.nsplit, db, xb, C0v, C1v, Coutv, pre_scale, pre_shift)
-#if UH_BUILD_PRE
-                if (pre) {
-                    if (p.nwr == 4) { if (slab16) UH_LAUNCH_WGRAD_V2(4, true, true); else UH_LAUNCH_WGRAD_V2(4, true, false); }
-                    else { if (slab16) UH_LAUNCH_WGRAD_V2(2, true, true); else UH_LAUNCH_WGRAD_V2(2, true, false); }
-                } else
-#endif
-                if (p.nwr == 4) { if (slab16) UH_LAUNCH_WGRAD_V2(4, false, true); else UH_LAUNCH_WGRAD_V2(4, false, false); }
-                else { if (slab16) UH_LAUNCH_WGRAD_V2(2, false, true); else UH_LAUNCH_WGRAD_V2(2, false, false); }
-#undef UH_LAUNCH_WGRAD_V2
-                UH_CHECK_LAUNCH("conv3x3_wgrad_mfma_v2");
-            }
-        }
-        if (!dma) {
-            if (split) {
-                if constexpr (ES == 4)
-                    hipLaunchKernelGGL((conv3x3_wgrad_mfma<T, true>), dim3(p.nsplit, (Cin / 64) * (Cout / 64)), dim3(256), 0, st, dy,
-                                       lddy, x0, C0, ld0, x1, C1, ld1, slabs, Cout, B, H, W, p.tilesX, p.tilesY, p.nsplit, C0v,
-                                       C1v, Coutv);
-            } else
-                hipLaunchKernelGGL(conv3x3_wgrad_mfma<T>, dim3(p.nsplit, (Cin / 64) * (Cout / 64)), dim3(256), 0, st, dy, lddy,
-                                   x0, C0, ld0, x1, C1, ld1, slabs, Cout, B, H, W, p.tilesX, p.tilesY, p.nsplit, C0v, C1v, Coutv);
-            UH_CHECK_LAUNCH("conv3x3_wgrad_mfma");
-        }
-    } else {
-        constexpr int V = 16 / ES;
-        bool done = false;
-        if constexpr (ES == 2) {
-            if (Cin <= 4 && Cout == 64 && uh_aligned16(dy) && (lddy * ES) % 16 == 0) {      // 72 accumulators per lane
-                hipLaunchKernelGGL((conv3x3_wgrad_stem_v3<T, 1>), dim3(p.nsplit, Cin), dim3(256), 0, st, dy, lddy, x0, ld0, slabs,
-                                   B, H, W, p.tilesX, p.tilesY, Cin);
-                UH_CHECK_LAUNCH("conv3x3_wgrad_stem_v3");
-                done = true;
-            }
-        }
-        if (done) {
-        } else if (Cout % V == 0 && uh_aligned16(dy) && (lddy * ES) % 16 == 0) {
-            hipLaunchKernelGGL(conv3x3_wgrad_stem_v2<T>, dim3(p.nsplit, 1, Cin), dim3(256), 0, st, dy, lddy, x0, Cin, ld0,
-                               slabs, Cout, B, H, W, p.nsplit);
-            UH_CHECK_LAUNCH("conv3x3_wgrad_stem_v2");
-        } else {
-            hipLaunchKernelGGL(conv3x3_wgrad_stem<T>, dim3(p.nsplit, (Cout + 63) / 64), dim3(256), 0, st, dy, lddy, x0, Cin,
-                               ld0, slabs, Cout, B, H, W, p.tilesX, p.tilesY, p.nsplit);
-            UH_CHECK_LAUNCH("conv3x3_wgrad_stem");
-        }
+    const dim3 block(p.threads);
+    const int64_t px = (int64_t)c.B * c.H * c.W;
+    switch (p.kernel) {
+    case WG_GENERIC:
+        hipLaunchKernelGGL(conv3x3_wgrad_generic<T>, p.grid, block, 0, c.st, dy, c.lddy, x0, c.C0, c.ld0, x1, c.C1, c.ld1, c.dw, c.Cout, c.B, c.H, c.W);
+        UH_CHECK_LAUNCH("conv3x3_wgrad_generic");
+        return UH_OK;
+    case WG_DMA64: case WG_DMA128:
+        // db, xb: byte extents of the (sliced) source views as seen from their base pointers (below 2 GiB: wgrad_plan)
+        if constexpr (ES == 2)
+            wgrad_v2_launch<T>(p, c.st, dy, c.lddy, x0, c.C0, c.ld0, x1, c.C1, c.ld1, slabs, c.Cout, c.B, c.H, c.W, p.tilesX, p.tilesY, p.nsplit,
+                               (unsigned)(px * c.lddy * 2), (unsigned)(px * (c.ld0 > c.ld1 ? c.ld0 : c.ld1) * 2), C0v, C1v, Coutv, c.pre_scale,
+                               c.pre_shift);
+        UH_CHECK_LAUNCH("conv3x3_wgrad_mfma_v2");
+        break;
+    case WG_MFMA:
+        if (split) {
+            if constexpr (ES == 4)
+                hipLaunchKernelGGL((conv3x3_wgrad_mfma<T, true>), p.grid, block, 0, c.st, dy, c.lddy, x0, c.C0, c.ld0, x1, c.C1, c.ld1, slabs, c.Cout,
+                                   c.B, c.H, c.W, p.tilesX, p.tilesY, p.nsplit, C0v, C1v, Coutv);
+        } else
+            hipLaunchKernelGGL(conv3x3_wgrad_mfma<T>, p.grid, block, 0, c.st, dy, c.lddy, x0, c.C0, c.ld0, x1, c.C1, c.ld1, slabs, c.Cout, c.B, c.H, c.W,
+                               p.tilesX, p.tilesY, p.nsplit, C0v, C1v, Coutv);
+        UH_CHECK_LAUNCH("conv3x3_wgrad_mfma");
+        break;
+    case WG_STEM_V3:
+        if constexpr (ES == 2)
+            hipLaunchKernelGGL((conv3x3_wgrad_stem_v3<T, 1>), p.grid, block, 0, c.st, dy, c.lddy, x0, c.ld0, slabs, c.B, c.H, c.W, p.tilesX,
+                               p.tilesY, Cin);
+        UH_CHECK_LAUNCH("conv3x3_wgrad_stem_v3");
+        break;
+    case WG_STEM_V2:
+        hipLaunchKernelGGL(conv3x3_wgrad_stem_v2<T>, p.grid, block, 0, c.st, dy, c.lddy, x0, Cin, c.ld0, slabs, c.Cout, c.B, c.H, c.W, p.nsplit);
+        UH_CHECK_LAUNCH("conv3x3_wgrad_stem_v2");
+        break;
+    case WG_STEM:
+        hipLaunchKernelGGL(conv3x3_wgrad_stem<T>, p.grid, block, 0, c.st, dy, c.lddy, x0, Cin, c.ld0, slabs, c.Cout, c.B, c.H, c.W, p.tilesX,
+                           p.tilesY, p.nsplit);
+        UH_CHECK_LAUNCH("conv3x3_wgrad_stem");
+        break;
     }
-    int64_t n = (int64_t)Cout * 9 * Cin;      // multiple of 4 on every slab path (Cout % 64 == 0 or 9*... stem: Cout*9*Cin)
-    if (defer && n % 4 == 0 && uh_aligned16(dw) && uh_aligned16(slabs)) {
-        defer[0] = (int64_t)(uintptr_t)slabs; defer[1] = (int64_t)(uintptr_t)dw; defer[2] = n; defer[3] = p.nsplit;
-        defer[4] = slab16 ? 1 : 0; defer[5] = 9 * Cin; defer[7] = 32 * p.nwr;
-        defer[6] = slab16 ? uh_slab16_blocks(n / 2, p.nsplit) : (n / 4 + 63) / 64;      // blocks of the reduction (the caller turns it into an offset)
+    const SlabReduce& r = p.reduce;
+    // the forms slab_reduce_batched_kernel runs: 16-byte pieces on both sides ([6] = the row's blocks, its first block to the caller)
+    if (c.defer && (r.kernel == SR_VEC || r.kernel == SR_F16PAIR) && a16.ws) {
+        const int64_t row[8] = {(int64_t)(uintptr_t)slabs, (int64_t)(uintptr_t)c.dw, r.n, r.nsplit, r.kernel == SR_F16PAIR, r.row, r.blocks, r.coblk};
+        for (int k = 0; k < 8; ++k) c.defer[k] = row[k];
         return UH_OK;
     }
-    if (slab16) {
-        const int64_t npair = n / 2;
-        hipLaunchKernelGGL(slab_reduce_f16pair_kernel, dim3((unsigned)uh_slab16_blocks(npair, p.nsplit)), dim3(256), 0, st,
-                           (const unsigned*)slabs, dw, npair, 9 * Cin, p.nsplit, 32 * p.nwr);
-        UH_CHECK_LAUNCH("slab_reduce_f16pair_kernel");
-        return UH_OK;
-    }
-    if (n % 4 != 0 || !uh_aligned16(dw) || !uh_aligned16(slabs))
-        hipLaunchKernelGGL(slab_reduce_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           (const float*)slabs, dw, n, p.nsplit);
-    else
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((n / 4 + 63) / 64)), dim3(256), 0, st, (const float*)slabs,
-                           dw, n, p.nsplit);
-    UH_CHECK_LAUNCH("slab_reduce_kernel");
-    return UH_OK;
+    return slab_reduce_launch(r, slabs, c.dw, c.st);
+}
+
+static int conv3x3_wgrad_call(const char* fn, WgradCall& c, int dt, int flags = 0) {
+    if (const int rc = conv_check(fn, c, c.dy && c.dw, c.lddy, dt, flags)) return rc;
+    return c.dt == UH_BF16 ? conv3x3_wgrad_dispatch<bf16_t>(c) : conv3x3_wgrad_dispatch<float>(c);
 }
 
 extern "C" int uh_conv3x3_wgrad(const void* dy, int lddy, const void* x0, int C0, int ld0, const void* x1, int C1, int ld1,
                                 float* dw_krsc, int Cout, void* ws, size_t ws_bytes, int B, int H, int W, int dt,
                                 uh_stream stream) {
-    UH_REQUIRE(dy && x0 && dw_krsc, "uh_conv3x3_wgrad: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_wgrad: bad shape");
-    UH_REQUIRE(lddy >= Cout && ld0 >= C0 && (C1 == 0 || (x1 && ld1 >= C1)), "uh_conv3x3_wgrad: bad strides");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_wgrad: pixel count overflows int32");
-    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_wgrad: bad dtype %d", dt);
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == UH_BF16)
-        return conv3x3_wgrad_dispatch<bf16_t>((const bf16_t*)dy, lddy, (const bf16_t*)x0, C0, ld0, (const bf16_t*)x1, C1,
-                                              ld1, dw_krsc, Cout, ws, ws_bytes, B, H, W, st);
-    return conv3x3_wgrad_dispatch<float>((const float*)dy, lddy, (const float*)x0, C0, ld0, (const float*)x1, C1, ld1,
-                                         dw_krsc, Cout, ws, ws_bytes, B, H, W, st, dt == UH_F32X3);
+    WgradCall c;
+    c.dy = dy; c.lddy = lddy; c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.x1 = x1; c.C1 = C1; c.ld1 = ld1; c.dw = dw_krsc; c.Cout = Cout;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream;
+    return conv3x3_wgrad_call("uh_conv3x3_wgrad", c, dt);
 }
 
 // uh_conv3x3_wgrad without its last step: the contraction runs, the per-split partial results stay in `ws` (which must live until
@@ -3677,17 +3701,11 @@ extern "C" int uh_conv3x3_wgrad(const void* dy, int lddy, const void* x0, int C0
 extern "C" int uh_conv3x3_wgrad_partials(const void* dy, int lddy, const void* x0, int C0, int ld0, const void* x1, int C1,
                                          int ld1, float* dw_krsc, int Cout, void* ws, size_t ws_bytes, int B, int H, int W,
                                          int dt, int64_t* desc, uh_stream stream) {
-    UH_REQUIRE(dy && x0 && dw_krsc && desc, "uh_conv3x3_wgrad_partials: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_wgrad_partials: bad shape");
-    UH_REQUIRE(lddy >= Cout && ld0 >= C0 && (C1 == 0 || (x1 && ld1 >= C1)), "uh_conv3x3_wgrad_partials: bad strides");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_wgrad_partials: pixel count overflows int32");
-    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_wgrad_partials: bad dtype %d", dt);
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == UH_BF16)
-        return conv3x3_wgrad_dispatch<bf16_t>((const bf16_t*)dy, lddy, (const bf16_t*)x0, C0, ld0, (const bf16_t*)x1, C1,
-                                              ld1, dw_krsc, Cout, ws, ws_bytes, B, H, W, st, false, -1, -1, -1, nullptr, nullptr, desc);
-    return conv3x3_wgrad_dispatch<float>((const float*)dy, lddy, (const float*)x0, C0, ld0, (const float*)x1, C1, ld1,
-                                         dw_krsc, Cout, ws, ws_bytes, B, H, W, st, dt == UH_F32X3, -1, -1, -1, nullptr, nullptr, desc);
+    UH_REQUIRE(desc, "uh_conv3x3_wgrad_partials: null pointer");
+    WgradCall c;
+    c.dy = dy; c.lddy = lddy; c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.x1 = x1; c.C1 = C1; c.ld1 = ld1; c.dw = dw_krsc; c.Cout = Cout;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream; c.defer = desc;
+    return conv3x3_wgrad_call("uh_conv3x3_wgrad_partials", c, dt);
 }
 
 // table: DEVICE memory, nrows x 8 int64 (rows as uh_conv3x3_wgrad_partials fills them, [6] = first block of the row);
@@ -3706,14 +3724,13 @@ extern "C" int uh_slab_reduce_batched(const int64_t* table, int nrows, int64_t t
 extern "C" int uh_conv3x3_wgrad_pre(const void* dy, int lddy, const void* x0, int C0, int ld0, const float* pre_scale,
                                     const float* pre_shift, float* dw_krsc, int Cout, void* ws, size_t ws_bytes, int B, int H,
                                     int W, int dt, uh_stream stream) {
-    UH_REQUIRE(dy && x0 && dw_krsc && pre_scale && pre_shift, "uh_conv3x3_wgrad_pre: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && Cout > 0, "uh_conv3x3_wgrad_pre: bad shape");
-    UH_REQUIRE(lddy >= Cout && ld0 >= C0, "uh_conv3x3_wgrad_pre: bad strides");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_wgrad_pre: pixel count overflows int32");
-    UH_REQUIRE(dt == UH_BF16, "uh_conv3x3_wgrad_pre: bf16 only (dtype %d)", dt);
+    UH_REQUIRE(pre_scale && pre_shift, "uh_conv3x3_wgrad_pre: null pointer");
+    WgradCall c;
+    c.dy = dy; c.lddy = lddy; c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.dw = dw_krsc; c.Cout = Cout; c.ws = ws; c.ws_bytes = ws_bytes;
+    c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream; c.pre_scale = pre_scale; c.pre_shift = pre_shift;
+    if (const int rc = conv_check("uh_conv3x3_wgrad_pre", c, c.dy && c.dw, c.lddy, dt, CK_BF16_ONLY)) return rc;
     UH_REQUIRE(C0 % 64 == 0 && Cout % 64 == 0, "uh_conv3x3_wgrad_pre: channel counts must be multiples of 64");
-    return conv3x3_wgrad_dispatch<bf16_t>((const bf16_t*)dy, lddy, (const bf16_t*)x0, C0, ld0, nullptr, 0, 0, dw_krsc, Cout, ws,
-                                          ws_bytes, B, H, W, (hipStream_t)stream, false, -1, -1, -1, pre_scale, pre_shift);
+    return conv3x3_wgrad_dispatch<bf16_t>(c);
 }
 
 // ---- the stem with a recomputed output (kernels: stem_mfma.hip): 1 -> 64 channels, bf16, w = KRSC pack [64][9][1]
@@ -3770,22 +3787,13 @@ extern "C" int uh_stem_bn_relu_bwd_wgrad(const void* dz, int lddz, const void* x
                "uh_stem_bn_relu_bwd_wgrad: null pointer / bad stride");
     UH_REQUIRE(uh_aligned16(dz) && (lddz * 2) % 16 == 0, "uh_stem_bn_relu_bwd_wgrad: dz must be 16-byte aligned with a 16-byte pixel pitch");
     UH_REQUIRE(ws_bytes >= uh_stem_bwd_wgrad_ws_bytes(B, H, W, Cin), "uh_stem_bn_relu_bwd_wgrad: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     const float inv_n = (float)(1.0 / (double)(n_total > 0 ? n_total : (int64_t)B * H * W));
     float* slabs = (float*)ws;
     const int rc = uh_stem_mfma_launch(3, x, ldx, w, scale, shift, mean, rstd, dgamma, dbeta, inv_n, dz, lddz, nullptr, 0, slabs, B, H, W,
                                        uh_stem_nblk(B, H, W), stream);
     if (rc != UH_OK) return rc;
-    const int64_t n = (int64_t)64 * 9 * Cin;
-    const int nsplit = uh_stem_nblk(B, H, W);
-    if (n % 4 != 0 || !uh_aligned16(dw_krsc) || !uh_aligned16(slabs))
-        hipLaunchKernelGGL(slab_reduce_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)slabs, dw_krsc, n, nsplit);
-    else if (n <= 4096 && nsplit >= 256)
-        hipLaunchKernelGGL(slab_reduce_tall_kernel, dim3((unsigned)((n / 4 + 3) / 4)), dim3(256), 0, st, (const float*)slabs, dw_krsc, n, nsplit);
-    else
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((n / 4 + 63) / 64)), dim3(256), 0, st, (const float*)slabs, dw_krsc, n, nsplit);
-    UH_CHECK_LAUNCH("slab_reduce_kernel");
-    return UH_OK;
+    return slab_reduce_launch(slab_reduce_plan((int64_t)64 * 9 * Cin, uh_stem_nblk(B, H, W), 9 * Cin, 64, false,
+                                               uh_aligned16(dw_krsc) && uh_aligned16(slabs), true), slabs, dw_krsc, (hipStream_t)stream);
 }
 
 // Narrow variant (see uh_conv3x3_fwd_narrow): the filter gradient is that of the PADDED layer [Cout][3][3][C0 + C1]; x0 / x1 /
@@ -3793,18 +3801,9 @@ extern "C" int uh_stem_bn_relu_bwd_wgrad(const void* dz, int lddz, const void* x
 extern "C" int uh_conv3x3_wgrad_narrow(const void* dy, int lddy, int Cout, int Coutv, const void* x0, int C0, int C0v, int ld0,
                                        const void* x1, int C1, int C1v, int ld1, float* dw_krsc, void* ws, size_t ws_bytes,
                                        int B, int H, int W, int dt, uh_stream stream) {
-    UH_REQUIRE(dy && x0 && dw_krsc, "uh_conv3x3_wgrad_narrow: null pointer");
-    UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_wgrad_narrow: bad shape");
-    UH_REQUIRE(C0v > 0 && C0v <= C0 && C1v >= 0 && C1v <= C1 && Coutv > 0 && Coutv <= Cout, "uh_conv3x3_wgrad_narrow: bad valid counts");
-    UH_REQUIRE(lddy >= Coutv && ld0 >= C0v && (C1 == 0 || (x1 && ld1 >= C1v)), "uh_conv3x3_wgrad_narrow: bad strides");
-    UH_REQUIRE((int64_t)B * H * W < (1ll << 31), "uh_conv3x3_wgrad_narrow: pixel count overflows int32");
-    UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_wgrad_narrow: bad dtype %d", dt);
-    const int vec = dt == UH_BF16 ? 8 : 4;
-    UH_REQUIRE(C0v % vec == 0 && C1v % vec == 0 && Coutv % vec == 0, "uh_conv3x3_wgrad_narrow: valid counts must be multiples of a 16-byte piece");
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == UH_BF16)
-        return conv3x3_wgrad_dispatch<bf16_t>((const bf16_t*)dy, lddy, (const bf16_t*)x0, C0, ld0, (const bf16_t*)x1, C1,
-                                              ld1, dw_krsc, Cout, ws, ws_bytes, B, H, W, st, false, C0v, C1v, Coutv);
-    return conv3x3_wgrad_dispatch<float>((const float*)dy, lddy, (const float*)x0, C0, ld0, (const float*)x1, C1, ld1,
-                                         dw_krsc, Cout, ws, ws_bytes, B, H, W, st, dt == UH_F32X3, C0v, C1v, Coutv);
+    WgradCall c;
+    c.dy = dy; c.lddy = lddy; c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.x1 = x1; c.C1 = C1; c.ld1 = ld1; c.dw = dw_krsc; c.Cout = Cout;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream;
+    c.C0v = C0v; c.C1v = C1v; c.Coutv = Coutv;
+    return conv3x3_wgrad_call("uh_conv3x3_wgrad_narrow", c, dt, CK_NARROW);
 }
