@@ -193,10 +193,10 @@ def test_second_consumer_of_the_activation_falls_back_to_the_reduce_pass():
         try:
             link = ops.BnSumLink() if fuse else None
             xin = x.clone().requires_grad_(True)
-            z1 = ops.ConvBnReluFn.apply(xin, None, c1.weight, b1.weight, b1.bias, b1.running_mean, b1.running_var, b1.num_batches_tracked,
-                                        True, 0.1, 1e-5, ops.TAIL_NONE, None, None, False, None, link, None)
-            z2 = ops.ConvBnReluFn.apply(z1, None, c2.weight, b2.weight, b2.bias, b2.running_mean, b2.running_var, b2.num_batches_tracked,
-                                        True, 0.1, 1e-5, ops.TAIL_NONE, None, None, False, None, None, link)
+            z1 = ops.ConvBnReluFn.apply(xin, None, c1.weight, b1.weight, b1.bias, None, None, ops.ConvBnOpts(
+                b1.running_mean, b1.running_var, b1.num_batches_tracked, True, 0.1, 1e-5, bnsum_pub=link))
+            z2 = ops.ConvBnReluFn.apply(z1, None, c2.weight, b2.weight, b2.bias, None, None, ops.ConvBnOpts(
+                b2.running_mean, b2.running_var, b2.num_batches_tracked, True, 0.1, 1e-5, bnsum_use=link))
             loss = (z2.float() * cot.float()).sum()
             if second_reader:
                 loss = loss + (z1.float() * side.float()).sum()

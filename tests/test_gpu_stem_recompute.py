@@ -41,8 +41,8 @@ def test_recomputed_stem_matches_the_stored_path(B, H, W, cin):
             conv, bn = conv.to(dev), bn.to(dev)
             w = conv.weight
             if mode == "stored":
-                z = ops.ConvBnReluFn.apply(x, None, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                           True, 0.1, bn.eps)
+                z = ops.ConvBnReluFn.apply(x, None, w, bn.weight, bn.bias, None, None, ops.ConvBnOpts(
+                    bn.running_mean, bn.running_var, bn.num_batches_tracked, True, 0.1, bn.eps))
             else:
                 assert ops.stem_recompute_ok(x, cin, 64)
                 z = ops.StemConvBnReluFn.apply(x, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,

@@ -8,7 +8,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch.autograd import Function
@@ -89,6 +89,10 @@ def pixel_ld(t: torch.Tensor) -> int:
     return max(C, 1)
 
 
+def pixel_ld_or0(t: Optional[torch.Tensor]) -> int:
+    return 0 if t is None else pixel_ld(t)          # (an absent second source)
+
+
 def is_pixel_dense(t: torch.Tensor) -> bool:
     B, H, W, C = t.shape
     if C > 1 and t.stride(3) != 1:
@@ -108,6 +112,11 @@ def is_pixel_dense(t: torch.Tensor) -> bool:
 def dense_nhwc(t: torch.Tensor) -> torch.Tensor:
     """Return `t` ([B,H,W,C]) if it can be walked with one pixel stride, else a packed copy."""
     return t if is_pixel_dense(t) else t.contiguous()
+
+
+def grad_like(dz: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
+    """An incoming NHWC gradient in `ref`'s dtype, walkable with one pixel stride."""
+    return dense_nhwc(dz if dz.dtype == ref.dtype else dz.to(ref.dtype))
 
 
 def to_nhwc(x: torch.Tensor, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -171,6 +180,11 @@ def conv_dt(x: torch.Tensor, C0: int, C1: int, Cout: int, need_dx: bool) -> int:
 
 # Use fragment-major filter packs (UH_WFRAG) wherever the LDS-DMA MFMA kernel runs (False: KRSC everywhere, for A/B runs).
 WFRAG = True
+
+
+def conv_flags(cdt: int, frag: bool) -> int:
+    """dtype code of a conv call + the flag that says its filter pack is fragment-major."""
+    return cdt | (UH_WFRAG if frag else 0)
 
 
 # Plan length of the eval forward (0 = off).  Under `with plan_images(1):` the eval-mode Conv->BN->ReLU and the transposed
@@ -350,8 +364,8 @@ def conv3x3_fwd(x0: torch.Tensor, x1: Optional[torch.Tensor], w_packed: torch.Te
         stats = torch.empty(nslab * (2 * Cout + 2), dtype=torch.float32, device=x0.device)
     name = "conv3x3_fwd_" + _variant((C0, C1), Cout, x0.element_size())
     with _Timed(name, 2.0 * B * H * W * Cout * 9 * (C0 + C1), ("fwd" if want_stats else "dgrad", B, H, W, C0 + C1, Cout)):
-        LIB.call("uh_conv3x3_fwd", x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1, 0 if x1 is None else pixel_ld(x1),
-                 w_packed.data_ptr(), y.data_ptr(), Cout, Cout, _p(stats), B, H, W, dt | (UH_WFRAG if wfrag else 0), _stream())
+        LIB.call("uh_conv3x3_fwd", x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1, pixel_ld_or0(x1),
+                 w_packed.data_ptr(), y.data_ptr(), Cout, Cout, _p(stats), B, H, W, conv_flags(dt, wfrag), _stream())
     return y, stats, nslab
 
 
@@ -450,21 +464,22 @@ def conv3x3_wgrad(dy: torch.Tensor, x0: torch.Tensor, x1: Optional[torch.Tensor]
     name = "conv3x3_wgrad_" + ("mfma" if (C0 % 64 == 0 and C1 % 64 == 0 and Cout % 64 == 0) else
                                 ("stem" if C0 + C1 <= 4 else "generic"))
     batch = SLAB_BATCH if (defer_cb is not None and DEFER_SLABS and name == "conv3x3_wgrad_mfma") else None
+    timed = _Timed(name, 2.0 * B * H * W * Cout * 9 * (C0 + C1), ("wgrad", B, H, W, C0 + C1, Cout))
     if batch is not None:
         ws = batch.workspace(out_krsc.data_ptr(), nbytes, dy.device)
         desc = (ctypes.c_int64 * 8)()
-        with _Timed(name, 2.0 * B * H * W * Cout * 9 * (C0 + C1), ("wgrad", B, H, W, C0 + C1, Cout)):
+        with timed:
             LIB.call("uh_conv3x3_wgrad_partials", dy.data_ptr(), pixel_ld(dy), x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1,
-                     0 if x1 is None else pixel_ld(x1), out_krsc.data_ptr(), Cout, ws.data_ptr(), nbytes, B, H, W, dt,
+                     pixel_ld_or0(x1), out_krsc.data_ptr(), Cout, ws.data_ptr(), nbytes, B, H, W, dt,
                      ctypes.addressof(desc), _stream())
         if desc[3] == 0:                       # a path without slabs: the gradient is final
             return False
         batch.add(list(desc), defer_cb)
         return True
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
-    with _Timed(name, 2.0 * B * H * W * Cout * 9 * (C0 + C1), ("wgrad", B, H, W, C0 + C1, Cout)):
+    with timed:
         LIB.call("uh_conv3x3_wgrad", dy.data_ptr(), pixel_ld(dy), x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1,
-                 0 if x1 is None else pixel_ld(x1), out_krsc.data_ptr(), Cout, ws.data_ptr(), nbytes, B, H, W, dt, _stream())
+                 pixel_ld_or0(x1), out_krsc.data_ptr(), Cout, ws.data_ptr(), nbytes, B, H, W, dt, _stream())
     return False
 
 
@@ -513,7 +528,7 @@ def bench_double_conv(B: int, H: int, W: int, Cin: int, Cout: int, dtype: torch.
 
     def fwd(src, cin, wp, dst, cout, stat, frag=False):
         LIB.call("uh_conv3x3_fwd", src.data_ptr(), cin, cin, None, 0, 0, wp.data_ptr(), dst.data_ptr(), cout, cout,
-                 _p(stat), B, H, W, dt | (UH_WFRAG if frag else 0), st)
+                 _p(stat), B, H, W, conv_flags(dt, frag), st)
 
     def wgrad(dy, src, cin):
         LIB.call("uh_conv3x3_wgrad", dy.data_ptr(), Cout, src.data_ptr(), cin, cin, None, 0, 0, dw.data_ptr(), Cout,
@@ -556,14 +571,20 @@ SYNC_BN = None
 SYNC_BN_BATCH = None
 
 
-def _sync_bn_forward(coef, m2, n_local, Cout, g32, b32, running_mean, running_var, nbt_ptr, momentum, eps):
+def coef_views(coef: torch.Tensor):
+    """-> (scale, shift, mean, rstd): the four per-channel views of a [scale | shift | mean | rstd] buffer."""
+    C = coef.numel() // 4
+    return coef[:C], coef[C:2 * C], coef[2 * C:3 * C], coef[3 * C:]
+
+
+def _sync_bn_forward(coef, m2, n_local, Cout, g32, b32, o, nbt_ptr):
     """Merge the per-rank (count, mean, M2) rows into the global-batch statistics: one all_gather of 2C+1 floats per
     layer, then the same uh_bn_finalize over `world` rows (Chan merge in double), which also updates the running
     statistics with the global unbiased variance.  Returns the global pixel count."""
     import torch.distributed as dist
     group, world = SYNC_BN
     dev = coef.device
-    mean = coef[2 * Cout:3 * Cout]
+    mean = coef_views(coef)[2]
     row = torch.cat([mean, m2, torch.full((1,), float(n_local), dtype=torch.float32, device=dev)])
     gathered = torch.empty(world * (2 * Cout + 1), dtype=torch.float32, device=dev)
     dist.all_gather(list(gathered.view(world, 2 * Cout + 1).unbind(0)), row, group=group)
@@ -575,11 +596,78 @@ def _sync_bn_forward(coef, m2, n_local, Cout, g32, b32, running_mean, running_va
     # sizes once per step, so ragged shards -- the last batch of an epoch -- get the right variance denominator)
     gb, lb = SYNC_BN_BATCH if SYNC_BN_BATCH is not None else (world, 1)
     n_total = int(n_local) * gb // lb
-    scale, shift, rstd = coef[:Cout], coef[Cout:2 * Cout], coef[3 * Cout:]
-    LIB.call("uh_bn_finalize", stats.data_ptr(), world, Cout, n_total, g32.data_ptr(), b32.data_ptr(),
-             _p(running_mean), _p(running_var), nbt_ptr, float(momentum), float(eps), scale.data_ptr(), shift.data_ptr(),
-             mean.data_ptr(), rstd.data_ptr(), None, _stream())
+    LIB.call("uh_bn_finalize", stats.data_ptr(), world, Cout, n_total, g32.data_ptr(), b32.data_ptr(), _p(o.running_mean),
+             _p(o.running_var), nbt_ptr, float(o.momentum), float(o.eps), *[v.data_ptr() for v in coef_views(coef)], None, _stream())
     return n_total
+
+
+def _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, o, ldc: Optional[int] = None):
+    """Per-channel [scale | shift | mean | rstd] from the conv kernels' statistics rows (+ running statistics /
+    num_batches_tracked update, + the cross-rank merge under SyncBN; `o`: the layer's ConvBnOpts).  `ldc`: the rows are that many channels wide and only
+    the first Cout count (small-width layers: the conv is computed for the padded layer; uh_bn_finalize_ld).
+    -> (coef, n_total)"""
+    global BN_STATS_EPOCH
+    BN_STATS_EPOCH += 1                       # running statistics are about to change under torch's feet
+    dev = stats.device
+    coef = torch.empty(4 * Cout, dtype=torch.float32, device=dev)
+    out = [v.data_ptr() for v in coef_views(coef)]
+    g32 = gamma if gamma.dtype == torch.float32 else gamma.float()
+    b32 = beta if beta.dtype == torch.float32 else beta.float()
+    nbt = o.num_batches_tracked
+    fused_nbt = nbt is not None and nbt.is_cuda and nbt.dtype == torch.int64
+    nbt_ptr = nbt.data_ptr() if fused_nbt else None
+    rows = ("uh_bn_finalize", stats.data_ptr(), nslab) if ldc is None else ("uh_bn_finalize_ld", stats.data_ptr(), nslab, ldc)
+    # (SyncBN: this call only forms the local mean / M2; the merge below updates the running statistics)
+    m2 = None if SYNC_BN is None else torch.empty(Cout, dtype=torch.float32, device=dev)
+    running = (_p(o.running_mean), _p(o.running_var), nbt_ptr) if SYNC_BN is None else (None, None, None)
+    LIB.call(*rows, Cout, n, g32.data_ptr(), b32.data_ptr(), *running, float(o.momentum), float(o.eps), *out, _p(m2), _stream())
+    n_total = n if SYNC_BN is None else _sync_bn_forward(coef, m2, n, Cout, g32, b32, o, nbt_ptr)
+    if nbt is not None and not fused_nbt:
+        nbt.add_(1)
+    return coef, n_total
+
+
+def _bn_global_sums(dgamma, dbeta, C, sync_bn):
+    """SyncBN: the parameter gradients stay LOCAL sums (the gradient all-reduce SUMS them like every other gradient: the loss
+    is already normalised by the global batch); the dx formula needs the GLOBAL sums.  -> (sum for gamma, sum for beta)"""
+    import torch.distributed as dist
+    glob = torch.cat([dgamma.reshape(-1), dbeta.reshape(-1)])
+    dist.all_reduce(glob, op=dist.ReduceOp.SUM, group=sync_bn[0])
+    return glob[:C], glob[C:]
+
+
+def _bn_backward_finish(partials, nblk, C, dgamma, dbeta, sync_bn, n_total, apply):
+    """Close BatchNorm backward over `nblk` rows of partial sums: `apply(part_ptr, nb, dg_ptr, db_ptr, n_total)` finishes the
+    per-channel sums itself (local statistics), or is handed the global ones and the global pixel count (SyncBN)."""
+    if sync_bn is None:
+        apply(partials.data_ptr(), nblk, dgamma.data_ptr(), dbeta.data_ptr(), 0)
+        return
+    LIB.call("uh_bn_bwd_finalize", partials.data_ptr(), nblk, C, dgamma.data_ptr(), dbeta.data_ptr(), _stream())
+    sums_g, sums_b = _bn_global_sums(dgamma, dbeta, C, sync_bn)
+    apply(None, 0, sums_g.data_ptr(), sums_b.data_ptr(), n_total)
+
+
+def _bn_param_grads(bufs, wanted):
+    """`bufs`: the (buffer, callback) pairs _grad_buffer gave for gamma and beta.  Fires the callbacks -> what autograd gets
+    for each: the buffer, or None when the gradient is final in the optimizer's flat buffer or nobody asked for it."""
+    out = []
+    for (grad, cb), want in zip(bufs, wanted):
+        if cb is not None:
+            cb()
+            grad = None
+        out.append(grad if want else None)
+    return out
+
+
+def _unpack_dw3x3(dwk, dweight):
+    """KRSC scratch gradient -> the (strided) gradient buffer of a [Cout, Cin, 3, 3] parameter."""
+    sO, sI, sH, sW = dweight.stride()
+    LIB.call("uh_unpack_dw3x3", dwk.data_ptr(), dweight.data_ptr(), sO, sI, sH, sW, dweight.shape[0], dweight.shape[1], _stream())
+
+
+def _grads_for(inputs, **grads):
+    """backward's answer: one entry per forward input, in order, None where no gradient was named."""
+    return tuple(grads.get(k) for k in inputs)
 
 
 # Fuse BatchNorm + ReLU of a DoubleConv's last conv with its consumer (csrc/bn_fused.hip) in training: TAIL_POOL where the
@@ -635,7 +723,7 @@ def pre_fuse_ok(x0: torch.Tensor, mid: int, Cout: int) -> bool:
 # (8 of the 12 plain BatchNorm layers of the bilinear UNet).  UH_FUSE_BNSUM=0 turns it off.
 FUSE_BNSUM = os.environ.get("UH_FUSE_BNSUM", "1") != "0"
 # Layers (image height x channels of the tensor whose BatchNorm sums are formed, e.g. "32x512,512x64") that keep the separate
-# reduce pass although the fusion is on -- per-layer A/B runs (scratch/r4_bnsum_layers.sh) and the default exclusion list.
+# reduce pass although the fusion is on -- per-layer A/B runs and the default exclusion list.
 BNSUM_OFF = {tuple(int(v) for v in k.split("x")) for k in os.environ.get("UH_BNSUM_OFF", "").split(",") if k}
 
 
@@ -652,30 +740,67 @@ class BnSumLink:
         self.dz_version = -1
 
 
+class ConvBnOpts(NamedTuple):
+    """What a ConvBnReluFn / ConvBnReluNarrowFn call carries besides the tensors that can receive a gradient.
+    `tail` (training only): TAIL_POOL -> the node returns (z, maxpool2(z)) (unet_parts.py:32 on top), the backward takes (dskip,
+    dpool) and never materialises their sum; TAIL_HEAD -> returns the fp32 logits of the 1x1 OutConv (the node's head_w
+    [ncls,Cout,1,1], head_b; unet_parts.py:103) and z is never written; TAIL_UP (up_size = (Ho, Wo)) -> returns the bilinear
+    x2 up-sampling of z zero-padded to Ho x Wo (unet_parts.py:70,80,85-88: z's only reader) and z is never written.
+    `bnsum_pub` / `bnsum_use` (BnSumLink): this layer is the first / the second conv of a DoubleConv whose
+    BatchNorm-backward sums may be formed by the second conv's backward-data.
+    `defer` (training, no tail): the BatchNorm + ReLU of THIS layer is left to its consumer -- the node returns (y, coef): the raw
+    conv output standing in for the activation (its gradient is the activation's gradient) and the [scale | shift | mean
+    | rstd] coefficients.  `pre_coef`: x0 is such a raw output; its BatchNorm + ReLU is applied by this layer's conv
+    loaders (forward and backward-weights), the activation is never stored.  `c0_true`: see ConvBnReluNarrowFn."""
+    running_mean: Optional[torch.Tensor] = None
+    running_var: Optional[torch.Tensor] = None
+    num_batches_tracked: Optional[torch.Tensor] = None
+    training: bool = True
+    momentum: float = 0.1
+    eps: float = BN_EPS_DEFAULT
+    tail: int = TAIL_NONE
+    up_size: Optional[Tuple[int, int]] = None
+    defer: bool = False
+    pre_coef: Optional[torch.Tensor] = None
+    bnsum_pub: Optional[BnSumLink] = None
+    bnsum_use: Optional[BnSumLink] = None
+    c0_true: Optional[int] = None
+
+
+def _conv_bn_relu_eval(x0, x1, weight, gamma, beta, o: ConvBnOpts):
+    """inference (model.eval(): evaluate.py:30, predict.py:17): running statistics -> per-channel scale/shift, applied with
+    the ReLU inside the conv epilogue (under plan_images: in the pinned kernel form); nothing is kept for a backward pass."""
+    B, H, W, C0 = x0.shape
+    C1 = 0 if x1 is None else x1.shape[3]
+    Cout = weight.shape[0]
+    cdt = conv_dt(x0, C0, C1, Cout, False)
+    plan = PLAN_IMAGES
+    frag = wfrag_ok(B, H, W, C0, C1, Cout, pixel_ld(x0), pixel_ld_or0(x1), Cout, cdt, plan)
+    wf = pack_w3x3(weight, x0.dtype, False, cdt)[0] if cdt == UH_F32X3 else packed_w3x3_cached(weight, x0.dtype, frag)
+    scale, shift = bn_eval_coeffs_cached(gamma, beta, o.running_mean, o.running_var, o.eps, Cout, Cout)
+    z = torch.empty(B, H, W, Cout, dtype=x0.dtype, device=x0.device)
+    name, images = ("uh_conv3x3_fwd_affine_relu_plan", (B, plan)) if plan else ("uh_conv3x3_fwd_affine_relu", (B,))
+    LIB.call(name, x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1, pixel_ld_or0(x1), wf.data_ptr(), z.data_ptr(), Cout, Cout,
+             scale.data_ptr(), shift.data_ptr(), *images, H, W, conv_flags(cdt, frag), _stream())
+    return z
+
+
+_CBR_INPUTS = ("x0", "x1", "weight", "gamma", "beta", "head_w", "head_b", "opts")
+_EVAL_BACKWARD = "backward through eval-mode BatchNorm is not part of the train path"
+
+
 class ConvBnReluFn(Function):
     """(nn.Conv2d(3x3, pad 1, no bias) -> nn.BatchNorm2d -> nn.ReLU) of unet_parts.py:15-17 / 18-20 as
     one autograd node.  Inputs: x0 (+ optional x1 = second half of the channel concat of
-    unet_parts.py:95, never materialised), the reference-layout parameters, BN buffers.
-
-    `tail` (training only): TAIL_POOL -> returns (z, maxpool2(z)) (unet_parts.py:32 on top), the backward takes
-    (dskip, dpool) and never materialises their sum; TAIL_HEAD -> returns the fp32 logits of the 1x1 OutConv
-    (head_w [ncls,Cout,1,1], head_b; unet_parts.py:103) and z is never written; TAIL_UP (up_size = (Ho, Wo)) -> returns the
-    bilinear x2 up-sampling of z zero-padded to Ho x Wo (unet_parts.py:70,80,85-88: z's only reader) and z is never written."""
+    unet_parts.py:95, never materialised), the reference-layout parameters, the 1x1 head's parameters (TAIL_HEAD, else
+    None) and the options record with the BN buffers (ConvBnOpts)."""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, gamma, beta, running_mean, running_var, num_batches_tracked,
-                training: bool, momentum: float, eps: float, tail: int = 0, head_w=None, head_b=None,
-                defer: bool = False, pre_coef=None, bnsum_pub: Optional[BnSumLink] = None,
-                bnsum_use: Optional[BnSumLink] = None, up_size=None):
-        """`bnsum_pub` / `bnsum_use` (BnSumLink): this layer is the first / the second conv of a DoubleConv whose
-        BatchNorm-backward sums may be formed by the second conv's backward-data.
-        `defer` (training, no tail): the BatchNorm + ReLU of THIS layer is left to its consumer -- returns (y, coef): the raw
-        conv output standing in for the activation (its gradient is the activation's gradient) and the [scale | shift | mean
-        | rstd] coefficients.  `pre_coef`: x0 is such a raw output; its BatchNorm + ReLU is applied by this layer's conv
-        loaders (forward and backward-weights), the activation is never stored."""
+    def forward(ctx, x0, x1, weight, gamma, beta, head_w, head_b, opts: ConvBnOpts):
         _require_gpu(x0, "activation")
         x0 = dense_nhwc(x0)
         x1 = None if x1 is None else dense_nhwc(x1)
+        training, tail, defer, pre_coef = opts.training, opts.tail, opts.defer, opts.pre_coef
         B, H, W, C0 = x0.shape
         C1 = 0 if x1 is None else x1.shape[3]
         Cout, Cin = weight.shape[0], weight.shape[1]
@@ -685,57 +810,34 @@ class ConvBnReluFn(Function):
             raise RuntimeError("ConvBnReluFn: a deferred BatchNorm+ReLU input needs a single-source training-mode layer")
         if defer and (not training or tail != TAIL_NONE):
             raise RuntimeError("ConvBnReluFn: defer is a training-mode option of layers without a fused tail")
-        need_dx = any(ctx.needs_input_grad[:2])
-        cdt = conv_dt(x0, C0, C1, Cout, need_dx and training)
-        # fragment-major filter packs where the LDS-DMA MFMA kernel runs (forward: this call; backward-data: the conv of dy
-        # [B,H,W,Cout] with the transposed filter into dx [B,H,W,Cin])
-        plan = 0 if training else PLAN_IMAGES
-        frag_f = wfrag_ok(B, H, W, C0, C1, Cout, pixel_ld(x0), 0 if x1 is None else pixel_ld(x1), Cout, cdt, plan)
-        frag_d = bool(need_dx and training) and wfrag_ok(B, H, W, Cout, 0, Cin, Cout, 0, Cin, cdt)
-        if training:
-            hit = WEIGHT_PACK.lookup(weight, x0.dtype, frag_f, frag_d) if (WEIGHT_PACK is not None and cdt != UH_F32X3) else None
-            wf, wd = hit if hit is not None else pack_w3x3(weight, x0.dtype, need_dx, cdt, frag_f, frag_d)
-        elif cdt == UH_F32X3:
-            wf, wd = pack_w3x3(weight, x0.dtype, False, cdt)[0], None
-        else:
-            wf, wd = packed_w3x3_cached(weight, x0.dtype, frag_f), None
-        ctx.cdt = cdt
-        ctx.frag_d = frag_d
-        dev = x0.device
-        n = B * H * W
-        if training:
-            if pre_coef is None:
-                y, stats, nslab = conv3x3_fwd(x0, x1, wf, Cout, True, cdt, frag_f)
-            else:
-                y = torch.empty((B, H, W, Cout), dtype=x0.dtype, device=dev)
-                nslab = LIB.query("uh_conv3x3_stat_slabs", B, H, W, C0, Cout, cdt)
-                stats = torch.empty(nslab * (2 * Cout + 2), dtype=torch.float32, device=dev)
-                with _Timed("conv3x3_fwd_mfma", 2.0 * B * H * W * Cout * 9 * C0):
-                    LIB.call("uh_conv3x3_fwd_pre", x0.data_ptr(), C0, pixel_ld(x0), pre_coef.data_ptr(), pre_coef[C0:].data_ptr(),
-                             wf.data_ptr(), y.data_ptr(), Cout, Cout, stats.data_ptr(), B, H, W,
-                             cdt | (UH_WFRAG if frag_f else 0), _stream())
-            coef, n_total = _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, running_mean, running_var,
-                                                   num_batches_tracked, momentum, eps)
-            scale, shift, mean, rstd = coef[:Cout], coef[Cout:2 * Cout], coef[2 * Cout:3 * Cout], coef[3 * Cout:]
-        else:
-            # inference (model.eval(): evaluate.py:30, predict.py:17): running statistics -> per-channel scale/shift,
-            # applied with the ReLU inside the conv epilogue; nothing is kept for a backward pass
-            scale, shift = bn_eval_coeffs_cached(gamma, beta, running_mean, running_var, eps, Cout, Cout)
-            z = torch.empty(B, H, W, Cout, dtype=x0.dtype, device=dev)
-            if plan:
-                LIB.call("uh_conv3x3_fwd_affine_relu_plan", x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1,
-                         pixel_ld(x1) if x1 is not None else 0, wf.data_ptr(), z.data_ptr(), Cout, Cout, scale.data_ptr(),
-                         shift.data_ptr(), B, plan, H, W, cdt | (UH_WFRAG if frag_f else 0), _stream())
-            else:
-                LIB.call("uh_conv3x3_fwd_affine_relu", x0.data_ptr(), C0, pixel_ld(x0), _p(x1), C1,
-                         pixel_ld(x1) if x1 is not None else 0, wf.data_ptr(), z.data_ptr(), Cout, Cout, scale.data_ptr(),
-                         shift.data_ptr(), B, H, W, cdt | (UH_WFRAG if frag_f else 0), _stream())
-            ctx.training = False
+        ctx.training = training
+        if not training:
             if tail != TAIL_NONE:
                 raise RuntimeError("ConvBnReluFn: fused tails are a training-mode path")
-            return z
+            return _conv_bn_relu_eval(x0, x1, weight, gamma, beta, opts)
+        need_dx = any(ctx.needs_input_grad[:2])
+        cdt = conv_dt(x0, C0, C1, Cout, need_dx)
+        # fragment-major filter packs where the LDS-DMA MFMA kernel runs (forward: this call; backward-data: the conv of dy
+        # [B,H,W,Cout] with the transposed filter into dx [B,H,W,Cin])
+        frag_f = wfrag_ok(B, H, W, C0, C1, Cout, pixel_ld(x0), pixel_ld_or0(x1), Cout, cdt)
+        frag_d = need_dx and wfrag_ok(B, H, W, Cout, 0, Cin, Cout, 0, Cin, cdt)
+        hit = WEIGHT_PACK.lookup(weight, x0.dtype, frag_f, frag_d) if (WEIGHT_PACK is not None and cdt != UH_F32X3) else None
+        wf, wd = hit if hit is not None else pack_w3x3(weight, x0.dtype, need_dx, cdt, frag_f, frag_d)
+        ctx.cdt, ctx.frag_d = cdt, frag_d
+        dev = x0.device
+        n = B * H * W
+        if pre_coef is None:
+            y, stats, nslab = conv3x3_fwd(x0, x1, wf, Cout, True, cdt, frag_f)
+        else:
+            y = torch.empty((B, H, W, Cout), dtype=x0.dtype, device=dev)
+            nslab = LIB.query("uh_conv3x3_stat_slabs", B, H, W, C0, Cout, cdt)
+            stats = torch.empty(nslab * (2 * Cout + 2), dtype=torch.float32, device=dev)
+            with _Timed("conv3x3_fwd_mfma", 2.0 * B * H * W * Cout * 9 * C0):
+                LIB.call("uh_conv3x3_fwd_pre", x0.data_ptr(), C0, pixel_ld(x0), pre_coef.data_ptr(), pre_coef[C0:].data_ptr(),
+                         wf.data_ptr(), y.data_ptr(), Cout, Cout, stats.data_ptr(), B, H, W, conv_flags(cdt, frag_f), _stream())
+        coef, n_total = _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, opts)
+        scale, shift, mean, rstd = coef_views(coef)
         ctx.bn_params = (gamma, beta)
-        ctx.training = training
         ctx.dims = (B, H, W, C0, C1, Cout)
         ctx.n_total = n_total
         ctx.sync_bn = SYNC_BN                    # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
@@ -743,109 +845,99 @@ class ConvBnReluFn(Function):
         ctx.pre = pre_coef is not None
         ctx.bnsum_pub = ctx.bnsum_use = None
         if FUSE_BNSUM and x0.dtype == torch.bfloat16 and cdt == UH_BF16:
+            bnsum_pub, bnsum_use = opts.bnsum_pub, opts.bnsum_use
             if bnsum_pub is not None and tail == TAIL_NONE and not defer:
                 bnsum_pub.y, bnsum_pub.coef = y, coef
                 bnsum_pub.partials = bnsum_pub.dz = None      # (left over when a previous backward never reached this layer)
                 ctx.bnsum_pub = bnsum_pub
             if bnsum_use is not None and bnsum_use.y is not None and x1 is None and pre_coef is None:
                 ctx.bnsum_use = bnsum_use
-        if pre_coef is not None:
-            x1 = pre_coef                      # rides in the saved-tensor slot of the (absent) second source
+        # (pre_coef rides in the saved-tensor slot of the absent second source)
+        saved = [x0, x1 if pre_coef is None else pre_coef, y, coef, wd, weight]
         if defer:
-            ctx.save_for_backward(x0, x1, y, coef, wd, weight)
             ctx.mark_non_differentiable(coef)
-            return y, coef
-        if tail == TAIL_HEAD:
+            out = (y, coef)
+        elif tail == TAIL_HEAD:
             ncls = head_w.shape[0]
             hw2 = head_w.reshape(ncls, Cout).contiguous().float()
             hb2 = head_b.contiguous().float()
             logits = torch.empty((B, H, W, ncls), dtype=torch.float32, device=dev)
             LIB.call("uh_bn_relu_head_fwd", y.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), hw2.data_ptr(),
                      hb2.data_ptr(), logits.data_ptr(), n, Cout, ncls, _dt(y), _stream())
-            ctx.save_for_backward(x0, x1, y, coef, wd, weight, hw2)
+            saved.append(hw2)
             ctx.head_params = (head_w, head_b)
-            return logits
-        if tail == TAIL_UP:
-            Ho, Wo = up_size
+            out = logits
+        elif tail == TAIL_UP:
+            Ho, Wo = opts.up_size
             pt, pl = _pad_geometry(H, W, Ho, Wo)
             u = torch.empty((B, Ho, Wo, Cout), dtype=y.dtype, device=dev)
             LIB.call("uh_bn_relu_upsample2x_fwd", y.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), u.data_ptr(), Cout,
                      B, H, W, Cout, Ho, Wo, pt, pl, _dt(y), _stream())
             ctx.up = (Ho, Wo, pt, pl)
-            ctx.save_for_backward(x0, x1, y, coef, wd, weight)
-            return u
-        z = torch.empty_like(y)
-        if tail == TAIL_POOL:
+            out = u
+        elif tail == TAIL_POOL:
+            z = torch.empty_like(y)
             pooled = torch.empty((B, H // 2, W // 2, Cout), dtype=y.dtype, device=dev)
             LIB.call("uh_bn_relu_pool_apply", y.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), z.data_ptr(), Cout,
                      pooled.data_ptr(), Cout, B, H, W, Cout, _dt(y), _stream())
-            ctx.save_for_backward(x0, x1, y, coef, wd, weight)
             ctx.set_materialize_grads(False)
-            return z, pooled
-        LIB.call("uh_bn_relu_apply", y.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), z.data_ptr(), Cout,
-                 n, Cout, _dt(y), _stream())
-        ctx.save_for_backward(x0, x1, y, coef, wd, weight)
-        return z
+            out = (z, pooled)
+        else:
+            out = torch.empty_like(y)
+            LIB.call("uh_bn_relu_apply", y.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), out.data_ptr(), Cout,
+                     n, Cout, _dt(y), _stream())
+        ctx.save_for_backward(*saved)
+        return out
 
     @staticmethod
     def backward(ctx, *grads):
-        tail = ctx.tail if ctx.training else TAIL_NONE
-        hw2 = None
-        if tail == TAIL_HEAD:
-            x0, x1, y, coef, wd, weight, hw2 = ctx.saved_tensors
-        else:
-            x0, x1, y, coef, wd, weight = ctx.saved_tensors
-        B, H, W, C0, C1, Cout = ctx.dims
         if not ctx.training:
-            raise RuntimeError("backward through eval-mode BatchNorm is not part of the train path")
-        pre_coef = None
-        if ctx.pre:
-            pre_coef, x1 = x1, None
+            raise RuntimeError(_EVAL_BACKWARD)
+        need = dict(zip(_CBR_INPUTS, ctx.needs_input_grad))
+        tail = ctx.tail
+        x0, x1, y, coef, wd, weight, *hw2 = ctx.saved_tensors          # (hw2: the head tail's fp32 [ncls, Cout] filter)
+        B, H, W, C0, C1, Cout = ctx.dims
+        pre_coef, x1 = (x1, None) if ctx.pre else (None, x1)
         Cin = C0 + C1
         n = B * H * W
         dev = y.device
-        scale, shift, mean, rstd = coef[:Cout], coef[Cout:2 * Cout], coef[2 * Cout:3 * Cout], coef[3 * Cout:]
+        scale, shift, mean, rstd = coef_views(coef)
         dt = _dt(y)
         nblk = LIB.query("uh_bn_bwd_nblk", n, Cout)
         partials = torch.empty(nblk * 2 * Cout, dtype=torch.float32, device=dev)
         bn_args = (y.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr())
         dhead = (None, None)
         # The gradient of z: a tensor (no tail), dlogits . head_w (head tail) or dskip + route(dpool) (pool tail) -- the
-        # last two are rebuilt inside both BatchNorm passes instead of being stored.  `reduce()` writes the per-block
+        # last two are rebuilt inside both BatchNorm passes instead of being stored.  The reduce pass writes the per-block
         # sums, `apply(...)` finishes (or is handed) the per-channel sums and writes dy.
         if tail == TAIL_HEAD:
             dl = grads[0].float().contiguous()
+            hw2, = hw2
             ncls = hw2.shape[0]
             head_w, head_b = ctx.head_params
-            (dwb, cb_hw), (dbb, cb_hb) = _grad_buffer(head_w, ctx.needs_input_grad[12]), _grad_buffer(head_b, ctx.needs_input_grad[13])
+            (dwb, cb_hw), (dbb, cb_hb) = _grad_buffer(head_w, need["head_w"]), _grad_buffer(head_b, need["head_b"])
             direct = cb_hw is not None and cb_hb is not None and dwb.stride(0) == Cout and dwb.stride(1) == 1 and \
                 dbb.is_contiguous() and dwb.dtype == torch.float32 and dbb.dtype == torch.float32
             dhw = dwb if direct else torch.empty((ncls, Cout), dtype=torch.float32, device=dev)
             dhb = dbb if direct else torch.empty(ncls, dtype=torch.float32, device=dev)
             nbytes = LIB.query("uh_bn_relu_head_bwd_ws_bytes", n, Cout, ncls)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-
-            def reduce():
-                LIB.call("uh_bn_relu_head_bwd_reduce", dl.data_ptr(), hw2.data_ptr(), *bn_args, partials.data_ptr(),
-                         dhw.data_ptr(), dhb.data_ptr(), ws.data_ptr(), nbytes, n, Cout, ncls, dt, _stream())
-                if direct:
-                    cb_hw()
-                    cb_hb()
+            LIB.call("uh_bn_relu_head_bwd_reduce", dl.data_ptr(), hw2.data_ptr(), *bn_args, partials.data_ptr(),
+                     dhw.data_ptr(), dhb.data_ptr(), ws.data_ptr(), nbytes, n, Cout, ncls, dt, _stream())
+            if direct:
+                cb_hw()
+                cb_hb()
 
             def apply(part_ptr, nb, dg_ptr, db_ptr, n_total):
                 LIB.call("uh_bn_relu_head_bwd_apply", dl.data_ptr(), hw2.data_ptr(), *bn_args, part_ptr, nb, dg_ptr, db_ptr,
                          dy.data_ptr(), Cout, n, n_total, Cout, ncls, dt, _stream())
-            dhead = (None, None) if direct else (dhw.view(head_w.shape) if ctx.needs_input_grad[12] else None,
-                                                 dhb if ctx.needs_input_grad[13] else None)
+            dhead = (None, None) if direct else (dhw.view(head_w.shape) if need["head_w"] else None,
+                                                 dhb if need["head_b"] else None)
         elif tail == TAIL_POOL and grads[1] is not None:
             dskip, dpool = grads
-            dpool = dense_nhwc(dpool if dpool.dtype == y.dtype else dpool.to(y.dtype))
-            if dskip is not None:
-                dskip = dense_nhwc(dskip if dskip.dtype == y.dtype else dskip.to(y.dtype))
-            sk = (_p(dskip), 0 if dskip is None else pixel_ld(dskip), dpool.data_ptr(), pixel_ld(dpool))
-
-            def reduce():
-                LIB.call("uh_bn_relu_pool_bwd_reduce", *sk, *bn_args, partials.data_ptr(), B, H, W, Cout, dt, _stream())
+            dskip, dpool = None if dskip is None else grad_like(dskip, y), grad_like(dpool, y)
+            sk = (_p(dskip), pixel_ld_or0(dskip), dpool.data_ptr(), pixel_ld(dpool))
+            LIB.call("uh_bn_relu_pool_bwd_reduce", *sk, *bn_args, partials.data_ptr(), B, H, W, Cout, dt, _stream())
 
             def apply(part_ptr, nb, dg_ptr, db_ptr, n_total):
                 LIB.call("uh_bn_relu_pool_bwd_apply", *sk, *bn_args, part_ptr, nb, dg_ptr, db_ptr, dy.data_ptr(), Cout,
@@ -853,8 +945,8 @@ class ConvBnReluFn(Function):
         else:
             dz = grads[0]
             if dz is None:          # pool tail whose outputs were both unused
-                return (None,) * 19
-            dz = dense_nhwc(dz if dz.dtype == y.dtype else dz.to(y.dtype))
+                return _grads_for(_CBR_INPUTS)
+            dz = grad_like(dz, y)
             if tail == TAIL_UP:     # the gradient arrives for the up-sampled tensor: transpose of the interpolation first
                 Ho, Wo, pt, pl = ctx.up
                 du, dz = dz, torch.empty((B, H, W, Cout), dtype=y.dtype, device=dev)
@@ -871,39 +963,23 @@ class ConvBnReluFn(Function):
                 else:
                     link = None
                 ctx.bnsum_pub.partials = ctx.bnsum_pub.dz = ctx.bnsum_pub.y = ctx.bnsum_pub.coef = None
-            fused_sums = link is not None
-
-            def reduce():
-                if not fused_sums:
-                    LIB.call("uh_bn_relu_bwd_reduce", dz.data_ptr(), pixel_ld(dz), *bn_args, partials.data_ptr(), n, Cout, dt,
-                             _stream())
+            if link is None:
+                LIB.call("uh_bn_relu_bwd_reduce", dz.data_ptr(), pixel_ld(dz), *bn_args, partials.data_ptr(), n, Cout, dt, _stream())
 
             def apply(part_ptr, nb, dg_ptr, db_ptr, n_total):
                 LIB.call("uh_bn_relu_bwd_apply", dz.data_ptr(), pixel_ld(dz), *bn_args, part_ptr, nb, dg_ptr, db_ptr,
                          dy.data_ptr(), Cout, n, n_total, Cout, dt, _stream())
-        reduce()
-        gamma_p, beta_p = ctx.bn_params
-        (dgamma, cb_g), (dbeta, cb_b) = _grad_buffer(gamma_p, ctx.needs_input_grad[3]), _grad_buffer(beta_p, ctx.needs_input_grad[4])
+        bn_wanted = (need["gamma"], need["beta"])
+        bn_bufs = [_grad_buffer(p, w) for p, w in zip(ctx.bn_params, bn_wanted)]
         dy = torch.empty_like(y)
-        if ctx.sync_bn is None:
-            apply(partials.data_ptr(), nblk, dgamma.data_ptr(), dbeta.data_ptr(), 0)
-        else:
-            # SyncBN: the parameter gradients stay LOCAL sums (the gradient all-reduce SUMS them like every other
-            # gradient: the loss is already normalised by the global batch); the dx formula needs the GLOBAL sums and the
-            # global pixel count
-            import torch.distributed as dist
-            LIB.call("uh_bn_bwd_finalize", partials.data_ptr(), nblk, Cout, dgamma.data_ptr(), dbeta.data_ptr(), _stream())
-            glob = torch.cat([dgamma.reshape(-1), dbeta.reshape(-1)])
-            dist.all_reduce(glob, op=dist.ReduceOp.SUM, group=ctx.sync_bn[0])
-            apply(None, 0, glob[:Cout].data_ptr(), glob[Cout:].data_ptr(), ctx.n_total)
+        _bn_backward_finish(partials, nblk, Cout, bn_bufs[0][0], bn_bufs[1][0], ctx.sync_bn, ctx.n_total, apply)
         # backward-data first: it is the only consumer on the critical path (the next layer's BatchNorm backward waits
         # for it).  Backward-weights then goes to the side stream BEHIND it, so that it runs beside the HBM-bound
         # kernels of the layers that follow (BatchNorm backward, pool / upsample backward) instead of beside this
         # layer's own MFMA-bound backward-data.
         dx0 = dx1 = None
-        if wd is not None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
-            use = ctx.bnsum_use
-            rows = 0
+        if wd is not None and (need["x0"] or need["x1"]):
+            use, rows = ctx.bnsum_use, 0
             if use is not None and use.y is not None and use.y.shape == (B, H, W, Cin) and use.y.is_contiguous() and \
                     (H, Cin) not in BNSUM_OFF:
                 rows = LIB.query("uh_conv3x3_dgrad_bnsum_rows", B, H, W, Cout, Cin, Cout, Cin, Cin, ctx.cdt)
@@ -916,15 +992,14 @@ class ConvBnReluFn(Function):
                 with _Timed("conv3x3_dgrad_bnsum_mfma", 2.0 * B * H * W * Cin * 9 * Cout, ("dgrad", B, H, W, Cout, Cin)):
                     LIB.call("uh_conv3x3_dgrad_bnsum", dy.data_ptr(), Cout, Cout, wd.data_ptr(), dx.data_ptr(), Cin, Cin,
                              use.y.data_ptr(), Cin, use.coef.data_ptr(), bsum.data_ptr(), B, H, W,
-                             ctx.cdt | (UH_WFRAG if ctx.frag_d else 0), _stream())
+                             conv_flags(ctx.cdt, ctx.frag_d), _stream())
                 use.partials, use.rows, use.dz, use.dz_version = bsum, rows, dx, dx._version
             else:
                 dx, _, _ = conv3x3_fwd(dy, None, wd, Cin, False, ctx.cdt, ctx.frag_d)
-            dx0 = dx[..., :C0] if ctx.needs_input_grad[0] else None
-            dx1 = dx[..., C0:] if (x1 is not None and ctx.needs_input_grad[1]) else None
+            dx0 = dx[..., :C0] if need["x0"] else None
+            dx1 = dx[..., C0:] if (x1 is not None and need["x1"]) else None
         # weight gradient: straight into the parameter's layout when that IS KRSC (channels_last weights)
-        dweight = None
-        side_done = None
+        dweight = side_done = None
 
         def run_wgrad(out_, defer_cb=None):
             if pre_coef is None:
@@ -932,7 +1007,7 @@ class ConvBnReluFn(Function):
             conv3x3_wgrad_pre(dy, x0, pre_coef, out_)
             return False
 
-        if ctx.needs_input_grad[2]:
+        if need["weight"]:
             dweight, cb_w = _grad_buffer(weight)
             if cb_w is not None and WGRAD_STREAM is not None and _is_krsc_dense(weight):
                 side = WGRAD_STREAM
@@ -955,22 +1030,12 @@ class ConvBnReluFn(Function):
             else:
                 dwk = torch.empty(Cout * 9 * Cin, dtype=torch.float32, device=dev)
                 run_wgrad(dwk)
-                sO, sI, sH, sW = dweight.stride()
-                LIB.call("uh_unpack_dw3x3", dwk.data_ptr(), dweight.data_ptr(), sO, sI, sH, sW, Cout, Cin, _stream())
+                _unpack_dw3x3(dwk, dweight)
             if cb_w is not None:
                 cb_w(side_done)
                 dweight = None
-        if cb_g is not None:
-            cb_g()
-            dgamma = None
-        if cb_b is not None:
-            cb_b()
-            dbeta = None
-        if not ctx.needs_input_grad[3]:
-            dgamma = None
-        if not ctx.needs_input_grad[4]:
-            dbeta = None
-        return dx0, dx1, dweight, dgamma, dbeta, None, None, None, None, None, None, None, dhead[0], dhead[1], None, None, None, None, None
+        dgamma, dbeta = _bn_param_grads(bn_bufs, bn_wanted)
+        return _grads_for(_CBR_INPUTS, x0=dx0, x1=dx1, weight=dweight, gamma=dgamma, beta=dbeta, head_w=dhead[0], head_b=dhead[1])
 
 
 # ----------------------------------------------------------------------------- the stem, output recomputed
@@ -984,35 +1049,6 @@ STEM_RECOMPUTE_MAX_CIN = 1
 def stem_recompute_ok(x0: torch.Tensor, Cin: int, Cout: int) -> bool:
     return bool(STEM_RECOMPUTE and x0.dtype == torch.bfloat16 and Cin <= STEM_RECOMPUTE_MAX_CIN and x0.shape[-1] == Cin and
                 LIB.query("uh_stem_ok", Cin, Cout, UH_BF16) and x0.shape[0] * x0.shape[1] * x0.shape[2] < 2 ** 31)
-
-
-def _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps):
-    """Per-channel [scale | shift | mean | rstd] from the conv kernels' statistics rows (+ running statistics /
-    num_batches_tracked update, + the cross-rank merge under SyncBN).  -> (coef, n_total)"""
-    global BN_STATS_EPOCH
-    BN_STATS_EPOCH += 1
-    dev = stats.device
-    coef = torch.empty(4 * Cout, dtype=torch.float32, device=dev)
-    scale, shift, mean, rstd = coef[:Cout], coef[Cout:2 * Cout], coef[2 * Cout:3 * Cout], coef[3 * Cout:]
-    g32 = gamma if gamma.dtype == torch.float32 else gamma.float()
-    b32 = beta if beta.dtype == torch.float32 else beta.float()
-    nbt = num_batches_tracked
-    fused_nbt = nbt is not None and nbt.is_cuda and nbt.dtype == torch.int64
-    nbt_ptr = nbt.data_ptr() if fused_nbt else None
-    n_total = n
-    if SYNC_BN is None:
-        LIB.call("uh_bn_finalize", stats.data_ptr(), nslab, Cout, n, g32.data_ptr(), b32.data_ptr(), _p(running_mean),
-                 _p(running_var), nbt_ptr, float(momentum), float(eps), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                 rstd.data_ptr(), None, _stream())
-    else:
-        m2 = torch.empty(Cout, dtype=torch.float32, device=dev)
-        LIB.call("uh_bn_finalize", stats.data_ptr(), nslab, Cout, n, g32.data_ptr(), b32.data_ptr(), None, None, None,
-                 float(momentum), float(eps), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                 m2.data_ptr(), _stream())
-        n_total = _sync_bn_forward(coef, m2, n, Cout, g32, b32, running_mean, running_var, nbt_ptr, momentum, eps)
-    if nbt is not None and not fused_nbt:
-        nbt.add_(1)
-    return coef, n_total
 
 
 class StemConvBnReluFn(Function):
@@ -1036,8 +1072,8 @@ class StemConvBnReluFn(Function):
         stats = torch.empty(nslab * (2 * Cout + 2), dtype=torch.float32, device=dev)
         with _Timed("conv3x3_fwd_stem", 2.0 * n * Cout * 9 * Cin):
             LIB.call("uh_stem_stats", x0.data_ptr(), Cin, pixel_ld(x0), wf.data_ptr(), stats.data_ptr(), B, H, W, UH_BF16, _stream())
-        coef, n_total = _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, running_mean, running_var,
-                                               num_batches_tracked, momentum, eps)
+        coef, n_total = _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, ConvBnOpts(
+            running_mean, running_var, num_batches_tracked, momentum=momentum, eps=eps))
         z = torch.empty((B, H, W, Cout), dtype=x0.dtype, device=dev)
         with _Timed("conv3x3_fwd_stem", 2.0 * n * Cout * 9 * Cin):
             LIB.call("uh_stem_bn_relu_fwd", x0.data_ptr(), Cin, pixel_ld(x0), wf.data_ptr(), coef.data_ptr(), coef[Cout:].data_ptr(),
@@ -1054,22 +1090,20 @@ class StemConvBnReluFn(Function):
         x0, coef, wf, weight = ctx.saved_tensors
         B, H, W, Cin, Cout = ctx.dims
         dev = x0.device
-        dz = dense_nhwc(dz if dz.dtype == x0.dtype else dz.to(x0.dtype))
-        scale, shift, mean, rstd = coef[:Cout], coef[Cout:2 * Cout], coef[2 * Cout:3 * Cout], coef[3 * Cout:]
+        dz = grad_like(dz, x0)
+        scale, shift, mean, rstd = coef_views(coef)
         args = (dz.data_ptr(), pixel_ld(dz), x0.data_ptr(), Cin, pixel_ld(x0), wf.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                 mean.data_ptr(), rstd.data_ptr())
         nblk = LIB.query("uh_stem_nblk", B, H, W)
         partials = torch.empty(nblk * 2 * Cout, dtype=torch.float32, device=dev)
         LIB.call("uh_stem_bn_relu_bwd_reduce", *args, partials.data_ptr(), B, H, W, UH_BF16, _stream())
-        gamma_p, beta_p = ctx.bn_params
-        (dgamma, cb_g), (dbeta, cb_b) = _grad_buffer(gamma_p, ctx.needs_input_grad[2]), _grad_buffer(beta_p, ctx.needs_input_grad[3])
-        LIB.call("uh_bn_bwd_finalize", partials.data_ptr(), nblk, Cout, dgamma.data_ptr(), dbeta.data_ptr(), _stream())
-        sums_g, sums_b = dgamma, dbeta
-        if ctx.sync_bn is not None:             # the dy formula needs the GLOBAL sums; the parameter gradients stay local
-            import torch.distributed as dist
-            glob = torch.cat([dgamma.reshape(-1), dbeta.reshape(-1)])
-            dist.all_reduce(glob, op=dist.ReduceOp.SUM, group=ctx.sync_bn[0])
-            sums_g, sums_b = glob[:Cout], glob[Cout:]
+        bn_wanted = ctx.needs_input_grad[2:4]
+        bn_bufs = [_grad_buffer(p, w) for p, w in zip(ctx.bn_params, bn_wanted)]
+        sums_g, sums_b = bn_bufs[0][0], bn_bufs[1][0]
+        # (this node always finalizes first: the sums are an argument of its backward-weights kernel)
+        LIB.call("uh_bn_bwd_finalize", partials.data_ptr(), nblk, Cout, sums_g.data_ptr(), sums_b.data_ptr(), _stream())
+        if ctx.sync_bn is not None:
+            sums_g, sums_b = _bn_global_sums(sums_g, sums_b, Cout, ctx.sync_bn)
         dweight = None
         if ctx.needs_input_grad[1]:
             dweight, cb_w = _grad_buffer(weight)
@@ -1081,21 +1115,11 @@ class StemConvBnReluFn(Function):
                 LIB.call("uh_stem_bn_relu_bwd_wgrad", *args, sums_g.data_ptr(), sums_b.data_ptr(), ctx.n_total, dwk.data_ptr(),
                          ws.data_ptr(), nbytes, B, H, W, UH_BF16, _stream())
             if not direct:
-                sO, sI, sH, sW = dweight.stride()
-                LIB.call("uh_unpack_dw3x3", dwk.data_ptr(), dweight.data_ptr(), sO, sI, sH, sW, Cout, Cin, _stream())
+                _unpack_dw3x3(dwk, dweight)
             if cb_w is not None:
                 cb_w(None)
                 dweight = None
-        if cb_g is not None:
-            cb_g()
-            dgamma = None
-        if cb_b is not None:
-            cb_b()
-            dbeta = None
-        if not ctx.needs_input_grad[2]:
-            dgamma = None
-        if not ctx.needs_input_grad[3]:
-            dbeta = None
+        dgamma, dbeta = _bn_param_grads(bn_bufs, bn_wanted)
         return None, dweight, dgamma, dbeta, None, None, None, None, None
 
 
@@ -1121,34 +1145,59 @@ def narrow_ok(x0: torch.Tensor, x1: Optional[torch.Tensor], Cout: int) -> bool:
     return Cout % vec == 0
 
 
+def _narrow_dims(x0, x1, Cout):
+    """-> stored channels of both sources, then the 64-aligned counts the layer is computed at (sources, output)."""
+    C0m, C1m = x0.shape[3], 0 if x1 is None else x1.shape[3]
+    return C0m, C1m, _rup64(C0m), _rup64(C1m) if C1m else 0, _rup64(Cout)
+
+
+def _narrow_fwd(x0, x1, wf, out, stats, scale, shift, cdt, plan=0):
+    """uh_conv3x3_fwd_narrow(_plan) of a small-width layer into `out`: statistics rows (training) or the eval-mode scale /
+    shift + ReLU in the epilogue."""
+    B, H, W, Cout = out.shape
+    C0m, C1m, Cp0, Cp1, Cop = _narrow_dims(x0, x1, Cout)
+    name, images = ("uh_conv3x3_fwd_narrow_plan", (B, plan)) if plan else ("uh_conv3x3_fwd_narrow", (B,))
+    with _Timed("conv3x3_fwd_narrow", 2.0 * B * H * W * Cop * 9 * (Cp0 + Cp1)):
+        LIB.call(name, x0.data_ptr(), Cp0, C0m, pixel_ld(x0), _p(x1), Cp1, C1m, pixel_ld_or0(x1), wf.data_ptr(),
+                 out.data_ptr(), Cout, Cop, Cout, _p(stats), _p(scale), _p(shift), *images, H, W, cdt, _stream())
+
+
+def _conv_bn_relu_narrow_eval(x0, x1, wf, cdt, Cout, gamma, beta, o: ConvBnOpts):
+    B, H, W, _ = x0.shape
+    # scale / shift are read in 16-byte pieces for every padded channel group: Cop entries, the first Cout real
+    scale, shift = bn_eval_coeffs_cached(gamma, beta, o.running_mean, o.running_var, o.eps, Cout, _rup64(Cout))
+    z = torch.empty(B, H, W, Cout, dtype=x0.dtype, device=x0.device)
+    _narrow_fwd(x0, x1, wf, z, None, scale, shift, cdt, PLAN_IMAGES)
+    return z
+
+
+_NARROW_INPUTS = ("x0", "x1", "weight", "gamma", "beta", "opts")
+
+
 class ConvBnReluNarrowFn(Function):
     """(Conv2d 3x3 -> BatchNorm2d -> ReLU) of unet_parts.py:15-20 for the small-width models (UNet_S / UNet_T,
     unet_model.py:52-126): COMPUTED as the next 64-aligned layer -- zero filters / unit gamma in the padding, so the
     MFMA kernels of the full-width UNet apply -- while every activation in HBM (x, raw conv output, z and their
     gradients) keeps its real channel count: the conv kernels read channels beyond the stored count as zeros and never
-    write them (uh_conv3x3_fwd_narrow / uh_conv3x3_wgrad_narrow).  `c0_true`: x0 may itself carry zero channels up to
+    write them (uh_conv3x3_fwd_narrow / uh_conv3x3_wgrad_narrow).  `opts.c0_true`: x0 may itself carry zero channels up to
     a 16-byte piece (the 1- or 3-channel input image); only its first c0_true channels meet filter taps."""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, gamma, beta, running_mean, running_var, num_batches_tracked,
-                training: bool, momentum: float, eps: float, c0_true: int):
+    def forward(ctx, x0, x1, weight, gamma, beta, opts: ConvBnOpts):
         _require_gpu(x0, "activation")
         x0 = dense_nhwc(x0)
         x1 = None if x1 is None else dense_nhwc(x1)
-        B, H, W, C0m = x0.shape
-        C1m = 0 if x1 is None else x1.shape[3]
+        training, c0_true = opts.training, opts.c0_true
+        B, H, W, _ = x0.shape
         Cout, Cin = weight.shape[0], weight.shape[1]
+        C0m, C1m, Cp0, Cp1, Cop = _narrow_dims(x0, x1, Cout)
         if Cin != c0_true + C1m or c0_true > C0m:
             raise RuntimeError(f"conv expects {Cin} input channels, got {c0_true}+{C1m}")
         if not narrow_ok(x0, x1, Cout):
             raise RuntimeError("narrow conv: stored channel counts / strides must be multiples of 16 bytes")
-        Cp0, Cp1, Cop = _rup64(C0m), _rup64(C1m) if C1m else 0, _rup64(Cout)
-        Cinp = Cp0 + Cp1
-        dev = x0.device
-        need_dx = (ctx.needs_input_grad[0], x1 is not None and ctx.needs_input_grad[1])
-        cdt = conv_dt(x0, Cp0, Cp1, Cop, any(need_dx) and training)
-        single = x1 is None
-        want_wd = (training and need_dx[0], training and need_dx[1])
+        Cinp, dev, single = Cp0 + Cp1, x0.device, x1 is None
+        want_wd = (training and ctx.needs_input_grad[0], training and not single and ctx.needs_input_grad[1])
+        cdt = conv_dt(x0, Cp0, Cp1, Cop, any(want_wd))
         w32 = weight if weight.dtype == torch.float32 else weight.float()
         wd0 = wd1 = None
         if cdt == UH_F32X3:
@@ -1173,59 +1222,23 @@ class ConvBnReluNarrowFn(Function):
             if wd is not None:
                 wd0 = wd[:Cp0 * 9 * Cop] if want_wd[0] else None
                 wd1 = wd[Cp0 * 9 * Cop:] if want_wd[1] else None
-        g32 = gamma if gamma.dtype == torch.float32 else gamma.float()
-        b32 = beta if beta.dtype == torch.float32 else beta.float()
-        n = B * H * W
-        ld0, ld1 = pixel_ld(x0), 0 if x1 is None else pixel_ld(x1)
-        flops = 2.0 * n * Cop * 9 * Cinp
+        ctx.training = training
         if not training:
-            # scale / shift are read in 16-byte pieces for every padded channel group: Cop entries, the first Cout real
-            scale, shift = bn_eval_coeffs_cached(gamma, beta, running_mean, running_var, eps, Cout, Cop)
-            z = torch.empty(B, H, W, Cout, dtype=x0.dtype, device=dev)
-            with _Timed("conv3x3_fwd_narrow", flops):
-                if PLAN_IMAGES:
-                    LIB.call("uh_conv3x3_fwd_narrow_plan", x0.data_ptr(), Cp0, C0m, ld0, _p(x1), Cp1, C1m, ld1, wf.data_ptr(),
-                             z.data_ptr(), Cout, Cop, Cout, None, scale.data_ptr(), shift.data_ptr(), B, PLAN_IMAGES, H, W, cdt,
-                             _stream())
-                else:
-                    LIB.call("uh_conv3x3_fwd_narrow", x0.data_ptr(), Cp0, C0m, ld0, _p(x1), Cp1, C1m, ld1, wf.data_ptr(),
-                             z.data_ptr(), Cout, Cop, Cout, None, scale.data_ptr(), shift.data_ptr(), B, H, W, cdt, _stream())
-            ctx.training = False
-            return z
-        coef = torch.empty(4 * Cout, dtype=torch.float32, device=dev)
-        scale, shift, mean, rstd = coef[:Cout], coef[Cout:2 * Cout], coef[2 * Cout:3 * Cout], coef[3 * Cout:]
-        global BN_STATS_EPOCH
-        BN_STATS_EPOCH += 1                       # running statistics are about to change under torch's feet
+            return _conv_bn_relu_narrow_eval(x0, x1, wf, cdt, Cout, gamma, beta, opts)
+        n = B * H * W
         y = torch.empty(B, H, W, Cout, dtype=x0.dtype, device=dev)
         nslab = LIB.query("uh_conv3x3_stat_slabs", B, H, W, Cinp, Cop, cdt)
         stats = torch.empty(nslab * (2 * Cop + 2), dtype=torch.float32, device=dev)
-        with _Timed("conv3x3_fwd_narrow", flops):
-            LIB.call("uh_conv3x3_fwd_narrow", x0.data_ptr(), Cp0, C0m, ld0, _p(x1), Cp1, C1m, ld1, wf.data_ptr(),
-                     y.data_ptr(), Cout, Cop, Cout, stats.data_ptr(), None, None, B, H, W, cdt, _stream())
-        nbt = num_batches_tracked
-        fused_nbt = nbt is not None and nbt.is_cuda and nbt.dtype == torch.int64
-        nbt_ptr = nbt.data_ptr() if fused_nbt else None
-        n_total = n
+        _narrow_fwd(x0, x1, wf, y, stats, None, None, cdt)
         # statistics rows are Cop channels wide (the conv is computed for the padded layer); only the Cout real ones count
-        if SYNC_BN is None:
-            LIB.call("uh_bn_finalize_ld", stats.data_ptr(), nslab, Cop, Cout, n, g32.data_ptr(), b32.data_ptr(),
-                     _p(running_mean), _p(running_var), nbt_ptr, float(momentum), float(eps), scale.data_ptr(),
-                     shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), None, _stream())
-        else:
-            m2 = torch.empty(Cout, dtype=torch.float32, device=dev)
-            LIB.call("uh_bn_finalize_ld", stats.data_ptr(), nslab, Cop, Cout, n, g32.data_ptr(), b32.data_ptr(), None, None,
-                     None, float(momentum), float(eps), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                     m2.data_ptr(), _stream())
-            n_total = _sync_bn_forward(coef, m2, n, Cout, g32, b32, running_mean, running_var, nbt_ptr, momentum, eps)
-        if nbt is not None and not fused_nbt:
-            nbt.add_(1)
+        coef, n_total = _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, opts, ldc=Cop)
+        scale, shift, _, _ = coef_views(coef)
         z = torch.empty_like(y)
         LIB.call("uh_bn_relu_apply", y.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), z.data_ptr(), Cout, n, Cout,
                  _dt(y), _stream())
         ctx.save_for_backward(x0, x1, y, coef, wd0, wd1, weight)
         ctx.bn_params = (gamma, beta)
-        ctx.training = True
-        ctx.dims = (B, H, W, C0m, C1m, Cout, c0_true)
+        ctx.dims = (B, H, W, Cout, c0_true)
         ctx.cdt = cdt
         ctx.n_total = n_total
         ctx.sync_bn = SYNC_BN                    # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
@@ -1234,35 +1247,29 @@ class ConvBnReluNarrowFn(Function):
     @staticmethod
     def backward(ctx, dz):
         if not ctx.training:
-            raise RuntimeError("backward through eval-mode BatchNorm is not part of the train path")
+            raise RuntimeError(_EVAL_BACKWARD)
+        need = dict(zip(_NARROW_INPUTS, ctx.needs_input_grad))
         x0, x1, y, coef, wd0, wd1, weight = ctx.saved_tensors
-        B, H, W, C0m, C1m, Cout, c0_true = ctx.dims
-        Cp0, Cp1, Cop = _rup64(C0m), _rup64(C1m) if C1m else 0, _rup64(Cout)
+        B, H, W, Cout, c0_true = ctx.dims
+        C0m, C1m, Cp0, Cp1, Cop = _narrow_dims(x0, x1, Cout)
         Cinp = Cp0 + Cp1
         n = B * H * W
         dev = y.device
-        dz = dense_nhwc(dz if dz.dtype == y.dtype else dz.to(y.dtype))
-        scale, shift, mean, rstd = coef[:Cout], coef[Cout:2 * Cout], coef[2 * Cout:3 * Cout], coef[3 * Cout:]
+        dz = grad_like(dz, y)
+        scale, shift, mean, rstd = coef_views(coef)
         dt = _dt(y)
         nblk = LIB.query("uh_bn_bwd_nblk", n, Cout)
         partials = torch.empty(nblk * 2 * Cout, dtype=torch.float32, device=dev)
-        LIB.call("uh_bn_relu_bwd_reduce", dz.data_ptr(), pixel_ld(dz), y.data_ptr(), Cout, scale.data_ptr(),
-                 shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), partials.data_ptr(), n, Cout, dt, _stream())
-        gamma_p, beta_p = ctx.bn_params
-        (dgamma, cb_g), (dbeta, cb_b) = _grad_buffer(gamma_p, ctx.needs_input_grad[3]), _grad_buffer(beta_p, ctx.needs_input_grad[4])
+        bn_args = (dz.data_ptr(), pixel_ld(dz), y.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+        LIB.call("uh_bn_relu_bwd_reduce", *bn_args, partials.data_ptr(), n, Cout, dt, _stream())
+        bn_wanted = (need["gamma"], need["beta"])
+        bn_bufs = [_grad_buffer(p, w) for p, w in zip(ctx.bn_params, bn_wanted)]
         dy = torch.empty_like(y)
-        if ctx.sync_bn is None:
-            LIB.call("uh_bn_relu_bwd_apply", dz.data_ptr(), pixel_ld(dz), y.data_ptr(), Cout, scale.data_ptr(),
-                     shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), partials.data_ptr(), nblk, dgamma.data_ptr(),
-                     dbeta.data_ptr(), dy.data_ptr(), Cout, n, 0, Cout, dt, _stream())
-        else:
-            import torch.distributed as dist
-            LIB.call("uh_bn_bwd_finalize", partials.data_ptr(), nblk, Cout, dgamma.data_ptr(), dbeta.data_ptr(), _stream())
-            glob = torch.cat([dgamma.reshape(-1), dbeta.reshape(-1)])
-            dist.all_reduce(glob, op=dist.ReduceOp.SUM, group=ctx.sync_bn[0])
-            LIB.call("uh_bn_relu_bwd_apply", dz.data_ptr(), pixel_ld(dz), y.data_ptr(), Cout, scale.data_ptr(),
-                     shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), None, 0, glob[:Cout].data_ptr(),
-                     glob[Cout:].data_ptr(), dy.data_ptr(), Cout, n, ctx.n_total, Cout, dt, _stream())
+
+        def apply(part_ptr, nb, dg_ptr, db_ptr, n_total):
+            LIB.call("uh_bn_relu_bwd_apply", *bn_args, part_ptr, nb, dg_ptr, db_ptr, dy.data_ptr(), Cout, n, n_total, Cout, dt,
+                     _stream())
+        _bn_backward_finish(partials, nblk, Cout, bn_bufs[0][0], bn_bufs[1][0], ctx.sync_bn, ctx.n_total, apply)
         # backward-data: the padded layer's transposed conv, once per source, each writing its own narrow dx
         dx = [None, None]
         for i, (wd, Cp, Cm) in enumerate(((wd0, Cp0, C0m), (wd1, Cp1, C1m))):
@@ -1273,14 +1280,14 @@ class ConvBnReluNarrowFn(Function):
                 LIB.call("uh_conv3x3_fwd_narrow", dy.data_ptr(), Cop, Cout, Cout, None, 0, 0, 0, wd.data_ptr(),
                          dx[i].data_ptr(), Cm, Cp, Cm, None, None, None, B, H, W, ctx.cdt, _stream())
         dweight = None
-        if ctx.needs_input_grad[2]:
+        if need["weight"]:
             wdt = UH_F32X3 if (ctx.cdt == UH_F32X3) else dt
             nbytes = LIB.query("uh_conv3x3_wgrad_ws_bytes", B, H, W, Cinp, Cop, dt)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             dwk = torch.empty(Cop, 3, 3, Cinp, dtype=torch.float32, device=dev)
             with _Timed("conv3x3_wgrad_narrow", 2.0 * n * Cop * 9 * Cinp):
                 LIB.call("uh_conv3x3_wgrad_narrow", dy.data_ptr(), Cout, Cop, Cout, x0.data_ptr(), Cp0, C0m, pixel_ld(x0),
-                         _p(x1), Cp1, C1m, 0 if x1 is None else pixel_ld(x1), dwk.data_ptr(), ws.data_ptr(), nbytes,
+                         _p(x1), Cp1, C1m, pixel_ld_or0(x1), dwk.data_ptr(), ws.data_ptr(), nbytes,
                          B, H, W, wdt, _stream())
             dweight, cb_w = _grad_buffer(weight)
             dweight[:, :c0_true].copy_(dwk[:Cout, :, :, :c0_true].permute(0, 3, 1, 2))
@@ -1289,17 +1296,8 @@ class ConvBnReluNarrowFn(Function):
             if cb_w is not None:
                 cb_w()
                 dweight = None
-        if cb_g is not None:
-            cb_g()
-            dgamma = None
-        if cb_b is not None:
-            cb_b()
-            dbeta = None
-        if not ctx.needs_input_grad[3]:
-            dgamma = None
-        if not ctx.needs_input_grad[4]:
-            dbeta = None
-        return dx[0], dx[1], dweight, dgamma, dbeta, None, None, None, None, None, None, None
+        dgamma, dbeta = _bn_param_grads(bn_bufs, bn_wanted)
+        return _grads_for(_NARROW_INPUTS, x0=dx[0], x1=dx[1], weight=dweight, gamma=dgamma, beta=dbeta)
 
 
 # ----------------------------------------------------------------------------- max-pool

@@ -66,6 +66,7 @@ def _conv_bn_relu(x0, x1, conv: nn.Conv2d, bn: nn.BatchNorm2d, training: bool, k
     `x0_channels`: x0 is already such a padded tensor and only its first x0_channels channels are real.
     `keep_padded`: return the padded tensor (DoubleConv hands it to its second conv without a copy)."""
     momentum = 0.1 if bn.momentum is None else bn.momentum
+    opts = ops.ConvBnOpts(bn.running_mean, bn.running_var, bn.num_batches_tracked, training, momentum, bn.eps, pre_coef=pre_coef)
     w = conv.weight
     Cout, Cin = w.shape[0], w.shape[1]
     C0 = x0_channels if x0_channels is not None else x0.shape[-1]
@@ -79,18 +80,18 @@ def _conv_bn_relu(x0, x1, conv: nn.Conv2d, bn: nn.BatchNorm2d, training: bool, k
             # the network's first layer: its conv output is recomputed by every consumer instead of stored
             return ops.StemConvBnReluFn.apply(x0, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                               momentum, bn.eps)
-        args = (x0, x1, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, training, momentum,
-                bn.eps)
+        args = (x0, x1, w, bn.weight, bn.bias)
         if defer:      # (the caller has checked ops.pre_fuse_ok: this layer's BatchNorm + ReLU is applied by its consumer)
-            return ops.ConvBnReluFn.apply(*args, ops.TAIL_NONE, None, None, True, None)
-        link = (bnsum_pub, bnsum_use) if training else (None, None)      # (ops.BnSumLink: see DoubleConv.nhwc)
-        if training and tail == "pool" and ops.pool_tail_ok(x0, Cout):
-            return ops.ConvBnReluFn.apply(*args, ops.TAIL_POOL, None, None, False, pre_coef, *link)
-        if training and isinstance(tail, OutConv) and ops.head_tail_ok(x0, Cout, tail.conv.weight):
-            return ops.ConvBnReluFn.apply(*args, ops.TAIL_HEAD, tail.conv.weight, tail.conv.bias, False, pre_coef, *link)
-        if training and _is_up(tail) and ops.up_tail_ok(x0, Cout, tail[1], tail[2]):
-            return ops.ConvBnReluFn.apply(*args, ops.TAIL_UP, None, None, False, pre_coef, *link, (tail[1], tail[2]))
-        return _finish_tail(ops.ConvBnReluFn.apply(*args, ops.TAIL_NONE, None, None, False, pre_coef, *link), tail)
+            return ops.ConvBnReluFn.apply(*args, None, None, opts._replace(defer=True, pre_coef=None))
+        if training:
+            opts = opts._replace(bnsum_pub=bnsum_pub, bnsum_use=bnsum_use)      # (ops.BnSumLink: see DoubleConv.nhwc)
+            if tail == "pool" and ops.pool_tail_ok(x0, Cout):
+                return ops.ConvBnReluFn.apply(*args, None, None, opts._replace(tail=ops.TAIL_POOL))
+            if isinstance(tail, OutConv) and ops.head_tail_ok(x0, Cout, tail.conv.weight):
+                return ops.ConvBnReluFn.apply(*args, tail.conv.weight, tail.conv.bias, opts._replace(tail=ops.TAIL_HEAD))
+            if _is_up(tail) and ops.up_tail_ok(x0, Cout, tail[1], tail[2]):
+                return ops.ConvBnReluFn.apply(*args, None, None, opts._replace(tail=ops.TAIL_UP, up_size=(tail[1], tail[2])))
+        return _finish_tail(ops.ConvBnReluFn.apply(*args, None, None, opts), tail)
     if defer or pre_coef is not None:
         raise RuntimeError("a deferred BatchNorm+ReLU needs 64-aligned layers (ops.pre_fuse_ok)")
     if ops.NARROW_IO and x0_channels is None:
@@ -99,8 +100,7 @@ def _conv_bn_relu(x0, x1, conv: nn.Conv2d, bn: nn.BatchNorm2d, training: bool, k
         vec = 16 // x0.element_size()
         x0n = _pad_c(x0, (C0 + vec - 1) // vec * vec)
         if ops.narrow_ok(x0n, x1, Cout):
-            return _finish_tail(ops.ConvBnReluNarrowFn.apply(x0n, x1, w, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                                             bn.num_batches_tracked, training, momentum, bn.eps, C0), tail)
+            return _finish_tail(ops.ConvBnReluNarrowFn.apply(x0n, x1, w, bn.weight, bn.bias, opts._replace(c0_true=C0)), tail)
     x0p = x0 if x0_channels is not None else _pad_c(x0, Cp0)
     x1p = None if x1 is None else _pad_c(x1, Cp1)
     # filter [Cout, C0 + C1, 3, 3] -> [Cop, Cp0 + Cp1, 3, 3]: each source's channel block is padded separately
@@ -114,7 +114,7 @@ def _conv_bn_relu(x0, x1, conv: nn.Conv2d, bn: nn.BatchNorm2d, training: bool, k
     if bn.running_mean is not None:
         rm = torch.nn.functional.pad(bn.running_mean, (0, Cop - Cout))
         rv = torch.nn.functional.pad(bn.running_var, (0, Cop - Cout), value=1.0)
-    zp = ops.ConvBnReluFn.apply(x0p, x1p, wp, gp, bp, rm, rv, bn.num_batches_tracked, training, momentum, bn.eps)
+    zp = ops.ConvBnReluFn.apply(x0p, x1p, wp, gp, bp, None, None, opts._replace(running_mean=rm, running_var=rv))
     if training and rm is not None:
         with torch.no_grad():
             bn.running_mean.copy_(rm[:Cout])
