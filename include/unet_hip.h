@@ -245,6 +245,15 @@ int uh_bn_finalize_ld(const float* stat_partials, int nslab, int ldc, int C, int
 int uh_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
                       const float* running_var, float eps, int C, float* scale, float* shift,
                       uh_stream stream);
+/* The launch plan of the pixel passes (BatchNorm + ReLU apply / backward, the pool tail, max-pool, bilinear x2, the 1x1
+ * backward-data): what a call over `items` pixels (or 2x2 windows) of C channels takes; host only, no device touched.
+ * aligned != 0: every tensor of the call is 16-byte aligned with a pixel stride of whole 16-byte pieces.  cap: the most
+ * workgroups of 256 threads the pass asks for (4096; 8192 for the 1x1 conv).  out[0..2] (HOST memory) = {vec, hoist, grid}:
+ * vec = channels per thread (8 bf16 / 4 fp32 where aligned and C is a multiple of that, else 1), grid = workgroups =
+ * min(cap, ceil(items * (C / vec) / 256)), hoist = 1 where vec > 1 and grid * 256 is a multiple of C / vec: every thread then stays on
+ * one channel group and the kernels that can keep that group's coefficients in registers do.  UH_EINVAL for a bad
+ * size or dtype or out == NULL. */
+int uh_pixel_pass_plan(int64_t items, int C, int dt, int aligned, int cap, int64_t* out);
 /* z = max(y*scale + shift, 0) */
 int uh_bn_relu_apply(const void* y, int ldy, const float* scale, const float* shift,
                      void* z, int ldz, int64_t npix, int C, int dt, uh_stream stream);

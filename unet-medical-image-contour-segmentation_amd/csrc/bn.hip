@@ -7,7 +7,7 @@
 // Backward (closed form):
 //   uh_bn_relu_bwd_reduce   per-block partial sums of dz*[z>0] and dz*[z>0]*xhat  (wave/LDS reductions)
 //   uh_bn_relu_bwd_apply    dgamma, dbeta, and dy = scale*(dzm - sum1/n - xhat*sum2/n)
-#include "uh_vec.h"
+#include "uh_launch.h"
 
 // ------------------------------------------------------------------------------------ finalize
 // Slab layout written by the conv epilogue: [nslab][2][C] = per-row (mean, M2) of the stored y, followed
@@ -222,11 +222,14 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const T* __restrict_
     }
 }
 
-static inline unsigned grid_for(int64_t total, int threads = 256, int cap = 256 * 16) {
-    int64_t g = (total + threads - 1) / threads;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (unsigned)g;
+extern "C" int uh_pixel_pass_plan(int64_t items, int C, int dt, int aligned, int cap, int64_t* out) {
+    UH_REQUIRE(items > 0 && C > 0 && cap > 0 && out && (dt == UH_F32 || dt == UH_BF16), "uh_pixel_pass_plan: bad args");
+    const int vec = dt == UH_BF16 ? 8 : 4;
+    const PixelPass p = uh_pixel_pass(items, C, 16 / vec, aligned && C % vec == 0, cap);
+    out[0] = p.vec;
+    out[1] = p.hoist;
+    out[2] = p.grid;
+    return UH_OK;
 }
 
 extern "C" int uh_bn_relu_apply(const void* y, int ldy, const float* scale, const float* shift, void* z, int ldz,
@@ -234,19 +237,11 @@ extern "C" int uh_bn_relu_apply(const void* y, int ldy, const float* scale, cons
     UH_REQUIRE(y && z && scale && shift && npix > 0 && C > 0 && ldy >= C && ldz >= C, "uh_bn_relu_apply: bad args");
     hipStream_t st = (hipStream_t)stream;
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(y, ldy, C) && uh_vec_ok<T>(z, ldz, C)) {
-            const unsigned g = grid_for(npix * (C / VEC));
-            if (((int64_t)g * 256) % (C / VEC) == 0)
-                hipLaunchKernelGGL((bn_relu_apply_kernel<T, VEC, true>), dim3(g), dim3(256), 0, st, (const T*)y, ldy, scale,
-                                   shift, (T*)z, ldz, npix, C);
-            else
-                hipLaunchKernelGGL((bn_relu_apply_kernel<T, VEC, false>), dim3(g), dim3(256), 0, st, (const T*)y, ldy, scale,
-                                   shift, (T*)z, ldz, npix, C);
-        } else {
-            hipLaunchKernelGGL((bn_relu_apply_kernel<T, 1, false>), dim3(grid_for(npix * C)), dim3(256), 0, st, (const T*)y,
-                               ldy, scale, shift, (T*)z, ldz, npix, C);
-        }
+        const PixelPass p = uh_pixel_pass(npix, C, sizeof(T), uh_all_vec_ok<T>(C, y, ldy, z, ldz), UH_GRID_CAP);
+        uh_pixel_launch<VEC>(p, [&](auto v, auto hoist) {
+            hipLaunchKernelGGL((bn_relu_apply_kernel<T, decltype(v)::value, decltype(hoist)::value>), dim3(p.grid), dim3(256), 0, st,
+                               (const T*)y, ldy, scale, shift, (T*)z, ldz, npix, C);
+        });
     });
     UH_CHECK_LAUNCH("bn_relu_apply_kernel");
     return UH_OK;
@@ -380,15 +375,12 @@ extern "C" int uh_bn_relu_bwd_reduce(const void* dz, int lddz, const void* y, in
     hipStream_t st = (hipStream_t)stream;
     int nblk = uh_bn_bwd_nblk(npix, C);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(dz, lddz, C) && uh_vec_ok<T>(y, ldy, C)) {
-            int G = C / VEC;
-            hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<T, VEC>), dim3(nblk, (G + 7) / 8), dim3(256), 0, st, (const T*)dz,
-                               lddz, (const T*)y, ldy, scale, shift, mean, rstd, partials, npix, C);
-        } else {
-            hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<T, 1>), dim3(nblk, (C + 7) / 8), dim3(256), 0, st, (const T*)dz, lddz,
-                               (const T*)y, ldy, scale, shift, mean, rstd, partials, npix, C);
-        }
+        // (blocks of 8 channel groups x nblk pixel chunks: only the vector form comes from the plan)
+        const PixelPass p = uh_pixel_pass(npix, C, sizeof(T), uh_all_vec_ok<T>(C, dz, lddz, y, ldy), UH_GRID_CAP);
+        uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+            hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<T, decltype(v)::value>), dim3(nblk, (C / p.vec + 7) / 8), dim3(256), 0, st,
+                               (const T*)dz, lddz, (const T*)y, ldy, scale, shift, mean, rstd, partials, npix, C);
+        });
     });
     UH_CHECK_LAUNCH("bn_relu_bwd_reduce_kernel");
     return UH_OK;
@@ -509,12 +501,15 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const T* __restr
     }
 }
 
-extern "C" int uh_bn_bwd_finalize(const float* partials, int nblk, int C, float* dgamma, float* dbeta, uh_stream stream) {
-    UH_REQUIRE(partials && dgamma && dbeta && nblk > 0 && C > 0, "uh_bn_bwd_finalize: bad args");
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + BWF_CH - 1) / BWF_CH), dim3(BWF_THREADS), 0, (hipStream_t)stream, partials, nblk, C,
-                       dgamma, dbeta);
+int uh_bn_bwd_finalize_launch(const float* partials, int nblk, int C, float* dgamma, float* dbeta, hipStream_t st) {
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + BWF_CH - 1) / BWF_CH), dim3(BWF_THREADS), 0, st, partials, nblk, C, dgamma, dbeta);
     UH_CHECK_LAUNCH("bn_bwd_finalize_kernel");
     return UH_OK;
+}
+
+extern "C" int uh_bn_bwd_finalize(const float* partials, int nblk, int C, float* dgamma, float* dbeta, uh_stream stream) {
+    UH_REQUIRE(partials && dgamma && dbeta && nblk > 0 && C > 0, "uh_bn_bwd_finalize: bad args");
+    return uh_bn_bwd_finalize_launch(partials, nblk, C, dgamma, dbeta, (hipStream_t)stream);
 }
 
 extern "C" int uh_bn_relu_bwd_apply(const void* dz, int lddz, const void* y, int ldy, const float* scale,
@@ -526,27 +521,17 @@ extern "C" int uh_bn_relu_bwd_apply(const void* dz, int lddz, const void* y, int
                "uh_bn_relu_bwd_apply: bad sizes");
     hipStream_t st = (hipStream_t)stream;
     if (nblk > 0) {          // nblk == 0: dgamma / dbeta already hold the (possibly cross-rank) sums
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + BWF_CH - 1) / BWF_CH), dim3(BWF_THREADS), 0, st, partials, nblk, C, dgamma, dbeta);
-        UH_CHECK_LAUNCH("bn_bwd_finalize_kernel");
+        const int rc = uh_bn_bwd_finalize_launch(partials, nblk, C, dgamma, dbeta, st);
+        if (rc != UH_OK) return rc;
     }
-    float inv_n = (float)(1.0 / (double)(n_total > 0 ? n_total : npix));
+    const float inv_n = uh_inv_n(n_total, npix);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(dz, lddz, C) && uh_vec_ok<T>(y, ldy, C) && uh_vec_ok<T>(dy, lddy, C)) {
-            const unsigned g = grid_for(npix * (C / VEC));
-            if (((int64_t)g * 256) % (C / VEC) == 0)
-                hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<T, VEC, true>), dim3(g), dim3(256), 0, st, (const T*)dz, lddz,
-                                   (const T*)y, ldy, scale, shift, mean, rstd, (const float*)dgamma, (const float*)dbeta,
-                                   (T*)dy, lddy, npix, C, inv_n);
-            else
-                hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<T, VEC, false>), dim3(g), dim3(256), 0, st, (const T*)dz, lddz,
-                                   (const T*)y, ldy, scale, shift, mean, rstd, (const float*)dgamma, (const float*)dbeta,
-                                   (T*)dy, lddy, npix, C, inv_n);
-        } else {
-            hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<T, 1, false>), dim3(grid_for(npix * C)), dim3(256), 0, st,
+        const PixelPass p = uh_pixel_pass(npix, C, sizeof(T), uh_all_vec_ok<T>(C, dz, lddz, y, ldy, dy, lddy), UH_GRID_CAP);
+        uh_pixel_launch<VEC>(p, [&](auto v, auto hoist) {
+            hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<T, decltype(v)::value, decltype(hoist)::value>), dim3(p.grid), dim3(256), 0, st,
                                (const T*)dz, lddz, (const T*)y, ldy, scale, shift, mean, rstd, (const float*)dgamma,
                                (const float*)dbeta, (T*)dy, lddy, npix, C, inv_n);
-        }
+        });
     });
     UH_CHECK_LAUNCH("bn_relu_bwd_apply_kernel");
     return UH_OK;

@@ -14,14 +14,7 @@
 // Every intermediate is rounded exactly as the unfused kernels round what they store (uh_round_as<T>), and sums run in the
 // same order per thread, so fused and unfused paths agree bit for bit on dy / z / pooled and to summation order on the
 // per-channel sums.  Thread = (pixel or 2x2 window, 16-byte channel group), like bn.hip.
-#include "uh_vec.h"
-
-static inline unsigned bf_grid(int64_t total, int cap = 256 * 16) {
-    int64_t g = (total + 255) / 256;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+#include "uh_launch.h"
 
 // ================================================================================================ pool tail
 extern "C" int uh_bn_relu_pool_ok(int B, int H, int W, int C, int dt) {
@@ -80,17 +73,13 @@ extern "C" int uh_bn_relu_pool_apply(const void* y, int ldy, const float* scale,
     UH_REQUIRE(uh_bn_relu_pool_ok(B, H, W, C, dt), "uh_bn_relu_pool_apply: shape not covered (even H, W; C a multiple of 16 bytes)");
     hipStream_t st = (hipStream_t)stream;
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        UH_REQUIRE(uh_vec_ok<T>(y, ldy, C) && uh_vec_ok<T>(z, ldz, C) && uh_vec_ok<T>(pooled, ldp, C),
+        UH_REQUIRE(uh_all_vec_ok<T>(C, y, ldy, z, ldz, pooled, ldp),
                    "uh_bn_relu_pool_apply: tensors must be 16-byte aligned with 16-byte multiple pixel strides");
-        const int G = C / VEC;
-        const unsigned g = bf_grid((int64_t)B * (H / 2) * (W / 2) * G);
-        if (((int64_t)g * 256) % G == 0)
-            hipLaunchKernelGGL((bn_relu_pool_apply_kernel<T, VEC, true>), dim3(g), dim3(256), 0, st, (const T*)y, ldy, scale, shift,
-                               (T*)z, ldz, (T*)pooled, ldp, B, H, W, C);
-        else
-            hipLaunchKernelGGL((bn_relu_pool_apply_kernel<T, VEC, false>), dim3(g), dim3(256), 0, st, (const T*)y, ldy, scale, shift,
-                               (T*)z, ldz, (T*)pooled, ldp, B, H, W, C);
+        const PixelPass p = uh_pixel_pass((int64_t)B * (H / 2) * (W / 2), C, sizeof(T), true, UH_GRID_CAP);
+        uh_pixel_launch<VEC, false>(p, [&](auto v, auto hoist) {
+            hipLaunchKernelGGL((bn_relu_pool_apply_kernel<T, decltype(v)::value, decltype(hoist)::value>), dim3(p.grid), dim3(256), 0, st,
+                               (const T*)y, ldy, scale, shift, (T*)z, ldz, (T*)pooled, ldp, B, H, W, C);
+        });
     });
     UH_CHECK_LAUNCH("bn_relu_pool_apply_kernel");
     return UH_OK;
@@ -316,8 +305,7 @@ extern "C" int uh_bn_relu_pool_bwd_reduce(const void* dskip, int ldskip, const v
     hipStream_t st = (hipStream_t)stream;
     const int nblk = uh_bn_bwd_nblk((int64_t)B * H * W, C);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        UH_REQUIRE(uh_vec_ok<T>(dpool, lddp, C) && uh_vec_ok<T>(y, ldy, C) && (!dskip || uh_vec_ok<T>(dskip, ldskip, C)),
+        UH_REQUIRE(uh_all_vec_ok<T>(C, dpool, lddp, y, ldy, dskip, ldskip),
                    "uh_bn_relu_pool_bwd_reduce: tensors must be 16-byte aligned with 16-byte multiple pixel strides");
         const int G = C / VEC;
         hipLaunchKernelGGL((bn_relu_pool_bwd_reduce_kernel<T, VEC>), dim3(nblk, (G + 7) / 8), dim3(256), 0, st, (const T*)dskip,
@@ -336,26 +324,20 @@ extern "C" int uh_bn_relu_pool_bwd_apply(const void* dskip, int ldskip, const vo
                    (!dskip || ldskip >= C), "uh_bn_relu_pool_bwd_apply: shape not covered");
     hipStream_t st = (hipStream_t)stream;
     if (nblk > 0) {
-        int rc = uh_bn_bwd_finalize(partials, nblk, C, dgamma, dbeta, stream);
+        const int rc = uh_bn_bwd_finalize_launch(partials, nblk, C, dgamma, dbeta, st);
         if (rc != UH_OK) return rc;
     }
     const int64_t npix = (int64_t)B * H * W;
-    const float inv_n = (float)(1.0 / (double)(n_total > 0 ? n_total : npix));
+    const float inv_n = uh_inv_n(n_total, npix);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        UH_REQUIRE(uh_vec_ok<T>(dpool, lddp, C) && uh_vec_ok<T>(y, ldy, C) && uh_vec_ok<T>(dy, lddy, C) &&
-                       (!dskip || uh_vec_ok<T>(dskip, ldskip, C)),
+        UH_REQUIRE(uh_all_vec_ok<T>(C, dpool, lddp, y, ldy, dy, lddy, dskip, ldskip),
                    "uh_bn_relu_pool_bwd_apply: tensors must be 16-byte aligned with 16-byte multiple pixel strides");
-        const int G = C / VEC;
-        const unsigned g = bf_grid(npix / 4 * G);
-        if (((int64_t)g * 256) % G == 0)
-            hipLaunchKernelGGL((bn_relu_pool_bwd_apply_kernel<T, VEC, true>), dim3(g), dim3(256), 0, st, (const T*)dskip, ldskip,
-                               (const T*)dpool, lddp, (const T*)y, ldy, scale, shift, mean, rstd, (const float*)dgamma,
-                               (const float*)dbeta, (T*)dy, lddy, B, H, W, C, inv_n);
-        else
-            hipLaunchKernelGGL((bn_relu_pool_bwd_apply_kernel<T, VEC, false>), dim3(g), dim3(256), 0, st, (const T*)dskip, ldskip,
-                               (const T*)dpool, lddp, (const T*)y, ldy, scale, shift, mean, rstd, (const float*)dgamma,
-                               (const float*)dbeta, (T*)dy, lddy, B, H, W, C, inv_n);
+        const PixelPass p = uh_pixel_pass(npix / 4, C, sizeof(T), true, UH_GRID_CAP);
+        uh_pixel_launch<VEC, false>(p, [&](auto v, auto hoist) {
+            hipLaunchKernelGGL((bn_relu_pool_bwd_apply_kernel<T, decltype(v)::value, decltype(hoist)::value>), dim3(p.grid), dim3(256), 0, st,
+                               (const T*)dskip, ldskip, (const T*)dpool, lddp, (const T*)y, ldy, scale, shift, mean, rstd,
+                               (const float*)dgamma, (const float*)dbeta, (T*)dy, lddy, B, H, W, C, inv_n);
+        });
     });
     UH_CHECK_LAUNCH("bn_relu_pool_bwd_apply_kernel");
     return UH_OK;
@@ -582,34 +564,17 @@ __global__ __launch_bounds__(256) void bn_relu_head_bwd_apply_kernel(const float
     }
 }
 
-static inline int head_nblk(int64_t npix, int C) { return uh_bn_bwd_nblk(npix, C); }
-
-#define UH_HEAD_SWITCH(LPPV, ...)                                                 \
-    switch (ncls) {                                                               \
-        case 1: { constexpr int NC = 1; constexpr int LPP = LPPV; __VA_ARGS__ } break;  \
-        case 2: { constexpr int NC = 2; constexpr int LPP = LPPV; __VA_ARGS__ } break;  \
-        case 3: { constexpr int NC = 3; constexpr int LPP = LPPV; __VA_ARGS__ } break;  \
-        default: { constexpr int NC = 4; constexpr int LPP = LPPV; __VA_ARGS__ } break; \
-    }
-#define UH_HEAD_DISPATCH(V, ...)                          \
-    do {                                                  \
-        if (C == 8 * (V)) { UH_HEAD_SWITCH(8, __VA_ARGS__) } \
-        else { UH_HEAD_SWITCH(16, __VA_ARGS__) }          \
-    } while (0)
-
 extern "C" int uh_bn_relu_head_fwd(const void* y, int ldy, const float* scale, const float* shift, const float* head_w,
                                    const float* head_b, float* logits, int64_t npix, int C, int ncls, int dt, uh_stream stream) {
     UH_REQUIRE(y && scale && shift && head_w && head_b && logits && npix > 0 && ldy >= C, "uh_bn_relu_head_fwd: bad args");
     UH_REQUIRE(uh_bn_relu_head_ok(C, ncls, dt), "uh_bn_relu_head_fwd: shape not covered (C = 8 or 16 channel groups, n_classes <= 4)");
     hipStream_t st = (hipStream_t)stream;
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
         UH_REQUIRE(uh_vec_ok<T>(y, ldy, C), "uh_bn_relu_head_fwd: y must be 16-byte aligned with a 16-byte multiple pixel stride");
-        UH_HEAD_DISPATCH(VEC, {
-            const int ppb4 = 4 * (256 / LPP);
-            const unsigned grid = bf_grid((npix + ppb4 - 1) / ppb4 * 256);
-            hipLaunchKernelGGL((bn_relu_head_fwd_kernel<T, VEC, NC, LPP>), dim3(grid), dim3(256), 0, st, (const T*)y, ldy, scale,
-                               shift, head_w, head_b, logits, npix);
+        uh_head_dispatch<4>(ncls, C / VEC, [&](auto nc, auto lpp) {
+            constexpr int NC = decltype(nc)::value, LPP = decltype(lpp)::value;
+            hipLaunchKernelGGL((bn_relu_head_fwd_kernel<T, VEC, NC, LPP>), dim3(uh_head_grid(npix, LPP, UH_GRID_CAP)), dim3(256), 0, st,
+                               (const T*)y, ldy, scale, shift, head_w, head_b, logits, npix);
         });
     });
     UH_CHECK_LAUNCH("bn_relu_head_fwd_kernel");
@@ -617,7 +582,7 @@ extern "C" int uh_bn_relu_head_fwd(const void* y, int ldy, const float* scale, c
 }
 
 extern "C" size_t uh_bn_relu_head_bwd_ws_bytes(int64_t npix, int C, int ncls) {
-    return (size_t)head_nblk(npix, C) * ncls * (C + 1) * sizeof(float) + 16;
+    return (size_t)uh_bn_bwd_nblk(npix, C) * ncls * (C + 1) * sizeof(float) + 16;
 }
 
 extern "C" int uh_bn_relu_head_bwd_reduce(const float* dlogits, const float* head_w, const void* y, int ldy, const float* scale,
@@ -627,7 +592,7 @@ extern "C" int uh_bn_relu_head_bwd_reduce(const float* dlogits, const float* hea
     UH_REQUIRE(dlogits && head_w && y && scale && shift && mean && rstd && partials && dhead_w && dhead_b && ws && npix > 0 &&
                    ldy >= C, "uh_bn_relu_head_bwd_reduce: bad args");
     UH_REQUIRE(uh_bn_relu_head_ok(C, ncls, dt), "uh_bn_relu_head_bwd_reduce: shape not covered");
-    const int nblk = head_nblk(npix, C);
+    const int nblk = uh_bn_bwd_nblk(npix, C);
     const size_t need = (size_t)nblk * ncls * (C + 1) * sizeof(float);
     if (ws_bytes < need) {
         uh_set_error("uh_bn_relu_head_bwd_reduce: workspace %zu < %zu bytes", ws_bytes, need);
@@ -635,11 +600,10 @@ extern "C" int uh_bn_relu_head_bwd_reduce(const float* dlogits, const float* hea
     }
     hipStream_t st = (hipStream_t)stream;
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
         UH_REQUIRE(uh_vec_ok<T>(y, ldy, C), "uh_bn_relu_head_bwd_reduce: y must be 16-byte aligned with a 16-byte multiple pixel stride");
-        UH_HEAD_DISPATCH(VEC, {
-            hipLaunchKernelGGL((bn_relu_head_bwd_reduce_kernel<T, VEC, NC, LPP>), dim3(nblk), dim3(256), 0, st, dlogits, head_w,
-                               (const T*)y, ldy, scale, shift, mean, rstd, partials, (float*)ws, npix);
+        uh_head_dispatch<4>(ncls, C / VEC, [&](auto nc, auto lpp) {
+            hipLaunchKernelGGL((bn_relu_head_bwd_reduce_kernel<T, VEC, decltype(nc)::value, decltype(lpp)::value>), dim3(nblk), dim3(256), 0,
+                               st, dlogits, head_w, (const T*)y, ldy, scale, shift, mean, rstd, partials, (float*)ws, npix);
         });
     });
     UH_CHECK_LAUNCH("bn_relu_head_bwd_reduce_kernel");
@@ -658,20 +622,18 @@ extern "C" int uh_bn_relu_head_bwd_apply(const float* dlogits, const float* head
     UH_REQUIRE(uh_bn_relu_head_ok(C, ncls, dt), "uh_bn_relu_head_bwd_apply: shape not covered");
     hipStream_t st = (hipStream_t)stream;
     if (nblk > 0) {
-        int rc = uh_bn_bwd_finalize(partials, nblk, C, dgamma, dbeta, stream);
+        const int rc = uh_bn_bwd_finalize_launch(partials, nblk, C, dgamma, dbeta, st);
         if (rc != UH_OK) return rc;
     }
-    const float inv_n = (float)(1.0 / (double)(n_total > 0 ? n_total : npix));
+    const float inv_n = uh_inv_n(n_total, npix);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        UH_REQUIRE(uh_vec_ok<T>(y, ldy, C) && uh_vec_ok<T>(dy, lddy, C),
+        UH_REQUIRE(uh_all_vec_ok<T>(C, y, ldy, dy, lddy),
                    "uh_bn_relu_head_bwd_apply: tensors must be 16-byte aligned with 16-byte multiple pixel strides");
-        UH_HEAD_DISPATCH(VEC, {
-            const int ppb4 = 4 * (256 / LPP);
-            const unsigned grid = bf_grid((npix + ppb4 - 1) / ppb4 * 256);
-            hipLaunchKernelGGL((bn_relu_head_bwd_apply_kernel<T, VEC, NC, LPP>), dim3(grid), dim3(256), 0, st, dlogits, head_w,
-                               (const T*)y, ldy, scale, shift, mean, rstd, (const float*)dgamma, (const float*)dbeta, (T*)dy, lddy,
-                               npix, inv_n);
+        uh_head_dispatch<4>(ncls, C / VEC, [&](auto nc, auto lpp) {
+            constexpr int NC = decltype(nc)::value, LPP = decltype(lpp)::value;
+            hipLaunchKernelGGL((bn_relu_head_bwd_apply_kernel<T, VEC, NC, LPP>), dim3(uh_head_grid(npix, LPP, UH_GRID_CAP)), dim3(256), 0, st,
+                               dlogits, head_w, (const T*)y, ldy, scale, shift, mean, rstd, (const float*)dgamma, (const float*)dbeta,
+                               (T*)dy, lddy, npix, inv_n);
         });
     });
     UH_CHECK_LAUNCH("bn_relu_head_bwd_apply_kernel");

@@ -4,14 +4,7 @@
 // ConvTranspose k2 s2 never overlaps: output pixel (2h+r, 2w+s) depends on input pixel (h,w) only,
 // through the [Cin x Cout] slice W[:, :, r, s]  (SURVEY.md A.3).
 // OutConv has 1..4 output channels: pure HBM-bound streaming, reductions by wave shuffles.
-#include "uh_vec.h"
-
-static inline unsigned ct_grid(int64_t total) {
-    int64_t g = (total + 255) / 256;
-    if (g > 256 * 32) g = 256 * 32;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+#include "uh_launch.h"
 
 // ------------------------------------------------------------------------------------ ConvTranspose 2x2
 // Three GEMMs over pixels on a shared LDS-tiled SIMT kernel (64x64 tile, 16-deep K steps, 4x4 outputs per thread,
@@ -370,19 +363,6 @@ __global__ __launch_bounds__(256) void conv1x1_fwd_nc_kernel(const T* __restrict
     }
 }
 
-template <typename T, int V, int LPP>
-static void c11_fwd_nc_launch(int ncls, const T* x, int ldx, const float* w, const float* bias, float* logits, int64_t npix,
-                              hipStream_t st) {
-    const int ppb4 = 4 * (256 / LPP);                      // pixels per workgroup trip
-    const unsigned grid = ct_grid((npix + ppb4 - 1) / ppb4 * 256);
-    switch (ncls) {
-        case 1: hipLaunchKernelGGL((conv1x1_fwd_nc_kernel<T, V, 1, LPP>), dim3(grid), dim3(256), 0, st, x, ldx, w, bias, logits, npix); break;
-        case 2: hipLaunchKernelGGL((conv1x1_fwd_nc_kernel<T, V, 2, LPP>), dim3(grid), dim3(256), 0, st, x, ldx, w, bias, logits, npix); break;
-        case 3: hipLaunchKernelGGL((conv1x1_fwd_nc_kernel<T, V, 3, LPP>), dim3(grid), dim3(256), 0, st, x, ldx, w, bias, logits, npix); break;
-        default: hipLaunchKernelGGL((conv1x1_fwd_nc_kernel<T, V, 4, LPP>), dim3(grid), dim3(256), 0, st, x, ldx, w, bias, logits, npix); break;
-    }
-}
-
 template <typename T, int V>
 __global__ __launch_bounds__(256) void conv1x1_dgrad_kernel(const float* __restrict__ dl, const float* __restrict__ w,
                                                             T* __restrict__ dx, int lddx, int64_t npix, int Cin, int ncls) {
@@ -510,19 +490,22 @@ extern "C" int uh_conv1x1_fwd(const void* x, int ldx, const float* w, const floa
     hipStream_t st = (hipStream_t)stream;
     size_t sm = (size_t)ncls * Cin * sizeof(float);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(x, ldx, Cin) && (Cin == 8 * VEC || Cin == 16 * VEC) && ncls <= 4) {      // the UNet head: 64 channels
-            if (Cin == 8 * VEC) c11_fwd_nc_launch<T, VEC, 8>(ncls, (const T*)x, ldx, w, bias, logits, npix, st);
-            else c11_fwd_nc_launch<T, VEC, 16>(ncls, (const T*)x, ldx, w, bias, logits, npix, st);
-        } else if (uh_vec_ok<T>(x, ldx, Cin)) {
-            int G = Cin / VEC, LPP = 1;
-            while (LPP * 2 <= G && LPP < 64) LPP *= 2;   // power of two lanes per pixel
-            int ppb = 256 / LPP;
-            hipLaunchKernelGGL((conv1x1_fwd_kernel<T, VEC>), dim3(ct_grid((npix + ppb - 1) / ppb * 256)), dim3(256), sm, st,
-                               (const T*)x, ldx, w, bias, logits, npix, Cin, ncls, LPP);
+        const bool vec = uh_vec_ok<T>(x, ldx, Cin);
+        if (vec && (Cin == 8 * VEC || Cin == 16 * VEC) && ncls <= 4) {      // the UNet head: 64 channels
+            uh_head_dispatch<4>(ncls, Cin / VEC, [&](auto nc, auto lpp) {
+                constexpr int NC = decltype(nc)::value, LPP = decltype(lpp)::value;
+                hipLaunchKernelGGL((conv1x1_fwd_nc_kernel<T, VEC, NC, LPP>), dim3(uh_head_grid(npix, LPP, UH_GRID_CAP_1X1)), dim3(256), 0, st,
+                                   (const T*)x, ldx, w, bias, logits, npix);
+            });
         } else {
-            hipLaunchKernelGGL((conv1x1_fwd_kernel<T, 1>), dim3(ct_grid(npix)), dim3(256), sm, st, (const T*)x, ldx, w, bias,
-                               logits, npix, Cin, ncls, 1);
+            int LPP = 1;                                 // power of two lanes per pixel (one in the scalar form)
+            while (vec && LPP * 2 <= Cin / VEC && LPP < 64) LPP *= 2;
+            const int ppb = 256 / LPP;
+            const PixelPass p{vec ? VEC : 1, false, uh_flat_grid((npix + ppb - 1) / ppb * 256, UH_GRID_CAP_1X1)};
+            uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+                hipLaunchKernelGGL((conv1x1_fwd_kernel<T, decltype(v)::value>), dim3(p.grid), dim3(256), sm, st, (const T*)x, ldx, w,
+                                   bias, logits, npix, Cin, ncls, LPP);
+            });
         }
     });
     UH_CHECK_LAUNCH("conv1x1_fwd_kernel");
@@ -534,13 +517,11 @@ extern "C" int uh_conv1x1_dgrad(const float* dlogits, const float* w, void* dx, 
     UH_REQUIRE(dlogits && w && dx && npix > 0 && Cin > 0 && ncls > 0 && lddx >= Cin, "uh_conv1x1_dgrad: bad args");
     hipStream_t st = (hipStream_t)stream;
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(dx, lddx, Cin))
-            hipLaunchKernelGGL((conv1x1_dgrad_kernel<T, VEC>), dim3(ct_grid(npix * (Cin / VEC))), dim3(256), 0, st, dlogits,
-                               w, (T*)dx, lddx, npix, Cin, ncls);
-        else
-            hipLaunchKernelGGL((conv1x1_dgrad_kernel<T, 1>), dim3(ct_grid(npix * Cin)), dim3(256), 0, st, dlogits, w, (T*)dx,
-                               lddx, npix, Cin, ncls);
+        const PixelPass p = uh_pixel_pass(npix, Cin, sizeof(T), uh_all_vec_ok<T>(Cin, dx, lddx), UH_GRID_CAP_1X1);
+        uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+            hipLaunchKernelGGL((conv1x1_dgrad_kernel<T, decltype(v)::value>), dim3(p.grid), dim3(256), 0, st, dlogits, w, (T*)dx, lddx,
+                               npix, Cin, ncls);
+        });
     });
     UH_CHECK_LAUNCH("conv1x1_dgrad_kernel");
     return UH_OK;
@@ -561,24 +542,19 @@ extern "C" int uh_conv1x1_wgrad(const float* dlogits, const void* x, int ldx, fl
         return UH_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-#define UH_C11_LAUNCH(T, V, NC)                                                                                      \
-    do {                                                                                                             \
-        int G = Cin / (V), GB = G < 256 ? G : 256, PL = 256 / GB;                                                    \
-        size_t sm = (size_t)PL * (NC) * (GB * (V) + 1) * sizeof(float);                                              \
-        hipLaunchKernelGGL((conv1x1_wgrad_kernel<T, V, NC>), dim3(nblk), dim3(256), sm, st, dlogits, (const T*)x, ldx, \
-                           (float*)ws, npix, Cin);                                                                   \
-    } while (0)
-#define UH_C11_NC(T, V)                                                                    \
-    switch (ncls) {                                                                        \
-        case 1: UH_C11_LAUNCH(T, V, 1); break; case 2: UH_C11_LAUNCH(T, V, 2); break;      \
-        case 3: UH_C11_LAUNCH(T, V, 3); break; case 4: UH_C11_LAUNCH(T, V, 4); break;      \
-        case 5: UH_C11_LAUNCH(T, V, 5); break; case 6: UH_C11_LAUNCH(T, V, 6); break;      \
-        case 7: UH_C11_LAUNCH(T, V, 7); break; default: UH_C11_LAUNCH(T, V, 8); break;     \
-    }
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(x, ldx, Cin) && ncls <= 4) { UH_C11_NC(T, VEC) }
-        else { UH_C11_NC(T, 1) }
+        // (more than four classes take the scalar form; the class ladder spans 1..8 in either form)
+        const PixelPass p{uh_vec_ok<T>(x, ldx, Cin) && ncls <= 4 ? VEC : 1, false, (unsigned)nblk};
+        uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+            constexpr int V = decltype(v)::value;
+            uh_class_dispatch<MAXCLS>(ncls, [&](auto nc) {
+                constexpr int NC = decltype(nc)::value;
+                const int G = Cin / V, GB = G < 256 ? G : 256, PL = 256 / GB;
+                const size_t sm = (size_t)PL * NC * (GB * V + 1) * sizeof(float);
+                hipLaunchKernelGGL((conv1x1_wgrad_kernel<T, V, NC>), dim3(p.grid), dim3(256), sm, st, dlogits, (const T*)x, ldx,
+                                   (float*)ws, npix, Cin);
+            });
+        });
     });
     UH_CHECK_LAUNCH("conv1x1_wgrad_kernel");
     int n = ncls * (Cin + 1);

@@ -1,14 +1,7 @@
 // pool_up.hip -- nn.MaxPool2d(2) (unet_parts.py:32) and nn.Upsample(scale_factor=2, 'bilinear',
 // align_corners=True) + F.pad (unet_parts.py:70,85-88) for NHWC tensors; all HBM-bound, one 16-byte
 // channel vector per lane.
-#include "uh_vec.h"
-
-static inline unsigned pu_grid(int64_t total) {
-    int64_t g = (total + 255) / 256;
-    if (g > 256 * 16) g = 256 * 16;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+#include "uh_launch.h"
 
 // ------------------------------------------------------------------------------------ max-pool
 template <typename T, int V>
@@ -86,13 +79,11 @@ extern "C" int uh_maxpool2_fwd(const void* x, int ldx, void* y, int ldy, int B, 
     hipStream_t st = (hipStream_t)stream;
     int64_t npo = (int64_t)B * (H / 2) * (W / 2);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(x, ldx, C) && uh_vec_ok<T>(y, ldy, C))
-            hipLaunchKernelGGL((maxpool2_fwd_kernel<T, VEC>), dim3(pu_grid(npo * (C / VEC))), dim3(256), 0, st, (const T*)x,
-                               ldx, (T*)y, ldy, B, H, W, C);
-        else
-            hipLaunchKernelGGL((maxpool2_fwd_kernel<T, 1>), dim3(pu_grid(npo * C)), dim3(256), 0, st, (const T*)x, ldx,
-                               (T*)y, ldy, B, H, W, C);
+        const PixelPass p = uh_pixel_pass(npo, C, sizeof(T), uh_all_vec_ok<T>(C, x, ldx, y, ldy), UH_GRID_CAP);
+        uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+            hipLaunchKernelGGL((maxpool2_fwd_kernel<T, decltype(v)::value>), dim3(p.grid), dim3(256), 0, st, (const T*)x, ldx, (T*)y, ldy,
+                               B, H, W, C);
+        });
     });
     UH_CHECK_LAUNCH("maxpool2_fwd_kernel");
     return UH_OK;
@@ -105,14 +96,11 @@ extern "C" int uh_maxpool2_bwd(const void* x, int ldx, const void* dy, int lddy,
     hipStream_t st = (hipStream_t)stream;
     int64_t np = (int64_t)B * H * W;
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(x, ldx, C) && uh_vec_ok<T>(dy, lddy, C) && uh_vec_ok<T>(dx, lddx, C) &&
-            (!dskip || uh_vec_ok<T>(dskip, ldskip, C)))
-            hipLaunchKernelGGL((maxpool2_bwd_kernel<T, VEC>), dim3(pu_grid(np * (C / VEC))), dim3(256), 0, st, (const T*)x,
-                               ldx, (const T*)dy, lddy, (const T*)dskip, ldskip, (T*)dx, lddx, B, H, W, C);
-        else
-            hipLaunchKernelGGL((maxpool2_bwd_kernel<T, 1>), dim3(pu_grid(np * C)), dim3(256), 0, st, (const T*)x, ldx,
+        const PixelPass p = uh_pixel_pass(np, C, sizeof(T), uh_all_vec_ok<T>(C, x, ldx, dy, lddy, dx, lddx, dskip, ldskip), UH_GRID_CAP);
+        uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+            hipLaunchKernelGGL((maxpool2_bwd_kernel<T, decltype(v)::value>), dim3(p.grid), dim3(256), 0, st, (const T*)x, ldx,
                                (const T*)dy, lddy, (const T*)dskip, ldskip, (T*)dx, lddx, B, H, W, C);
+        });
     });
     UH_CHECK_LAUNCH("maxpool2_bwd_kernel");
     return UH_OK;
@@ -493,22 +481,17 @@ extern "C" int uh_upsample2x_fwd(const void* x, int ldx, void* y, int ldy, int B
     int64_t np = (int64_t)B * Ho * Wo;
     float sy = up_scale(h), sx = up_scale(w);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(x, ldx, C) && uh_vec_ok<T>(y, ldy, C) && (int64_t)Wo * (C / VEC) < (1 << 23) &&
-            (int64_t)B * Ho < (1ll << 31)) {
+        const PixelPass p = uh_pixel_pass(np, C, sizeof(T), uh_all_vec_ok<T>(C, x, ldx, y, ldy), UH_GRID_CAP);
+        if (p.vec == VEC && (int64_t)Wo * (C / VEC) < (1 << 23) && (int64_t)B * Ho < (1ll << 31)) {
             const int G = C / VEC;
-            int gshift = -1;
-            for (int k = 0; k < 24; ++k)
-                if ((1 << k) == G) gshift = k;
             const unsigned gy = (unsigned)(((int64_t)Wo * G + 255) / 256);
             hipLaunchKernelGGL((upsample2x_fwd_rows_kernel<T, VEC>), dim3((unsigned)(B * ((Ho + UP_ROWS - 1) / UP_ROWS)), gy), dim3(256), 0, st, (const T*)x,
-                               ldx, (T*)y, ldy, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx, gshift);
-        } else if (uh_vec_ok<T>(x, ldx, C) && uh_vec_ok<T>(y, ldy, C))
-            hipLaunchKernelGGL((upsample2x_fwd_kernel<T, VEC>), dim3(pu_grid(np * (C / VEC))), dim3(256), 0, st,
-                               (const T*)x, ldx, (T*)y, ldy, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx);
-        else
-            hipLaunchKernelGGL((upsample2x_fwd_kernel<T, 1>), dim3(pu_grid(np * C)), dim3(256), 0, st, (const T*)x, ldx,
-                               (T*)y, ldy, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx);
+                               ldx, (T*)y, ldy, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx, uh_log2_exact(G));
+        } else
+            uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+                hipLaunchKernelGGL((upsample2x_fwd_kernel<T, decltype(v)::value>), dim3(p.grid), dim3(256), 0, st, (const T*)x, ldx,
+                                   (T*)y, ldy, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx);
+            });
     });
     UH_CHECK_LAUNCH("upsample2x_fwd_kernel");
     return UH_OK;
@@ -532,15 +515,11 @@ extern "C" int uh_bn_relu_upsample2x_fwd(const void* x, int ldx, const float* sc
     hipStream_t st = (hipStream_t)stream;
     float sy = up_scale(h), sx = up_scale(w);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        UH_REQUIRE((uh_vec_ok<T>(x, ldx, C) && uh_vec_ok<T>(y, ldy, C)), "uh_bn_relu_upsample2x_fwd: tensors must be 16-byte aligned with 16-byte pixel strides");
+        UH_REQUIRE(uh_all_vec_ok<T>(C, x, ldx, y, ldy), "uh_bn_relu_upsample2x_fwd: tensors must be 16-byte aligned with 16-byte pixel strides");
         const int G = C / VEC;
-        int gshift = -1;
-        for (int k = 0; k < 24; ++k)
-            if ((1 << k) == G) gshift = k;
         const unsigned gy = (unsigned)(((int64_t)Wo * G + 255) / 256);
         hipLaunchKernelGGL((upsample2x_fwd_rows_kernel<T, VEC, true>), dim3((unsigned)(B * ((Ho + UP_ROWS - 1) / UP_ROWS)), gy), dim3(256), 0, st, (const T*)x,
-                           ldx, (T*)y, ldy, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx, gshift, scale, shift);
+                           ldx, (T*)y, ldy, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx, uh_log2_exact(G), scale, shift);
     });
     UH_CHECK_LAUNCH("upsample2x_fwd_rows_kernel (BatchNorm + ReLU input)");
     return UH_OK;
@@ -553,8 +532,8 @@ extern "C" int uh_upsample2x_bwd(const void* dy, int lddy, void* dx, int lddx, i
     int64_t np = (int64_t)B * h * w;
     float sy = up_scale(h), sx = up_scale(w);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
-        if (uh_vec_ok<T>(dy, lddy, C) && uh_vec_ok<T>(dx, lddx, C) && h >= 2 && w >= 2) {
+        const PixelPass p = uh_pixel_pass(np, C, sizeof(T), uh_all_vec_ok<T>(C, dy, lddy, dx, lddx), UH_GRID_CAP);
+        if (p.vec == VEC && h >= 2 && w >= 2) {
             // strips of 16 input rows; shorter strips on small maps keep >= ~1024 workgroups in flight
             int ty = 16;
             while (ty > 2 && (int64_t)B * ((h + ty - 1) / ty) * w * (C / VEC) < 256 * 1024) ty >>= 1;
@@ -563,18 +542,18 @@ extern "C" int uh_upsample2x_bwd(const void* dy, int lddy, void* dx, int lddx, i
             // (UH_UP_BWD_PTR=1, read per call: the pointer form that tensors of 1 GiB and more take, for the test that holds the two
             // forms bit-identical)
             const char* force_ptr = getenv("UH_UP_BWD_PTR");
+            const dim3 grid(uh_flat_grid(nthr, UH_GRID_CAP));
             if (dyb < (1ll << 30) && !(force_ptr && force_ptr[0] == '1'))
-                hipLaunchKernelGGL((upsample2x_bwd_strip_kernel<T, VEC, true>), dim3(pu_grid(nthr)), dim3(256), 0, st, (const T*)dy,
+                hipLaunchKernelGGL((upsample2x_bwd_strip_kernel<T, VEC, true>), grid, dim3(256), 0, st, (const T*)dy,
                                    lddy, (T*)dx, lddx, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx, ty, (unsigned)dyb);
             else
-                hipLaunchKernelGGL((upsample2x_bwd_strip_kernel<T, VEC>), dim3(pu_grid(nthr)), dim3(256), 0, st, (const T*)dy,
+                hipLaunchKernelGGL((upsample2x_bwd_strip_kernel<T, VEC>), grid, dim3(256), 0, st, (const T*)dy,
                                    lddy, (T*)dx, lddx, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx, ty);
-        } else if (uh_vec_ok<T>(dy, lddy, C) && uh_vec_ok<T>(dx, lddx, C))
-            hipLaunchKernelGGL((upsample2x_bwd_kernel<T, VEC>), dim3(pu_grid(np * (C / VEC))), dim3(256), 0, st,
-                               (const T*)dy, lddy, (T*)dx, lddx, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx);
-        else
-            hipLaunchKernelGGL((upsample2x_bwd_kernel<T, 1>), dim3(pu_grid(np * C)), dim3(256), 0, st, (const T*)dy, lddy,
-                               (T*)dx, lddx, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx);
+        } else
+            uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+                hipLaunchKernelGGL((upsample2x_bwd_kernel<T, decltype(v)::value>), dim3(p.grid), dim3(256), 0, st, (const T*)dy, lddy,
+                                   (T*)dx, lddx, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx);
+            });
     });
     UH_CHECK_LAUNCH("upsample2x_bwd_kernel");
     return UH_OK;

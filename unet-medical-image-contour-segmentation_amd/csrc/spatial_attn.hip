@@ -12,7 +12,7 @@
 // lane and step) that meets by wave shuffles; the k x k correlations run on LDS tiles of the 2-channel maps; the per-channel
 // passes (gate, dx) are flat 16-byte vector loops.  The filter gradient is reduced per workgroup and finished in a fixed
 // order (no float atomics: two runs are bit-identical).  HBM-bound: DESIGN.md section 3 "Spatial attention".
-#include "uh_vec.h"
+#include "uh_launch.h"
 
 #define SA_BLOCK 256
 #define SA_DW_BLOCKS 1024          // upper bound of the filter-gradient partial rows (uh_spatial_attn_dw_nblk)
@@ -29,11 +29,8 @@ static inline unsigned sa_grid(int64_t npix, int G) {
     return (unsigned)((npix * G + SA_BLOCK - 1) / SA_BLOCK);
 }
 
-static inline unsigned sa_flat_grid(int64_t total) {
-    int64_t g = (total + SA_BLOCK - 1) / SA_BLOCK;
-    if (g > 256 * 32) g = 256 * 32;
-    return (unsigned)(g < 1 ? 1 : g);
-}
+static_assert(SA_BLOCK == 256, "uh_flat_grid counts workgroups of 256 threads");
+static inline unsigned sa_flat_grid(int64_t total) { return uh_flat_grid(total, UH_GRID_CAP_1X1); }
 
 // (m, i) beats (mo, io) as the channel maximum: larger, or NaN against a number, or equal with a lower channel index
 __device__ __forceinline__ bool sa_better(float m, int i, float mo, int io) {
@@ -303,7 +300,6 @@ static void sa_launch_fwd(const void* x, int ldx, float* pool, int* amax, const 
     const int64_t npix = (int64_t)B * H * W;
     const dim3 tiles((W + SA_TW - 1) / SA_TW, (H + SA_TH - 1) / SA_TH, B);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
         if (uh_vec_ok<T>(x, ldx, C) && (!y || uh_vec_ok<T>(y, ldy, C))) {
             const int G = sa_group(C, VEC);
             hipLaunchKernelGGL((sa_pool_kernel<T, VEC>), dim3(sa_grid(npix, G)), dim3(SA_BLOCK), 0, st, (const T*)x, ldx, pool,
@@ -333,7 +329,6 @@ static void sa_launch_bwd(const void* dy, int lddy, const float* ga, const void*
     float* gs = ws + 2 * npix;          // [npix]
     const dim3 tiles((W + SA_TW - 1) / SA_TW, (H + SA_TH - 1) / SA_TH, B);
     UH_DISPATCH_DT(dt, T, {
-        constexpr int VEC = 16 / (int)sizeof(T);
         const bool vec = uh_vec_ok<T>(dx, lddx, C) && (!dy || (uh_vec_ok<T>(dy, lddy, C) && uh_vec_ok<T>(x, ldx, C)));
         const int G = ga ? 1 : sa_group(C, vec ? VEC : 1);
         if (vec)

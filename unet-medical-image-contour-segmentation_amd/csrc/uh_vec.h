@@ -43,9 +43,9 @@ static inline bool uh_vec_ok(const void* p, int ld, int C) {
     return uh_aligned16(p) && (ld % VEC == 0) && (C % VEC == 0);
 }
 
-// Dispatch helper: calls f(std::integral_constant<int,V>) with V = VEC or 1.
-#define UH_DISPATCH_DT(dt, T, ...)                         \
-    do {                                                   \
-        if ((dt) == UH_BF16) { using T = bf16_t; __VA_ARGS__ } \
-        else { using T = float; __VA_ARGS__ }              \
+// Dispatch helper: runs the statements once with T = bf16_t (dt == UH_BF16) or float, and VEC = the elements of T in 16 bytes.
+#define UH_DISPATCH_DT(dt, T, ...)                                                                   \
+    do {                                                                                             \
+        if ((dt) == UH_BF16) { using T = bf16_t; constexpr int VEC = 8; (void)VEC; __VA_ARGS__ }     \
+        else { using T = float; constexpr int VEC = 4; (void)VEC; __VA_ARGS__ }                      \
     } while (0)
