@@ -531,6 +531,41 @@ size_t uh_contour_metrics_ws_bytes(int B, int H, int W);
 int uh_contour_metrics(const uint8_t* pred_u8, const uint8_t* true_u8, int cls_pred, int cls_true, uh_contour_record* records_out,
                        int B, int H, int W, void* ws, size_t ws_bytes, uh_stream stream);
 
+/* ---- surface loss on the device  (no counterpart in the reference; DESIGN.md section 3 "Surface loss"; csrc/surface_loss.hip) ----
+ * The distance-weighted surface loss of Kervadec et al., its maps built from the labels the step holds.  Per image b and
+ * selected class c (classes: HOST int [K], distinct ids, 1 <= K <= 8) of DEVICE int64 labels mask [B][H][W]:
+ *   T_c          (mask / mask_div == c), floor division: mask_div = 1 for a multi-class head, 2 for the binary head (BCE's target)
+ *   S(T), D_T    border and exact squared distance as the contour metrics define them (uh_edt_sq_u8 runs over K * B images)
+ *   phi_c[b,y,x] s * (float)sqrt((double)D_T[x]), s = -1 inside T_c, +1 outside; a border pixel is -0.0f; T_c empty in image b:
+ *                phi_c[b] = +0.0f everywhere and the image has no gradient for that class
+ *   surface      1 / (n_mean K) * sum_b sum_x sum_{c in C} p_c(x) phi_c(x), p = sigmoid(z) (ncls = 1) or softmax(z)_c (2 <= ncls <= 8)
+ *   binary       dL/dz   = g w / n_mean * phi * sigma (1 - sigma), sigma = sigmoid(z)
+ *   multi-class  dL/dz_k = g w / (n_mean K) * p_k * (phi_k [k in C] - sum_{c in C} p_c phi_c)
+ * n_mean = pixel count of the mean (B H W of the GLOBAL batch when sharded); g = gscale[0], a device pointer (NULL = 1), as in
+ * uh_bce_dice_grad.  Products and sums of the value in fp64, per-workgroup partials and a one-workgroup finish in a fixed order, no
+ * floating-point atomics: the same bits on every call; a pixel's gradient depends on its own logits and its own image's labels only.
+ * Limits: those of uh_edt_sq_u8 over K * B images (H, W <= 32768, H W < 2^31, K B <= 65535); UH_EINVAL otherwise, and for a null
+ * pointer, K < 1, a class id outside [0, ncls) for a softmax head (any id >= 0 where there is no head; the sigmoid head takes
+ * K = 1 and the id is a value of the target mask / mask_div, 1 for the foreground), ncls outside 1..8.
+ * uh_surface_border_i64: border_out DEVICE uint8 [K][B][H][W] = 1 on S(T_k), all K classes in one launch, no uint8 copy of the labels.
+ * uh_surface_dist_map:   phi_out DEVICE fp32 [K][B][H][W] (border, distance, map).
+ * uh_surface_loss_sums:  logits fp32 [B][H][W] (ncls = 1) or [npix][ncls]; out[0] = surface, out[1] = w * surface (after a sum over
+ *   data-parallel ranks they are the global batch's).  Leaves D in the workspace for uh_surface_loss_grad.
+ * uh_surface_loss_grad:  WRITES dlogits (every element; autograd owns the sum over the loss nodes).  rebuild = 0: D is what
+ *   uh_surface_loss_sums left in this workspace for the same labels and classes; rebuild != 0: border and distance are formed
+ *   again first (another call used the workspace in between).  No fp32 map is written.
+ * ws: uh_surface_loss_ws_bytes(B, H, W, K) bytes, 16-byte aligned: D, the border masks, the EDT's workspace and the partials. */
+size_t uh_surface_loss_ws_bytes(int B, int H, int W, int K);
+int uh_surface_border_i64(const int64_t* mask, int mask_div, const int* classes, int K, uint8_t* border_out, int B, int H, int W,
+                          uh_stream stream);
+int uh_surface_dist_map(const int64_t* mask, int mask_div, const int* classes, int K, float* phi_out, int B, int H, int W,
+                        void* ws, size_t ws_bytes, uh_stream stream);
+int uh_surface_loss_sums(const float* logits, const int64_t* mask, int mask_div, const int* classes, int K, int ncls, int B, int H,
+                         int W, double n_mean, float w, float* out, void* ws, size_t ws_bytes, uh_stream stream);
+int uh_surface_loss_grad(const float* logits, const int64_t* mask, int mask_div, const int* classes, int K, int ncls, int B, int H,
+                         int W, double n_mean, float w, const float* gscale, float* dlogits, int rebuild, void* ws,
+                         size_t ws_bytes, uh_stream stream);
+
 /* ---- input pipeline, device stage  (utils/data_loading.py:65-132, train.py:113-114) ---------------------------
  * What BasicDataset.__getitem__ does to a DECODED image / mask pair, for a whole batch in one pass:
  *   img_u8   DEVICE uint8 [B][Hin][Win][C] (C = 1..4, what np.asarray(PIL image) holds), or NULL (masks only)

@@ -1900,3 +1900,131 @@ def contour_metrics(pred_u8: torch.Tensor, true_u8: torch.Tensor, cls_pred: int,
     LIB.call("uh_contour_metrics", pred_u8.data_ptr(), true_u8.data_ptr(), int(cls_pred), int(cls_true), rec.data_ptr(), B, H, W,
              ws.data_ptr(), ws.numel(), _stream())
     return rec
+
+
+# ----------------------------------------------------------------------------- surface loss (csrc/surface_loss.hip)
+SURFACE_MAX_CLASSES = 8
+_SURFACE_WS = {}
+
+
+class _SurfaceWorkspace:
+    """One workspace per (shape, K, device, stream): it carries the squared distances from the value to the gradient of the same
+    step.  `generation` counts the value passes that wrote it: a backward that finds another generation than its forward's
+    (two losses of one shape in flight) has the distances formed again instead of reading someone else's."""
+
+    def __init__(self, nbytes: int, device):
+        self.buf = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        self.generation = 0
+
+
+def _surface_workspace(B: int, H: int, W: int, K: int, device) -> _SurfaceWorkspace:
+    key = (B, H, W, K, device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _SURFACE_WS.get(key)
+    if ws is None:
+        ws = _SURFACE_WS[key] = _SurfaceWorkspace(LIB.query("uh_surface_loss_ws_bytes", B, H, W, K), device)
+    return ws
+
+
+def surface_classes(classes, n_classes: Optional[int] = None) -> Tuple[int, ...]:
+    """The selected classes as a checked tuple of distinct ids (below n_classes where a head is given)."""
+    try:
+        cls = tuple(int(c) for c in classes)
+    except TypeError:
+        cls = (int(classes),)
+    if not 1 <= len(cls) <= SURFACE_MAX_CLASSES:
+        raise ValueError(f"surface loss: 1 to {SURFACE_MAX_CLASSES} classes, got {cls}")
+    if len(set(cls)) != len(cls) or min(cls) < 0 or (n_classes is not None and max(cls) >= n_classes):
+        raise ValueError(f"surface loss: classes {cls} must be distinct ids in [0, {n_classes if n_classes is not None else 'inf'})")
+    return cls
+
+
+def _class_array(cls: Tuple[int, ...]):
+    return (ctypes.c_int * len(cls))(*cls)
+
+
+def _label_batch(mask: torch.Tensor) -> torch.Tensor:
+    _require_gpu(mask, "labels")
+    if mask.dim() != 3:
+        raise RuntimeError(f"labels are [B,H,W], got {tuple(mask.shape)}")
+    mk = mask.contiguous()
+    return mk if mk.dtype == torch.int64 else mk.long()
+
+
+def surface_border(mask: torch.Tensor, classes, mask_div: int = 1) -> torch.Tensor:
+    """uint8 [K,B,H,W]: 1 on the border of (mask // mask_div == classes[k]), straight from the int64 labels."""
+    cls = surface_classes(classes)
+    mk = _label_batch(mask)
+    B, H, W = mk.shape
+    out = torch.empty(len(cls), B, H, W, dtype=torch.uint8, device=mk.device)
+    LIB.call("uh_surface_border_i64", mk.data_ptr(), int(mask_div), _class_array(cls), len(cls), out.data_ptr(), B, H, W, _stream())
+    return out
+
+
+def surface_dist_map(mask: torch.Tensor, classes, mask_div: int = 1) -> torch.Tensor:
+    """fp32 [K,B,H,W]: the signed distance of every pixel to the contour of (mask // mask_div == classes[k]) in its image,
+    negative inside, -0.0 on the border pixels, +0.0 everywhere in an image without the class."""
+    cls = surface_classes(classes)
+    mk = _label_batch(mask)
+    B, H, W = mk.shape
+    ws = _surface_workspace(B, H, W, len(cls), mk.device)
+    ws.generation += 1                                             # the distances in the workspace are no longer a loss's
+    out = torch.empty(len(cls), B, H, W, dtype=torch.float32, device=mk.device)
+    LIB.call("uh_surface_dist_map", mk.data_ptr(), int(mask_div), _class_array(cls), len(cls), out.data_ptr(), B, H, W,
+             ws.buf.data_ptr(), ws.buf.numel(), _stream())
+    return out
+
+
+class SurfaceLossFn(Function):
+    """The surface loss of DESIGN.md section 3 in one node: logits [B,H,W] (ncls = 1, sigmoid; target mask // mask_div) or NHWC
+    [B,H,W,C] (softmax), int64 labels [B,H,W], `classes` a tuple of distinct ids.  Returns (w * surface, surface) as 0-dim
+    tensors; the first carries the gradient, the second is the logged term.  `reduce_sums` sums the pair over data-parallel ranks
+    (the value is normalised by the GLOBAL pixel count n * world; the gradient needs no collective).  Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, logits, mask, mask_div: int, classes, weight: float, reduce_sums=None, world: float = 1):
+        _require_gpu(logits, "logits")
+        lg = logits.float().contiguous()
+        mk = _label_batch(mask)
+        B, H, W = mk.shape
+        ncls = 1 if lg.dim() == 3 else int(lg.shape[-1])
+        if lg.dim() not in (3, 4) or tuple(lg.shape[:3]) != (B, H, W):
+            raise RuntimeError(f"surface loss expects logits [B,H,W] or [B,H,W,C] matching labels {tuple(mk.shape)}, got "
+                               f"{tuple(logits.shape)}")
+        cls = surface_classes(classes, ncls if ncls > 1 else None)         # sigmoid head: the id is a value of mask // mask_div
+        if ncls == 1 and len(cls) != 1:
+            raise ValueError(f"surface loss: the sigmoid head has one map, got classes {cls}")
+        n_mean = float(round(B * H * W * world))
+        ws = _surface_workspace(B, H, W, len(cls), lg.device)
+        out = torch.empty(2, dtype=torch.float32, device=lg.device)
+        ws.generation += 1
+        LIB.call("uh_surface_loss_sums", lg.data_ptr(), mk.data_ptr(), int(mask_div), _class_array(cls), len(cls), ncls, B, H, W,
+                 n_mean, float(weight), out.data_ptr(), ws.buf.data_ptr(), ws.buf.numel(), _stream())
+        if reduce_sums is not None:
+            reduce_sums(out)
+        ctx.save_for_backward(lg, mk)
+        ctx.meta = (int(mask_div), cls, ncls, n_mean, float(weight), ws, ws.generation, logits.shape, logits.dtype)
+        ctx.set_materialize_grads(False)
+        value, weighted = out[0], out[1]
+        ctx.mark_non_differentiable(value)
+        return weighted, value
+
+    @staticmethod
+    def backward(ctx, g_weighted, *_unused):
+        if g_weighted is None:
+            return (None,) * 7
+        lg, mk = ctx.saved_tensors
+        mask_div, cls, ncls, n_mean, weight, ws, generation, shape, dtype = ctx.meta
+        B, H, W = mk.shape
+        g0 = g_weighted.reshape(1)
+        if g0.dtype != torch.float32 or not g0.is_contiguous():
+            g0 = g0.contiguous().float()
+        rebuild = ws.generation != generation
+        if rebuild:
+            ws.generation += 1
+        dl = torch.empty_like(lg)
+        LIB.call("uh_surface_loss_grad", lg.data_ptr(), mk.data_ptr(), mask_div, _class_array(cls), len(cls), ncls, B, H, W, n_mean,
+                 weight, g0.data_ptr(), dl.data_ptr(), int(rebuild), ws.buf.data_ptr(), ws.buf.numel(), _stream())
+        dl = dl.view(shape)
+        if dtype != torch.float32:
+            dl = dl.to(dtype)
+        return dl, None, None, None, None, None, None

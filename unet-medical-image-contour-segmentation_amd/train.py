@@ -26,10 +26,25 @@ from ._lib import LIB
 
 
 # ----------------------------------------------------------------------------------- loss
+def _add_surface(terms: Dict[str, torch.Tensor], lg: torch.Tensor, true_masks: torch.Tensor, n_classes: int, weight: float,
+                 classes, reduce_sums, world) -> Dict[str, torch.Tensor]:
+    """total += weight * surface (DESIGN.md section 3 "Surface loss"); `surface` joins the reported terms.  The fused loss's
+    NaN flag was formed without the new term and is dropped: train_step tests the new total itself."""
+    from .utils.surface_loss import head_classes
+    weighted, value = ops.SurfaceLossFn.apply(lg, true_masks, 2 if n_classes == 1 else 1, head_classes(n_classes, classes),
+                                              float(weight), reduce_sums, world)
+    terms["loss"] = terms["loss"] + weighted
+    terms["surface"] = value
+    terms.pop("nan_flag", None)
+    return terms
+
+
 def seg_loss(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int, *, reduce_sums=None, world: float = 1,
-             boundary_weight: Optional[float] = None) -> Dict[str, torch.Tensor]:
+             boundary_weight: Optional[float] = None, surface_weight: float = 0.0, surface_classes=None) -> Dict[str, torch.Tensor]:
     """train.py:118-142.  masks_pred: logits [B,n_classes,H,W] (as returned by the model);
-    true_masks: int64 [B,H,W] with the dataset's values {0,1,2,..} (NOT yet // 2)."""
+    true_masks: int64 [B,H,W] with the dataset's values {0,1,2,..} (NOT yet // 2).
+    surface_weight != 0 adds surface_weight * surface loss over `surface_classes` (default: the class evaluate scores) and the
+    term "surface"; with 0 nothing else is launched and the result is what it is without the option."""
     if n_classes == 1:
         w_b = 0.25 if boundary_weight is None else boundary_weight          # train.py:134
         lg = masks_pred.squeeze(1)
@@ -37,11 +52,16 @@ def seg_loss(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int,
         terms = {"loss": total, "bce": bce, "dice": dice, "boundary": bnd}
         if nan_flag is not None:
             terms["nan_flag"] = nan_flag          # float 0 / 1 written by the loss's finishing block (train.py:149)
+        if surface_weight:
+            _add_surface(terms, lg, true_masks, 1, surface_weight, surface_classes, reduce_sums, world)
         return terms
     w_b = 0.0 if boundary_weight is None else boundary_weight               # train.py:143-147 is commented out
     lg = masks_pred.permute(0, 2, 3, 1)
     out = ops.SegLossMulticlassFn.apply(lg, true_masks, w_b, 51, 7.0, reduce_sums, world)
-    return {"loss": out[0], "ce": out[1].detach(), "dice": out[2].detach(), "boundary": out[3].detach()}
+    terms = {"loss": out[0], "ce": out[1].detach(), "dice": out[2].detach(), "boundary": out[3].detach()}
+    if surface_weight:
+        _add_surface(terms, lg, true_masks, n_classes, surface_weight, surface_classes, reduce_sums, world)
+    return terms
 
 
 # ----------------------------------------------------------------------------------- optimizer
@@ -338,16 +358,18 @@ def _pinned_flag(device, n: int = 1) -> torch.Tensor:
 
 def train_step(model: nn.Module, optimizer, images: torch.Tensor, true_masks: torch.Tensor, *, amp: bool = True,
                gradient_clipping: float = 1.0, reduce_sums=None, world: int = 1, check_nan: bool = True,
-               boundary_weight: Optional[float] = None, cc_loss: bool = False) -> Dict[str, torch.Tensor]:
+               boundary_weight: Optional[float] = None, cc_loss: bool = False, surface_weight: float = 0.0,
+               surface_classes=None) -> Dict[str, torch.Tensor]:
     """Statement sequence of train.py:113-159.  `optimizer` is a FusedRMSprop (clipping fused into
-    its step) or any torch.optim optimizer (then clip_grad_norm_ is applied as in the reference)."""
+    its step) or any torch.optim optimizer (then clip_grad_norm_ is applied as in the reference).
+    surface_weight / surface_classes: the surface term of seg_loss (0: off, the step is what it is without the option)."""
     assert images.shape[1] == model.n_channels, \
         f"Network has been defined with {model.n_channels} input channels, but loaded images have " \
         f"{images.shape[1]} channels. Please check that the images are loaded correctly."   # train.py:108-111
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
         masks_pred = model(images)
         terms = seg_loss(masks_pred, true_masks, model.n_classes, reduce_sums=reduce_sums, world=world,
-                         boundary_weight=boundary_weight)
+                         boundary_weight=boundary_weight, surface_weight=surface_weight, surface_classes=surface_classes)
     if cc_loss and model.n_classes == 1:
         # the block train.py:124-132 keeps commented out (BASELINE config 5 turns it on): a Python float, no gradient.
         # sigmoid(x) > 0.5 <=> x > 0, so the 0/1 threshold mask stands in for the probabilities.  The masks stay on the
@@ -409,8 +431,12 @@ class TrainStepper:
 
     def __init__(self, model: nn.Module, lr: float = 1e-5, weight_decay: float = 1e-8, momentum: float = 0.999,
                  gradient_clipping: float = 1.0, amp: bool = True, process_group=None, check_nan: bool = True,
-                 wgrad_stream: Optional[bool] = None, cc_loss: bool = False, sync_bn: bool = False, fp32_mode: str = "exact"):
+                 wgrad_stream: Optional[bool] = None, cc_loss: bool = False, sync_bn: bool = False, fp32_mode: str = "exact",
+                 surface_weight: float = 0.0, surface_classes=None):
         self.model = model
+        # the surface term of seg_loss; a plain attribute: the epoch loop may change the weight between steps (0 = off)
+        self.surface_weight = float(surface_weight)
+        self.surface_classes = surface_classes
         # wgrad_stream: backward-weights kernels (and their slab reductions) on a stream of their own, beside the BatchNorm /
         # pool / upsample backward kernels of the layers that follow.  True / False force it; None (default) decides per step
         # (`_side_for`): ON for bf16 steps of at least 2^20 pixels per process.  Round 2 measured one stream 2-3 % faster and
@@ -530,7 +556,8 @@ class TrainStepper:
         ops.SLAB_BATCH = self._slabs if side is None else None
         try:
             return train_step(self.model, self.optimizer, images, true_masks, amp=self.amp,
-                              reduce_sums=self.reduce_sums, world=world, check_nan=self.check_nan, cc_loss=self.cc_loss)
+                              reduce_sums=self.reduce_sums, world=world, check_nan=self.check_nan, cc_loss=self.cc_loss,
+                              surface_weight=self.surface_weight, surface_classes=self.surface_classes)
         finally:
             ops.SLAB_BATCH = None
             ops.FP32_MODE = fp32_mode_before
@@ -549,9 +576,14 @@ class GraphedTrainStepper(TrainStepper):
             raise RuntimeError("GraphedTrainStepper is single-process; use TrainStepper with torch.distributed")
         if self.cc_loss:
             raise RuntimeError("connected_component_loss returns a Python float (a device read-back every step): not capturable")
+        self._refuse_surface()
         self._warmup = max(1, warmup)
         self._graph = None
         self._key = None
+
+    def _refuse_surface(self):
+        if self.surface_weight:
+            raise RuntimeError("GraphedTrainStepper does not capture the surface loss (surface_weight must be 0): use TrainStepper")
 
     def _eager_step(self, images, masks):
         self.model.train()
@@ -602,6 +634,7 @@ class GraphedTrainStepper(TrainStepper):
         self._key = (tuple(images.shape), tuple(masks.shape), float(opt.param_groups[0]["lr"]))
 
     def step(self, images, true_masks):
+        self._refuse_surface()
         key = (tuple(images.shape), tuple(true_masks.shape), float(self.optimizer.param_groups[0]["lr"]))
         if self._graph is None or key != self._key:
             self._capture(images, true_masks)

@@ -2,7 +2,7 @@
 
     python -m unet_amd.train -e 5 -b 1 -l 1e-5 -s 0.5 -c 3 [--bilinear] [-f model.pth] [--no-amp]
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
-                             [--pred-dir DIR] [--metrics] [--augment [SPEC]]
+                             [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--surface-loss [SPEC]]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -19,6 +19,10 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
   - --augment [SPEC] (default: off) passes every TRAINING batch through the seeded device augmentation of utils/augment.py
     (csrc/augment.hip): flips, rotation, scale, shift, brightness, contrast, gamma, noise, drawn per (seed, epoch, item);
     bare --augment is the preset 'default', SPEC is e.g. "flip,rotate=15,scale=0.1,noise=0.01".  Validation is never augmented;
+  - --surface-loss [W[,ramp=R][,classes=a+b]] (default: off) adds the distance-weighted surface loss (utils/surface_loss.py,
+    csrc/surface_loss.hip) to every training step, its distance maps rebuilt on the device from the step's own (augmented)
+    labels.  The weight of epoch e (1-based) is min(1, W + R (e - 1)); bare --surface-loss is "0.01,ramp=0.01"; classes default
+    to the one evaluate scores.  One log line per epoch gives the weight, the epoch line the summed term;
   - --load drops mask_values (train.py:275-280); -v is accepted and unused, as in the reference.
 Input batches come from DeviceBatchLoader: decode threads, pinned collation, rotation + BICUBIC / NEAREST rescale + /255
 + label remap on the device (csrc/data_rescale.hip, csrc/data_prep.hip), bit-identical to stacking ds[i].
@@ -33,11 +37,66 @@ import os
 import sys
 import time
 from pathlib import Path
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
 MODELS = ("UNet_S", "UNet", "UNet_T", "UNet_SA")
+
+
+class SurfaceSpec(NamedTuple):
+    """--surface-loss: the weight of epoch 1, its growth per epoch, the selected classes (None: the class evaluate scores)."""
+    weight: float
+    ramp: float = 0.0
+    classes: Optional[Tuple[int, ...]] = None
+
+
+SURFACE_BARE = "0.01,ramp=0.01"
+
+
+def parse_surface_spec(text: str) -> SurfaceSpec:
+    """"W[,ramp=R][,classes=a+b]" -> SurfaceSpec; ValueError names what is wrong."""
+    parts = [t.strip() for t in str(text).split(",")]
+    if not parts or not parts[0]:
+        raise ValueError("the weight is missing")
+    try:
+        weight = float(parts[0])
+    except ValueError:
+        raise ValueError(f"weight {parts[0]!r} is not a number") from None
+    if not math.isfinite(weight) or weight < 0.0:
+        raise ValueError(f"weight {parts[0]!r} must be finite and >= 0")
+    ramp, classes, seen = 0.0, None, set()
+    for tok in parts[1:]:
+        key, eq, val = tok.partition("=")
+        if not eq or not val or key not in ("ramp", "classes"):
+            raise ValueError(f"{tok!r} is not ramp=R or classes=a+b")
+        if key in seen:
+            raise ValueError(f"{key} is given twice")
+        seen.add(key)
+        try:
+            if key == "ramp":
+                ramp = float(val)
+            else:
+                classes = tuple(int(v) for v in val.split("+"))
+        except ValueError:
+            raise ValueError(f"{tok!r} does not parse") from None
+    if not math.isfinite(ramp) or ramp < 0.0:
+        raise ValueError("ramp must be finite and >= 0")
+    if classes is not None and (min(classes) < 0 or len(set(classes)) != len(classes)):
+        raise ValueError("classes must be distinct ids >= 0")
+    return SurfaceSpec(weight, ramp, classes)
+
+
+def _surface_arg(text: str) -> SurfaceSpec:
+    try:
+        return parse_surface_spec(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"bad --surface-loss {text!r}: {e}") from None
+
+
+def surface_weight_at(spec: SurfaceSpec, epoch: int) -> float:
+    """The surface weight of epoch `epoch` (1-based): min(1, W + R (epoch - 1))."""
+    return min(1.0, spec.weight + spec.ramp * (int(epoch) - 1))
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -68,6 +127,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--augment", nargs="?", const="default", default=None, metavar="SPEC",
                    help="Augment the training batches on the device: a preset name or e.g. 'flip,rotate=15,scale=0.1,"
                         "translate=0.05,brightness=0.1,contrast=0.1,gamma=0.2,noise=0.01' (bare flag: 'default'; default: off)")
+    p.add_argument("--surface-loss", dest="surface_loss", nargs="?", const=SURFACE_BARE, default=None, type=_surface_arg,
+                   metavar="W[,ramp=R][,classes=a+b]",
+                   help="Add W * surface loss (distance to the true contour, maps built on the device each step); the weight of "
+                        f"epoch e is min(1, W + R (e - 1)) (bare flag: '{SURFACE_BARE}'; default: off)")
     return p
 
 
@@ -106,12 +169,14 @@ def build_model(name: str, n_classes: int, bilinear: bool):
 def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: int, learning_rate: float, amp: bool,
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
                  train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
-                 augment=None) -> List[Dict]:
+                 augment=None, surface: Optional[SurfaceSpec] = None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
     `augment`: an AugmentConfig, a spec string or a BatchAugment for the TRAIN loader (a config is seeded with the loader's
-    seed: `seed`, or the loader's own draw when unseeded); the validation loader never gets one."""
+    seed: `seed`, or the loader's own draw when unseeded); the validation loader never gets one.
+    `surface`: a SurfaceSpec; every epoch's steps run with surface_weight_at(surface, epoch), and the record gains the weight
+    and the summed term."""
     from .evaluate import evaluate
     from .checkpoint import save_checkpoint
     from .train import TrainStepper, cosine_warm_restarts_lr
@@ -128,13 +193,17 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
         if log:
             log(f"Training augmentation (seed {augment.seed}): {augment.config.spec()}")
     val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
-    stepper = TrainStepper(model, lr=learning_rate, amp=amp)
+    stepper = TrainStepper(model, lr=learning_rate, amp=amp, surface_classes=surface.classes if surface is not None else None)
     lr = learning_rate
     global_step = 0
     history = []
     for epoch in range(1, epochs + 1):
         model.train()
-        losses = []
+        losses, surfaces = [], []
+        if surface is not None:
+            stepper.surface_weight = surface_weight_at(surface, epoch)
+            if log:
+                log(f"Epoch {epoch}/{epochs}: surface loss weight {stepper.surface_weight:.6g}")
         dice = (None, None, None)
         eval_s = 0.0
         seen = 0
@@ -144,6 +213,8 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
             images, true_masks = batch["image"], batch["mask"]
             terms = stepper.step(images, true_masks)
             losses.append(terms["loss"].detach())
+            if "surface" in terms:
+                surfaces.append(terms["surface"].detach())
             seen += images.shape[0]
             global_step += 1
             if eval_due(global_step, n_train, batch_size):
@@ -172,6 +243,9 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
             epoch_loss += v                                                                      # loss.item() summed
         rec = {"epoch": epoch, "loss": epoch_loss, "val_dice": dice[0], "val_dice_post": dice[1], "val_dice_min": dice[2],
                "lr": lr, "images": seen, "img_s": seen / max(wall - eval_s, 1e-9), "eval_s": eval_s}
+        if surface is not None:
+            rec["surface_weight"] = stepper.surface_weight
+            rec["surface"] = float(torch.stack(surfaces).double().sum().item()) if surfaces else 0.0
         if checkpoint_dir is not None and checkpoint_due(epoch, epochs):
             path = os.path.join(checkpoint_dir, f"checkpoint_epoch{epoch}.pth")
             save_checkpoint(model, path, mask_values=train_set.mask_values + val_set.mask_values)
@@ -180,6 +254,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
         if log:
             log(f"Epoch {epoch}/{epochs}: loss (total) {epoch_loss:.6g}, Dice {dice[0]} / post {dice[1]} / min {dice[2]}, "
                 f"lr {lr:.6g}, {rec['img_s']:.1f} images/s ({seen} images, evaluation {eval_s:.2f} s)"
+                + (f", surface (summed) {rec['surface']:.6g} at weight {rec['surface_weight']:.6g}" if "surface" in rec else "")
                 + (f", checkpoint {rec['checkpoint']}" if "checkpoint" in rec else ""))
     stepper.close()
     return history
@@ -200,6 +275,13 @@ def main(argv=None) -> int:
     if args.augment is not None:
         from .utils.augment import AugmentConfig
         augment = AugmentConfig.parse(args.augment)                           # a bad spec fails before anything is loaded
+    if args.surface_loss is not None:
+        from .utils.surface_loss import head_classes
+        try:
+            head_classes(args.classes, args.surface_loss.classes)             # against the head, before anything is loaded
+        except ValueError as e:
+            logging.error(f"train: --surface-loss: {e}")
+            return 2
     train_set = BasicDataset(root / "imgs" / "train", root / "masks" / "train", args.scale)
     val_set = BasicDataset(root / "imgs" / "val", root / "masks" / "val", args.scale)
     if args.seed is not None:
@@ -218,7 +300,7 @@ def main(argv=None) -> int:
                  f"{'bf16 autocast' if args.amp else 'fp32'}, checkpoints in {args.checkpoint_dir}")
     run_training(model, device, train_set, val_set, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.lr,
                  amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed, workers=args.workers, log=logging.info,
-                 pred_dir=args.pred_dir, metrics=args.metrics, augment=augment)
+                 pred_dir=args.pred_dir, metrics=args.metrics, augment=augment, surface=args.surface_loss)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")
