@@ -627,6 +627,22 @@ typedef struct uh_augment_params {
 int uh_batch_augment(const void* image_in, int ld_in, const int64_t* labels_in, const uh_augment_params* params, void* image_out,
                      int ld_out, int64_t* labels_out, int B, int H, int W, int C, int dt, int border, float fill_image,
                      int fill_label, uh_stream stream);
+/* uh_batch_augment_elastic: uh_batch_augment with an elastic deformation (DESIGN.md section 3 "Elastic deformation"): a cubic
+ * B-spline displacement field is added to the Q16 source position q of the affine walk, evaluated at the OUTPUT pixel; from
+ * q' = q + displacement on everything is uh_batch_augment (labels, bilinear image, borders, photometry, noise).
+ *   grid      control-point spacing in pixels, a multiple of 16 in [16, 256]; GW = ceil(W / grid) + 3, GH = ceil(H / grid) + 3
+ *   control   DEVICE int32 [B][GH][GW][2]: (dx, dy) of every control point in Q16 pixels, control point k of an axis at
+ *             position (k - 1) grid.  Values are clamped to |d| < 2^22 on load.
+ *   weights   DEVICE int32 [grid][4], 16-byte aligned: row n the uniform cubic B-spline basis at t = (n + 0.5) / grid in Q20,
+ *             every row summing to 2^20 (utils/augment.py: elastic_weights).  Values are clamped to [0, 2^20] on load.
+ *   With cx = x / grid, nx = x % grid, cy = y / grid, ny = y % grid, per component, in int64 with arithmetic shifts:
+ *     r_k = (sum_j weights[nx][j] control[cy + k][cx + j] + 2^19) >> 20   (k = 0..3),
+ *     displacement = (sum_k weights[ny][k] r_k + 2^19) >> 20.
+ *   Source addresses stay inside the image whatever the tables hold. */
+int uh_batch_augment_elastic(const void* image_in, int ld_in, const int64_t* labels_in, const uh_augment_params* params,
+                             const int32_t* control, const int32_t* weights, int grid, void* image_out, int ld_out,
+                             int64_t* labels_out, int B, int H, int W, int C, int dt, int border, float fill_image, int fill_label,
+                             uh_stream stream);
 
 /* ---- RAW -> contour pipeline, non-inference stages  (seg_main.py; utils/raw2png.py, png_normalize.py, png_denormalize.py,
  * mask2polygon.py).  Batched over B images of one geometry.

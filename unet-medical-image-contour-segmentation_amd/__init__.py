@@ -13,7 +13,7 @@ from .predict import predict_img, mask_to_image, preprocess_image, BatchPredicto
 from .checkpoint import save_checkpoint, load_checkpoint  # noqa: F401
 from .synthetic import ellipse_batch  # noqa: F401
 from .utils.data_loading import BasicDataset, CarvanaDataset, load_image  # noqa: F401
-from .utils.augment import AugmentConfig, BatchAugment  # noqa: F401
+from .utils.augment import AugmentConfig, BatchAugment, ElasticConfig  # noqa: F401
 from .utils.post_process import postprocess_mask, remove_internal_regions  # noqa: F401
 from .inference import GraphedForward  # noqa: F401
 from .utils.raw2png import read_raw, window_level  # noqa: F401

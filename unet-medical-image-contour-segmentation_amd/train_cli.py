@@ -2,7 +2,7 @@
 
     python -m unet_amd.train -e 5 -b 1 -l 1e-5 -s 0.5 -c 3 [--bilinear] [-f model.pth] [--no-amp]
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
-                             [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--surface-loss [SPEC]]
+                             [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--elastic [SPEC]] [--surface-loss [SPEC]]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -19,6 +19,10 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
   - --augment [SPEC] (default: off) passes every TRAINING batch through the seeded device augmentation of utils/augment.py
     (csrc/augment.hip): flips, rotation, scale, shift, brightness, contrast, gamma, noise, drawn per (seed, epoch, item);
     bare --augment is the preset 'default', SPEC is e.g. "flip,rotate=15,scale=0.1,noise=0.01".  Validation is never augmented;
+  - --elastic [SPEC] (default: off) adds a smooth elastic deformation to the same launch: random displacements on a coarse
+    control grid, cubic B-spline interpolation, image and labels warped together, drawn per (seed, epoch, item); bare
+    --elastic is the preset 'default' ("grid=64,sigma=4"), SPEC is "grid=G,sigma=S[,p=P]" with 8 S < G.  It works with or
+    without --augment (without it the affine map is the identity).  Validation is never deformed;
   - --surface-loss [W[,ramp=R][,classes=a+b]] (default: off) adds the distance-weighted surface loss (utils/surface_loss.py,
     csrc/surface_loss.hip) to every training step, its distance maps rebuilt on the device from the step's own (augmented)
     labels.  The weight of epoch e (1-based) is min(1, W + R (e - 1)); bare --surface-loss is "0.01,ramp=0.01"; classes default
@@ -127,6 +131,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--augment", nargs="?", const="default", default=None, metavar="SPEC",
                    help="Augment the training batches on the device: a preset name or e.g. 'flip,rotate=15,scale=0.1,"
                         "translate=0.05,brightness=0.1,contrast=0.1,gamma=0.2,noise=0.01' (bare flag: 'default'; default: off)")
+    p.add_argument("--elastic", nargs="?", const="default", default=None, metavar="SPEC",
+                   help="Deform the training batches elastically on the device: a preset name or 'grid=64,sigma=4[,p=1]' "
+                        "(control spacing and displacement sigma in pixels, 8 sigma < grid; bare flag: 'default'; default: off)")
     p.add_argument("--surface-loss", dest="surface_loss", nargs="?", const=SURFACE_BARE, default=None, type=_surface_arg,
                    metavar="W[,ramp=R][,classes=a+b]",
                    help="Add W * surface loss (distance to the true contour, maps built on the device each step); the weight of "
@@ -169,12 +176,13 @@ def build_model(name: str, n_classes: int, bilinear: bool):
 def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: int, learning_rate: float, amp: bool,
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
                  train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
-                 augment=None, surface: Optional[SurfaceSpec] = None) -> List[Dict]:
+                 augment=None, surface: Optional[SurfaceSpec] = None, elastic=None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
     `augment`: an AugmentConfig, a spec string or a BatchAugment for the TRAIN loader (a config is seeded with the loader's
     seed: `seed`, or the loader's own draw when unseeded); the validation loader never gets one.
+    `elastic`: an ElasticConfig or a spec string, added to that augmenter; alone, it deforms over the identity affine map.
     `surface`: a SurfaceSpec; every epoch's steps run with surface_weight_at(surface, epoch), and the record gains the weight
     and the summed term."""
     from .evaluate import evaluate
@@ -185,13 +193,17 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     if train_loader is None:
         train_loader = DeviceBatchLoader(train_set, batch_size, shuffle=True, drop_last=False, seed=seed, workers=workers,
                                          device=device)
-    if augment is not None:
-        from .utils.augment import BatchAugment
-        if not isinstance(augment, BatchAugment):
-            augment = BatchAugment(augment, train_loader.seed)
+    if augment is not None or elastic is not None:
+        from .utils.augment import AugmentConfig, BatchAugment
+        if isinstance(augment, BatchAugment):
+            if elastic is not None:
+                raise ValueError("run_training: a BatchAugment carries its own elastic configuration")
+        else:
+            augment = BatchAugment(augment if augment is not None else AugmentConfig(), train_loader.seed, elastic=elastic)
         train_loader.augment = augment
         if log:
-            log(f"Training augmentation (seed {augment.seed}): {augment.config.spec()}")
+            log(f"Training augmentation (seed {augment.seed}): {augment.config.spec()}"
+                + (f"; elastic {augment.elastic.spec()}" if augment.elastic is not None else ""))
     val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
     stepper = TrainStepper(model, lr=learning_rate, amp=amp, surface_classes=surface.classes if surface is not None else None)
     lr = learning_rate
@@ -275,6 +287,10 @@ def main(argv=None) -> int:
     if args.augment is not None:
         from .utils.augment import AugmentConfig
         augment = AugmentConfig.parse(args.augment)                           # a bad spec fails before anything is loaded
+    elastic = None
+    if args.elastic is not None:
+        from .utils.augment import ElasticConfig
+        elastic = ElasticConfig.parse(args.elastic)                           # likewise
     if args.surface_loss is not None:
         from .utils.surface_loss import head_classes
         try:
@@ -300,7 +316,7 @@ def main(argv=None) -> int:
                  f"{'bf16 autocast' if args.amp else 'fp32'}, checkpoints in {args.checkpoint_dir}")
     run_training(model, device, train_set, val_set, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.lr,
                  amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed, workers=args.workers, log=logging.info,
-                 pred_dir=args.pred_dir, metrics=args.metrics, augment=augment, surface=args.surface_loss)
+                 pred_dir=args.pred_dir, metrics=args.metrics, augment=augment, surface=args.surface_loss, elastic=elastic)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")
