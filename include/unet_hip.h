@@ -445,6 +445,19 @@ int uh_grad_sumsq(const float* g, int64_t n, float* norm_out, void* ws, size_t w
 int uh_rmsprop_step(float* p, float* g, float* square_avg, float* momentum_buf, int64_t n,
                     const float* total_norm, float max_norm, float lr, float alpha, float eps,
                     float weight_decay, float momentum, uh_stream stream);
+/* uh_rmsprop_step_ema: the same pass with one more stream, the exponential moving average of the parameters:
+ * ema += c * (p_new - ema), c = 1 - d_t, d_t = warmup > 0 ? min(decay, (1 + t) / (warmup + t)) : decay, all in fp32,
+ * t = updates[0] read on the device (the step may be replayed from a captured graph).  What it writes to p, g,
+ * square_avg and momentum_buf is bit-identical to uh_rmsprop_step; a non-finite total_norm leaves ema untouched too.
+ * uh_ema_tick: updates[0] += 1 unless total_norm[0] is not finite (total_norm may be NULL); once per optimizer step,
+ * behind its uh_rmsprop_step_ema launches.
+ * uh_swap_f32: exchanges two disjoint 16-byte aligned buffers of n floats (averaged weights in and out of the model). */
+int uh_rmsprop_step_ema(float* p, float* g, float* square_avg, float* momentum_buf, float* ema, int64_t n,
+                        const float* total_norm, float max_norm, float lr, float alpha, float eps,
+                        float weight_decay, float momentum, float decay, int warmup, const int32_t* updates,
+                        uh_stream stream);
+int uh_ema_tick(int32_t* updates, const float* total_norm, uh_stream stream);
+int uh_swap_f32(float* a, float* b, int64_t n, uh_stream stream);
 
 /* ---- scalar assembly ------------------------------------------------------------------------
  * dice_coeff from per-group sums {sum x*t, sum x, sum t} (dice_score.py:14-25): out[0] = mean over

@@ -9,8 +9,9 @@ from typing import Iterable, Optional
 import torch
 
 
-def save_checkpoint(model: torch.nn.Module, path: str, mask_values: Optional[Iterable] = None) -> str:
-    state_dict = {k: v.detach().to("cpu") for k, v in model.state_dict().items()}
+def save_checkpoint(model: torch.nn.Module, path: str, mask_values: Optional[Iterable] = None, state_dict=None) -> str:
+    """`state_dict`: written in place of the model's own (same keys; e.g. TrainStepper.ema_state_dict())."""
+    state_dict = {k: v.detach().to("cpu") for k, v in (model.state_dict() if state_dict is None else state_dict).items()}
     state_dict["mask_values"] = list(mask_values) if mask_values is not None else []
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)

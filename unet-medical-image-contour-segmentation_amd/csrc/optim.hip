@@ -55,14 +55,30 @@ extern "C" int uh_grad_sumsq(const float* g, int64_t n, float* norm_out, void* w
     return UH_OK;
 }
 
+// The per-element update, shared by rmsprop_kernel and rmsprop_ema_kernel: ONE statement sequence, so that the compiler
+// contracts both kernels' arithmetic the same way and what they write to p / g / sq / buf is bit-identical.
+__device__ __forceinline__ void rmsprop_update(float& p, float& g, float& s, float& b, float coef, float lr, float alpha,
+                                               float eps, float wd, float mu) {
+    float gc = g * coef;
+    g = gc;                                      // clip_grad_norm_ scales .grad in place
+    float ge = gc + wd * p;
+    s = alpha * s + (1.f - alpha) * ge * ge;
+    b = mu * b + ge / (sqrtf(s) + eps);
+    p = p - lr * b;
+}
+
+// A NaN / infinite gradient norm means the loss was not finite (train.py:149-151 aborts before it gets here): the step
+// kernels leave the parameters and the optimizer state untouched, so that a step replayed from a captured graph -- where
+// the host can only look at the loss afterwards -- cannot poison them either.
+__device__ __forceinline__ bool norm_not_finite(const float* total_norm) {
+    return total_norm && !(fabsf(total_norm[0]) < __builtin_huge_valf());
+}
+
 __global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ sq,
                                                       float* __restrict__ buf, int64_t n, const float* __restrict__ total_norm,
                                                       float max_norm, float lr, float alpha, float eps, float wd, float mu) {
     float coef = 1.f;
-    // A NaN / infinite gradient norm means the loss was not finite (train.py:149-151 aborts before it gets here): leave the
-    // parameters and the optimizer state untouched, so that a step replayed from a captured graph -- where the host can
-    // only look at the loss afterwards -- cannot poison them either.
-    if (total_norm && !(fabsf(total_norm[0]) < __builtin_huge_valf())) return;
+    if (norm_not_finite(total_norm)) return;
     if (max_norm > 0.f && total_norm) coef = fminf(max_norm / (total_norm[0] + 1e-6f), 1.f);
     const int64_t n4 = n >> 2;
     f32x4* p4 = reinterpret_cast<f32x4*>(p);
@@ -73,24 +89,67 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ p, flo
         f32x4 pv = p4[i], gv = g4[i], sv = s4[i], bv = b4[i];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float gc = gv[k] * coef;
-            gv[k] = gc;                                  // clip_grad_norm_ scales .grad in place
-            float ge = gc + wd * pv[k];
-            sv[k] = alpha * sv[k] + (1.f - alpha) * ge * ge;
-            bv[k] = mu * bv[k] + ge / (sqrtf(sv[k]) + eps);
-            pv[k] = pv[k] - lr * bv[k];
+            float pe = pv[k], ge = gv[k], se = sv[k], be = bv[k];
+            rmsprop_update(pe, ge, se, be, coef, lr, alpha, eps, wd, mu);
+            pv[k] = pe; gv[k] = ge; sv[k] = se; bv[k] = be;
         }
         p4[i] = pv; g4[i] = gv; s4[i] = sv; b4[i] = bv;
     }
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float gc = g[i] * coef;
-        g[i] = gc;
-        float ge = gc + wd * p[i];
-        float s = alpha * sq[i] + (1.f - alpha) * ge * ge;
-        float b = mu * buf[i] + ge / (sqrtf(s) + eps);
-        sq[i] = s; buf[i] = b;
-        p[i] = p[i] - lr * b;
+        float pe = p[i], ge = g[i], se = sq[i], be = buf[i];
+        rmsprop_update(pe, ge, se, be, coef, lr, alpha, eps, wd, mu);
+        p[i] = pe; g[i] = ge; sq[i] = se; buf[i] = be;
     }
+}
+
+// The same pass with one more read-and-write stream: e <- e + c (p_new - e), the exponential moving average of the
+// parameters, c = 1 - d_t.  t = updates[0] is read from device memory by every block (one scalar load): the whole step may
+// be replayed from a captured graph, and a decay passed by value would freeze the warm-up d_t = min(decay, (1 + t) /
+// (warmup + t)) inside the graph.
+__global__ __launch_bounds__(256) void rmsprop_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ sq,
+                                                          float* __restrict__ buf, float* __restrict__ ema, int64_t n,
+                                                          const float* __restrict__ total_norm, float max_norm, float lr,
+                                                          float alpha, float eps, float wd, float mu, float decay, int warmup,
+                                                          const int32_t* __restrict__ updates) {
+    float coef = 1.f;
+    if (norm_not_finite(total_norm)) return;
+    if (max_norm > 0.f && total_norm) coef = fminf(max_norm / (total_norm[0] + 1e-6f), 1.f);
+    float d = decay;
+    if (warmup > 0) {
+        const float t = (float)updates[0];
+        d = fminf(decay, (1.f + t) / ((float)warmup + t));
+    }
+    const float c = 1.f - d;
+    const int64_t n4 = n >> 2;
+    f32x4* p4 = reinterpret_cast<f32x4*>(p);
+    f32x4* g4 = reinterpret_cast<f32x4*>(g);
+    f32x4* s4 = reinterpret_cast<f32x4*>(sq);
+    f32x4* b4 = reinterpret_cast<f32x4*>(buf);
+    f32x4* e4 = reinterpret_cast<f32x4*>(ema);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 pv = p4[i], gv = g4[i], sv = s4[i], bv = b4[i], ev = e4[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float pe = pv[k], ge = gv[k], se = sv[k], be = bv[k];
+            rmsprop_update(pe, ge, se, be, coef, lr, alpha, eps, wd, mu);
+            pv[k] = pe; gv[k] = ge; sv[k] = se; bv[k] = be;
+            ev[k] = ev[k] + c * (pe - ev[k]);
+        }
+        p4[i] = pv; g4[i] = gv; s4[i] = sv; b4[i] = bv; e4[i] = ev;
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float pe = p[i], ge = g[i], se = sq[i], be = buf[i], ee = ema[i];
+        rmsprop_update(pe, ge, se, be, coef, lr, alpha, eps, wd, mu);
+        p[i] = pe; g[i] = ge; sq[i] = se; buf[i] = be;
+        ema[i] = ee + c * (pe - ee);
+    }
+}
+
+static inline unsigned rmsprop_grid(int64_t n) {
+    int64_t nb = (n / 4 + 255) / 256;
+    if (nb > 256 * 16) nb = 256 * 16;
+    if (nb < 1) nb = 1;
+    return (unsigned)nb;
 }
 
 extern "C" int uh_rmsprop_step(float* p, float* g, float* square_avg, float* momentum_buf, int64_t n,
@@ -99,11 +158,60 @@ extern "C" int uh_rmsprop_step(float* p, float* g, float* square_avg, float* mom
     UH_REQUIRE(p && g && square_avg && momentum_buf && n > 0, "uh_rmsprop_step: bad args");
     UH_REQUIRE(uh_aligned16(p) && uh_aligned16(g) && uh_aligned16(square_avg) && uh_aligned16(momentum_buf),
                "uh_rmsprop_step: buffers must be 16-byte aligned");
-    int64_t nb = (n / 4 + 255) / 256;
-    if (nb > 256 * 16) nb = 256 * 16;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(rmsprop_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, square_avg, momentum_buf,
+    hipLaunchKernelGGL(rmsprop_kernel, dim3(rmsprop_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, square_avg, momentum_buf,
                        n, total_norm, max_norm, lr, alpha, eps, weight_decay, momentum);
     UH_CHECK_LAUNCH("rmsprop_kernel");
+    return UH_OK;
+}
+
+extern "C" int uh_rmsprop_step_ema(float* p, float* g, float* square_avg, float* momentum_buf, float* ema, int64_t n,
+                                   const float* total_norm, float max_norm, float lr, float alpha, float eps,
+                                   float weight_decay, float momentum, float decay, int warmup, const int32_t* updates,
+                                   uh_stream stream) {
+    UH_REQUIRE(p && g && square_avg && momentum_buf && ema && updates && n > 0, "uh_rmsprop_step_ema: bad args");
+    UH_REQUIRE(uh_aligned16(p) && uh_aligned16(g) && uh_aligned16(square_avg) && uh_aligned16(momentum_buf) && uh_aligned16(ema),
+               "uh_rmsprop_step_ema: buffers must be 16-byte aligned");
+    UH_REQUIRE(decay > 0.f && decay < 1.f && warmup >= 0, "uh_rmsprop_step_ema: decay must lie in (0, 1), warmup >= 0");
+    hipLaunchKernelGGL(rmsprop_ema_kernel, dim3(rmsprop_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, square_avg,
+                       momentum_buf, ema, n, total_norm, max_norm, lr, alpha, eps, weight_decay, momentum, decay, warmup, updates);
+    UH_CHECK_LAUNCH("rmsprop_ema_kernel");
+    return UH_OK;
+}
+
+// Launched once per optimizer step behind its uh_rmsprop_step_ema launches (a step whose stale slices split the update into
+// several runs sees one t throughout); a skipped step (non-finite norm) does not count.
+__global__ void ema_tick_kernel(int32_t* updates, const float* total_norm) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || norm_not_finite(total_norm)) return;
+    updates[0] = updates[0] + 1;
+}
+
+extern "C" int uh_ema_tick(int32_t* updates, const float* total_norm, uh_stream stream) {
+    UH_REQUIRE(updates, "uh_ema_tick: bad args");
+    hipLaunchKernelGGL(ema_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, updates, total_norm);
+    UH_CHECK_LAUNCH("ema_tick_kernel");
+    return UH_OK;
+}
+
+// Exchange two fp32 buffers in place (the averaged weights go under the model and come out again without a third buffer).
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    const int64_t n4 = n >> 2;
+    f32x4* a4 = reinterpret_cast<f32x4*>(a);
+    f32x4* b4 = reinterpret_cast<f32x4*>(b);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 av = a4[i], bv = b4[i];
+        a4[i] = bv; b4[i] = av;
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float av = a[i], bv = b[i];
+        a[i] = bv; b[i] = av;
+    }
+}
+
+extern "C" int uh_swap_f32(float* a, float* b, int64_t n, uh_stream stream) {
+    UH_REQUIRE(a && b && n > 0, "uh_swap_f32: bad args");
+    UH_REQUIRE(uh_aligned16(a) && uh_aligned16(b), "uh_swap_f32: buffers must be 16-byte aligned");
+    UH_REQUIRE(a + n <= b || b + n <= a, "uh_swap_f32: the buffers overlap");
+    hipLaunchKernelGGL(swap_f32_kernel, dim3(rmsprop_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, n);
+    UH_CHECK_LAUNCH("swap_f32_kernel");
     return UH_OK;
 }

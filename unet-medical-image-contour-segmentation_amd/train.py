@@ -2,7 +2,8 @@
 
     seg_loss(...)     loss assembly of train.py:118-142 (fused single-pass kernels)
     FusedRMSprop      clip_grad_norm_(1.0) + RMSprop(lr, weight_decay=1e-8, momentum=0.999) of
-                      train.py:80-81,157-158 as two passes over one flat fp32 buffer
+                      train.py:80-81,157-158 as two passes over one flat fp32 buffer; optionally an exponential moving
+                      average of the parameters in the same pass (EmaConfig), and state_dict / load_state_dict
     train_step(...)   zero_grad -> forward (autocast) -> loss -> NaN check -> backward -> clip -> step
     TrainStepper      model + optimizer (+ data-parallel sync) bundle used by bench.py
     train_model(...)  the epoch loop of train.py:29-220 on a user-supplied iterable of batches
@@ -12,10 +13,12 @@ works unchanged: the modules are ordinary nn.Modules.
 """
 from __future__ import annotations
 
+import contextlib
+import dataclasses
 import math
 import os
 import weakref
-from typing import Dict, Iterable, Optional
+from typing import Dict, Iterable, Optional, Union
 
 import torch
 import torch.nn as nn
@@ -65,17 +68,74 @@ def seg_loss(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int,
 
 
 # ----------------------------------------------------------------------------------- optimizer
+@dataclasses.dataclass(frozen=True)
+class EmaConfig:
+    """The exponential moving average of the parameters kept by FusedRMSprop: e <- e + (1 - d_t) (p - e) after every
+    update, d_t = min(decay, (1 + t) / (warmup + t)) at the t-th update (0-based) when warmup > 0, else decay.  The
+    average starts as a copy of the parameters, so it needs no bias correction; the warm-up lets it follow the fast first
+    updates instead of holding on to the initialisation for 1 / (1 - decay) steps."""
+    decay: float = 0.999
+    warmup: int = 10
+
+    def __post_init__(self):
+        if not (isinstance(self.decay, (int, float)) and not isinstance(self.decay, bool) and 0.0 < float(self.decay) < 1.0):
+            raise ValueError(f"EmaConfig: decay lies in (0, 1), not {self.decay!r}")
+        if isinstance(self.warmup, bool) or int(self.warmup) != self.warmup or self.warmup < 0:
+            raise ValueError(f"EmaConfig: warmup is an integer >= 0, not {self.warmup!r}")
+
+    @classmethod
+    def parse(cls, spec: str) -> "EmaConfig":
+        """'DECAY[,warmup=N]' -> config, e.g. '0.999,warmup=10'; ValueError names what is wrong."""
+        parts = [t.strip() for t in str(spec).split(",")]
+        if not parts[0]:
+            raise ValueError(f"EmaConfig.parse: the decay is missing in {spec!r}")
+        try:
+            vals = {"decay": float(parts[0])}
+        except ValueError:
+            raise ValueError(f"EmaConfig.parse: decay {parts[0]!r} is not a number") from None
+        for tok in parts[1:]:
+            name, eq, val = (t.strip() for t in tok.partition("="))
+            if name != "warmup" or not eq or "warmup" in vals:
+                raise ValueError(f"EmaConfig.parse: {tok!r} is not warmup=N (once) in {spec!r}")
+            try:
+                vals["warmup"] = int(val)
+            except ValueError:
+                raise ValueError(f"EmaConfig.parse: warmup {val!r} is not an integer") from None
+        return cls(**vals)
+
+    def spec(self) -> str:
+        """The canonical spec: EmaConfig.parse(cfg.spec()) == cfg."""
+        return f"{float(self.decay)!r},warmup={int(self.warmup)}"
+
+    @classmethod
+    def of(cls, ema: Union[None, str, "EmaConfig"]) -> Optional["EmaConfig"]:
+        """None, a spec string or a config -> None or a config."""
+        if ema is None or isinstance(ema, cls):
+            return ema
+        if isinstance(ema, str):
+            return cls.parse(ema)
+        raise TypeError(f"ema is an EmaConfig or a spec string, not {type(ema).__name__}")
+
+
 class FusedRMSprop:
     """clip_grad_norm_ + torch.optim.RMSprop(momentum > 0, centered=False) over ONE flat buffer.
 
     Every parameter is re-pointed at a view of `flat_p` (values preserved, strides preserved, so
     channels_last weights stay channels_last); gradients are gathered into `flat_g` by
     post-accumulate hooks in backward-ready order, which is also the bucket order of the
-    data-parallel all-reduce."""
+    data-parallel all-reduce.
+
+    ema_decay (default None: off -- nothing is allocated and the launches are what they are without the option): keep an
+    exponential moving average of the parameters in `flat_ema`, laid out like `flat_p` and initialised to a copy of it,
+    updated inside the same pass (uh_rmsprop_step_ema) with the decay of EmaConfig(ema_decay, ema_warmup) at update number
+    `ema_updates` (a device int32[1], advanced once per applied step by uh_ema_tick: a step skipped for a non-finite
+    gradient norm does not count).  A parameter skipped as stale (no gradient this step) keeps its average untouched, like
+    the rest of its state.  Data parallel: the average is a function of parameters that are identical on every rank, so
+    every rank keeps the same one without communication.  swap_ema() exchanges the parameters and their average in place."""
 
     def __init__(self, params: Iterable[nn.Parameter], lr: float = 1e-5, alpha: float = 0.99, eps: float = 1e-8,
                  weight_decay: float = 1e-8, momentum: float = 0.999, gradient_clipping: float = 1.0,
-                 process_group=None, bucket_bytes: int = 8 << 20):
+                 process_group=None, bucket_bytes: int = 8 << 20, ema_decay: Optional[float] = None, ema_warmup: int = EmaConfig.warmup):
         plist = [p for p in params if p.requires_grad]
         if not plist:
             raise ValueError("FusedRMSprop got no parameters")
@@ -134,6 +194,11 @@ class FusedRMSprop:
         self.sync = None
         if dpmod.sync_enabled(process_group):
             self.sync = dpmod.BucketedGradSync(self.flat_g, slices, bucket_bytes, process_group)
+        self.ema = EmaConfig(float(ema_decay), ema_warmup) if ema_decay is not None else None
+        self.flat_ema = self.ema_updates = None
+        if self.ema is not None:
+            self.flat_ema = self.flat_p.clone()
+            self.ema_updates = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def close(self):
         """Detach from the parameters: hooks removed, in-place gradient destinations unregistered.  The parameters keep
@@ -291,12 +356,78 @@ class FusedRMSprop:
         st = torch.cuda.current_stream().cuda_stream
         LIB.call("uh_grad_sumsq", self.flat_g.data_ptr(), self.total, self.norm.data_ptr(), self.ws.data_ptr(),
                  self.ws.numel(), st)
-        for o, n in runs:
-            LIB.call("uh_rmsprop_step", self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(), self.flat_sq[o:].data_ptr(),
-                     self.flat_buf[o:].data_ptr(), n, self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]),
-                     float(g["alpha"]), float(g["eps"]), float(g["weight_decay"]), float(g["momentum"]), st)
+        if self.ema is None:
+            for o, n in runs:
+                LIB.call("uh_rmsprop_step", self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(), self.flat_sq[o:].data_ptr(),
+                         self.flat_buf[o:].data_ptr(), n, self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]),
+                         float(g["alpha"]), float(g["eps"]), float(g["weight_decay"]), float(g["momentum"]), st)
+        else:
+            for o, n in runs:
+                LIB.call("uh_rmsprop_step_ema", self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(),
+                         self.flat_sq[o:].data_ptr(), self.flat_buf[o:].data_ptr(), self.flat_ema[o:].data_ptr(), n,
+                         self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]), float(g["alpha"]), float(g["eps"]),
+                         float(g["weight_decay"]), float(g["momentum"]), float(self.ema.decay), int(self.ema.warmup),
+                         self.ema_updates.data_ptr(), st)
+            # behind every run's launch: all of them read the same update number
+            LIB.call("uh_ema_tick", self.ema_updates.data_ptr(), self.norm.data_ptr(), st)
         ops.WEIGHT_EPOCH += 1        # parameters changed behind torch's version counters (see ops.packed_w3x3_cached)
         return self.norm
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange the parameters and their moving average in place (uh_swap_f32: exact, no third buffer): the model then
+        computes with the averaged weights, and a second call puts everything back bit for bit.  The packed-filter and
+        folded BatchNorm caches are keyed on ops.WEIGHT_EPOCH (ops.packed_w3x3_cached, ops.bn_eval_coeffs_cached,
+        ops.ConvWeightPack), which is bumped."""
+        if self.ema is None:
+            raise RuntimeError("FusedRMSprop.swap_ema() without ema_decay")
+        LIB.call("uh_swap_f32", self.flat_p.data_ptr(), self.flat_ema.data_ptr(), self.total,
+                 torch.cuda.current_stream().cuda_stream)
+        ops.WEIGHT_EPOCH += 1
+
+    def _layout(self):
+        return [[int(o), int(n), [int(d) for d in p.shape]] for p, (o, n) in zip(self.params, self.slices)]
+
+    def state_dict(self) -> Dict:
+        """The state a resumed run needs beside the parameters themselves (they travel in the model's state_dict): clones of
+        the two RMSprop buffers, the moving average and its update count (None / 0 without one), the slice layout they are
+        laid out by, and the hyper-parameters (the current lr among them)."""
+        g = self.param_groups[0]
+        hyper = {k: float(g[k]) for k in ("lr", "alpha", "eps", "weight_decay", "momentum")}
+        hyper["gradient_clipping"] = self.gradient_clipping
+        hyper["ema_decay"] = float(self.ema.decay) if self.ema is not None else None
+        hyper["ema_warmup"] = int(self.ema.warmup) if self.ema is not None else None
+        return {"square_avg": self.flat_sq.detach().clone(), "momentum_buffer": self.flat_buf.detach().clone(),
+                "ema": self.flat_ema.detach().clone() if self.ema is not None else None,
+                "ema_updates": int(self.ema_updates.item()) if self.ema is not None else 0,
+                "layout": self._layout(), "total": int(self.total), "hyper": hyper}
+
+    @torch.no_grad()
+    def load_state_dict(self, state: Dict):
+        """Restore what state_dict() returned.  ValueError when the slice layout differs (another model, another parameter
+        order), when the state and this optimizer disagree about keeping a moving average, or when they keep it with another
+        decay or warm-up (the average is part of the run: it is not continued under other settings silently)."""
+        layout = [[int(o), int(n), [int(d) for d in shape]] for o, n, shape in state["layout"]]
+        if layout != self._layout() or int(state["total"]) != self.total:
+            raise ValueError("FusedRMSprop.load_state_dict: the state's slice layout is not this optimizer's "
+                             f"({len(layout)} slices over {int(state['total'])} floats against {len(self.slices)} over {self.total})")
+        if (state.get("ema") is not None) != (self.ema is not None):
+            raise ValueError("FusedRMSprop.load_state_dict: the state " + ("has" if state.get("ema") is not None else "lacks")
+                             + " a moving average and this optimizer " + ("keeps one" if self.ema is not None else "keeps none"))
+        hyper = dict(state["hyper"])
+        if self.ema is not None:
+            saved = EmaConfig(float(hyper["ema_decay"]), int(hyper["ema_warmup"]))
+            if saved != self.ema:
+                raise ValueError(f"FusedRMSprop.load_state_dict: the state's moving average was kept with {saved.spec()!r}, "
+                                 f"this optimizer keeps one with {self.ema.spec()!r}")
+            self.flat_ema.copy_(state["ema"])
+            self.ema_updates.fill_(int(state["ema_updates"]))
+        self.flat_sq.copy_(state["square_avg"])
+        self.flat_buf.copy_(state["momentum_buffer"])
+        for k in ("lr", "alpha", "eps", "weight_decay", "momentum"):
+            self.param_groups[0][k] = float(hyper[k])
+        self.gradient_clipping = float(hyper["gradient_clipping"])
+        ops.WEIGHT_EPOCH += 1
 
     def grad_of(self, p: torch.Tensor) -> torch.Tensor:
         """The (clipped, after step()) gradient of `p` as stored in the flat buffer."""
@@ -432,8 +563,12 @@ class TrainStepper:
     def __init__(self, model: nn.Module, lr: float = 1e-5, weight_decay: float = 1e-8, momentum: float = 0.999,
                  gradient_clipping: float = 1.0, amp: bool = True, process_group=None, check_nan: bool = True,
                  wgrad_stream: Optional[bool] = None, cc_loss: bool = False, sync_bn: bool = False, fp32_mode: str = "exact",
-                 surface_weight: float = 0.0, surface_classes=None):
+                 surface_weight: float = 0.0, surface_classes=None, ema: Union[None, str, EmaConfig] = None):
         self.model = model
+        # ema: an EmaConfig or a spec string ("0.999,warmup=10"): the optimizer keeps a moving average of the parameters
+        # (FusedRMSprop), averaged() computes with it.  None (default): nothing is allocated or launched for it.
+        self.ema = EmaConfig.of(ema)
+        self._averaged = False
         # the surface term of seg_loss; a plain attribute: the epoch loop may change the weight between steps (0 = off)
         self.surface_weight = float(surface_weight)
         self.surface_classes = surface_classes
@@ -485,7 +620,8 @@ class TrainStepper:
                 self.bn_group = group = dist.new_group(ranks=ranks)
             self.sync_bn = (group, self.world)
         self.optimizer = FusedRMSprop(model.parameters(), lr=lr, weight_decay=weight_decay, momentum=momentum,
-                                      gradient_clipping=gradient_clipping, process_group=process_group)
+                                      gradient_clipping=gradient_clipping, process_group=process_group,
+                                      **({} if self.ema is None else {"ema_decay": self.ema.decay, "ema_warmup": self.ema.warmup}))
         self._pack = None
         # the closing reductions of backward-weights wait for one batched launch behind the backward pass; data parallel: for
         # one launch per gradient bucket, so that the bucket's all-reduce still starts under the rest of the backward pass
@@ -512,6 +648,45 @@ class TrainStepper:
         except Exception:
             pass
 
+    @contextlib.contextmanager
+    def averaged(self):
+        """`with stepper.averaged(): evaluate(model, ...)` -- inside the block the model's parameters ARE the moving average
+        (swapped in place, FusedRMSprop.swap_ema), on leaving it the live ones are back bit for bit, also after an exception.
+        BatchNorm running statistics are shared with the live model and not averaged: they are already a moving average
+        (momentum 0.1) of the statistics of recent batches.  Nesting the block or calling step() inside it raises
+        RuntimeError: an update applied to the swapped buffers would train the average."""
+        if self.ema is None:
+            raise RuntimeError("TrainStepper.averaged() needs ema=...")
+        if self._averaged:
+            raise RuntimeError("TrainStepper.averaged() is already active (it does not nest)")
+        self.optimizer.swap_ema()
+        self._averaged = True
+        try:
+            yield self.model
+        finally:
+            self.optimizer.swap_ema()
+            self._averaged = False
+
+    def _refuse_averaged(self):
+        if self._averaged:
+            raise RuntimeError("TrainStepper.step() inside averaged(): the model holds the averaged weights")
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The model's state_dict on the CPU in the checkpoint wire format (checkpoint.py), with the averaged parameters in
+        place of the live ones and the live buffers (BatchNorm running statistics: see averaged())."""
+        if self.ema is None:
+            raise RuntimeError("TrainStepper.ema_state_dict() needs ema=...")
+        opt = self.optimizer
+        src = opt.flat_p if self._averaged else opt.flat_ema          # (inside averaged() the model holds the average)
+        base, size = opt.flat_p.data_ptr(), opt.flat_p.numel() * 4
+        out = {}
+        for k, v in self.model.state_dict().items():
+            off = v.data_ptr() - base
+            if 0 <= off < size and v.dtype == torch.float32:
+                v = torch.as_strided(src, v.shape, v.stride(), off // 4)
+            out[k] = v.detach().to("cpu", copy=True)
+        return out
+
     SIDE_MIN_PIXELS = 1 << 20
 
     def _side_for(self, images):
@@ -531,6 +706,7 @@ class TrainStepper:
         """One optimizer step (train.py:113-159).  `global_batch` (data parallel with sync_bn): the sum of the ranks' batch
         sizes when the caller knows it (equal shards: world * B) -- otherwise it is all-reduced here, which costs a blocking
         host read per step."""
+        self._refuse_averaged()
         self.model.train()
         side = self._side_for(images)
         ops.WGRAD_STREAM = side
@@ -567,7 +743,9 @@ class GraphedTrainStepper(TrainStepper):
     """TrainStepper whose whole step (forward, loss, backward, clip + RMSprop) is captured once into a HIP graph and
     replayed per batch: for launch-bound models (UNet_S / UNet_T: ~500 small kernels per step) the host no longer paces
     the GPU.  Fixed batch shape; re-captured when the learning rate changes (it is a kernel argument); single process
-    only.  A NaN loss is detected after the replay (the fused optimizer kernel has skipped the update: non-finite norm)."""
+    only.  A NaN loss is detected after the replay (the fused optimizer kernel has skipped the update: non-finite norm).
+    With `ema` the captured graph holds the averaging launches and the update counter's tick; the decay of the warm-up is
+    computed on the device from that counter, so every replay uses its own."""
 
     def __init__(self, model: nn.Module, *args, warmup: int = 2, **kw):
         kw.setdefault("wgrad_stream", False)         # one stream unless asked for: the graph is for launch-bound small models
@@ -612,6 +790,7 @@ class GraphedTrainStepper(TrainStepper):
         # the warm-up steps the capture protocol needs must not count as training: snapshot, warm up, restore
         snap_model = {k: v.clone() for k, v in self.model.state_dict().items()}
         snap_opt = (opt.flat_p.clone(), opt.flat_sq.clone(), opt.flat_buf.clone())
+        snap_ema = (opt.flat_ema.clone(), opt.ema_updates.clone()) if opt.ema is not None else None
         self._im = images.detach().clone(memory_format=torch.preserve_format)
         self._mk = masks.detach().clone()
         side = torch.cuda.Stream()
@@ -623,6 +802,8 @@ class GraphedTrainStepper(TrainStepper):
         torch.cuda.synchronize()
         with torch.no_grad():
             opt.flat_p.copy_(snap_opt[0]); opt.flat_sq.copy_(snap_opt[1]); opt.flat_buf.copy_(snap_opt[2])
+            if snap_ema is not None:
+                opt.flat_ema.copy_(snap_ema[0]); opt.ema_updates.copy_(snap_ema[1])
             for k, v in self.model.state_dict().items():
                 if v.data_ptr() < opt.flat_p.data_ptr() or v.data_ptr() >= opt.flat_p.data_ptr() + opt.flat_p.numel() * 4:
                     v.copy_(snap_model[k])                    # buffers (running statistics, num_batches_tracked)
@@ -635,6 +816,7 @@ class GraphedTrainStepper(TrainStepper):
 
     def step(self, images, true_masks):
         self._refuse_surface()
+        self._refuse_averaged()
         key = (tuple(images.shape), tuple(true_masks.shape), float(self.optimizer.param_groups[0]["lr"]))
         if self._graph is None or key != self._key:
             self._capture(images, true_masks)

@@ -3,6 +3,7 @@
     python -m unet_amd.train -e 5 -b 1 -l 1e-5 -s 0.5 -c 3 [--bilinear] [-f model.pth] [--no-amp]
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
                              [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--elastic [SPEC]] [--surface-loss [SPEC]]
+                             [--ema [DECAY[,warmup=N]]] [--save-state] [--resume STATE]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -27,6 +28,19 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     csrc/surface_loss.hip) to every training step, its distance maps rebuilt on the device from the step's own (augmented)
     labels.  The weight of epoch e (1-based) is min(1, W + R (e - 1)); bare --surface-loss is "0.01,ramp=0.01"; classes default
     to the one evaluate scores.  One log line per epoch gives the weight, the epoch line the summed term;
+  - --ema [DECAY[,warmup=N]] (default: off; bare: "0.999,warmup=10") keeps an exponential moving average of the parameters
+    inside the optimizer pass (train.EmaConfig, csrc/optim.hip).  Every evaluation of the loop then runs ONCE, on the
+    averaged weights (TrainStepper.averaged()): its Dice is what the log prints, marked "(EMA)", and what the learning-rate
+    rule receives.  checkpoint_epoch{E}.pth and model_epoch{E}.pth keep the live weights; checkpoint_epoch{E}_ema.pth and
+    model_epoch{E}_ema.pth are written beside them in the same wire format (predict, evaluate and seg_main load them as
+    they are).  BatchNorm running statistics are the live ones in both;
+  - --save-state writes checkpoint_dir/train_state.pth at the end of every epoch (a temporary file renamed over it): model
+    and optimizer state (both RMSprop buffers, the moving average and its update count), epoch, global step, lr, the
+    loader's and the augmenter's seeds, and a record of the arguments that determine the run (RECORDED);
+  - --resume STATE restores all of that and continues with the epoch after the saved one up to -e: the run is bit for bit
+    the run that was never interrupted.  A determining argument that differs from the record ends the command with
+    status 2 and a message naming it, and so does a state whose epoch is not below -e (nothing is left to train); -f together
+    with --resume is an error;
   - --load drops mask_values (train.py:275-280); -v is accepted and unused, as in the reference.
 Input batches come from DeviceBatchLoader: decode threads, pinned collation, rotation + BICUBIC / NEAREST rescale + /255
 + label remap on the device (csrc/data_rescale.hip, csrc/data_prep.hip), bit-identical to stacking ds[i].
@@ -35,6 +49,7 @@ command exits with status 2."""
 from __future__ import annotations
 
 import argparse
+import contextlib
 import logging
 import math
 import os
@@ -44,6 +59,8 @@ from pathlib import Path
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
+
+from .train import EmaConfig
 
 MODELS = ("UNet_S", "UNet", "UNet_T", "UNet_SA")
 
@@ -56,6 +73,12 @@ class SurfaceSpec(NamedTuple):
 
 
 SURFACE_BARE = "0.01,ramp=0.01"
+EMA_BARE = EmaConfig().spec()            # "0.999,warmup=10"
+STATE_FILE = "train_state.pth"
+# the arguments that determine a run, as --save-state records and --resume compares them: (record key, command-line name)
+RECORDED = (("model", "--model"), ("classes", "--classes"), ("bilinear", "--bilinear"), ("batch_size", "--batch-size"),
+            ("scale", "--scale"), ("amp", "--amp / --no-amp"), ("lr", "--learning-rate"), ("augment", "--augment"),
+            ("elastic", "--elastic"), ("surface", "--surface-loss"), ("ema", "--ema"))
 
 
 def parse_surface_spec(text: str) -> SurfaceSpec:
@@ -103,6 +126,55 @@ def surface_weight_at(spec: SurfaceSpec, epoch: int) -> float:
     return min(1.0, spec.weight + spec.ramp * (int(epoch) - 1))
 
 
+def surface_spec_text(spec: Optional[SurfaceSpec]) -> Optional[str]:
+    """The canonical spec of a SurfaceSpec (None stays None): parse_surface_spec(text) == spec."""
+    if spec is None:
+        return None
+    return f"{spec.weight!r},ramp={spec.ramp!r}" + (",classes=" + "+".join(str(c) for c in spec.classes) if spec.classes else "")
+
+
+def _ema_arg(text: str):
+    try:
+        return EmaConfig.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"bad --ema {text!r}: {e}") from None
+
+
+def run_record(args: argparse.Namespace) -> Dict:
+    """The arguments that determine what a run computes (RECORDED), specs in their canonical form, None for an option that is
+    off.  ValueError for a spec that does not parse."""
+    from .utils.augment import AugmentConfig, ElasticConfig
+    return {"model": args.model, "classes": int(args.classes), "bilinear": bool(args.bilinear),
+            "batch_size": int(args.batch_size), "scale": float(args.scale), "amp": bool(args.amp), "lr": float(args.lr),
+            "augment": AugmentConfig.parse(args.augment).spec() if args.augment is not None else None,
+            "elastic": ElasticConfig.parse(args.elastic).spec() if args.elastic is not None else None,
+            "surface": surface_spec_text(args.surface_loss),
+            "ema": args.ema.spec() if args.ema is not None else None}
+
+
+def load_resume_state(args: argparse.Namespace) -> Optional[Dict]:
+    """--resume: the saved state, read on the CPU and checked against this command line; None without the option.
+    ValueError names the argument that is wrong -- before a GPU, a dataset or a model is touched."""
+    if not args.resume:
+        return None
+    if args.load:
+        raise ValueError("--load / -f cannot be combined with --resume (the state file carries the weights)")
+    state = torch.load(args.resume, map_location="cpu", weights_only=True)
+    missing = [k for k in ("model", "optimizer", "epoch", "global_step", "lr", "loader_seed", "augment_seed", "args")
+               if not isinstance(state, dict) or k not in state]
+    if missing:
+        raise ValueError(f"--resume {args.resume}: not a training state (no {', '.join(missing)})")
+    if int(state["epoch"]) >= args.epochs:
+        raise ValueError(f"--resume {args.resume}: the state was saved after epoch {int(state['epoch'])} and --epochs / -e is "
+                         f"{args.epochs}: no epoch is left to train")
+    now = run_record(args)
+    for key, flag in RECORDED:
+        if state["args"].get(key) != now[key]:
+            raise ValueError(f"--resume {args.resume}: {flag} ({key}) is {now[key]!r} on the command line, but the state was "
+                             f"saved by a run with {state['args'].get(key)!r}")
+    return state
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Train the UNet on images and target masks")
     # the reference's flags, short forms and defaults (train.py:223-236)
@@ -138,6 +210,13 @@ def build_parser() -> argparse.ArgumentParser:
                    metavar="W[,ramp=R][,classes=a+b]",
                    help="Add W * surface loss (distance to the true contour, maps built on the device each step); the weight of "
                         f"epoch e is min(1, W + R (e - 1)) (bare flag: '{SURFACE_BARE}'; default: off)")
+    p.add_argument("--ema", nargs="?", const=EMA_BARE, default=None, type=_ema_arg, metavar="DECAY[,warmup=N]",
+                   help="Keep an exponential moving average of the weights in the optimizer pass; evaluations run on it and "
+                        f"*_ema.pth files are written beside the usual ones (bare flag: '{EMA_BARE}'; default: off)")
+    p.add_argument("--save-state", dest="save_state", action="store_true", default=False,
+                   help=f"Write checkpoint_dir/{STATE_FILE} after every epoch: everything --resume needs (default: off)")
+    p.add_argument("--resume", default=None, metavar="STATE",
+                   help="Continue the run a --save-state file was written by, bit for bit, with the epoch after the saved one")
     return p
 
 
@@ -176,7 +255,8 @@ def build_model(name: str, n_classes: int, bilinear: bool):
 def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: int, learning_rate: float, amp: bool,
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
                  train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
-                 augment=None, surface: Optional[SurfaceSpec] = None, elastic=None) -> List[Dict]:
+                 augment=None, surface: Optional[SurfaceSpec] = None, elastic=None, ema=None, save_state: bool = False,
+                 resume: Optional[Dict] = None, record: Optional[Dict] = None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
@@ -184,32 +264,54 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     seed: `seed`, or the loader's own draw when unseeded); the validation loader never gets one.
     `elastic`: an ElasticConfig or a spec string, added to that augmenter; alone, it deforms over the identity affine map.
     `surface`: a SurfaceSpec; every epoch's steps run with surface_weight_at(surface, epoch), and the record gains the weight
-    and the summed term."""
+    and the summed term.
+    `ema`: an EmaConfig or a spec string; every evaluation then runs inside stepper.averaged() (once, on the averaged
+    weights: that Dice is logged, marked "(EMA)", and drives the lr), every checkpoint gets a *_ema.pth twin, and the last
+    record returned carries the averaged model as "ema_state_dict" (TrainStepper.ema_state_dict(), on the CPU).
+    `save_state`: write checkpoint_dir/train_state.pth after every epoch, holding `record` (run_record) as its "args".
+    `resume`: such a state (load_resume_state); the model must already hold its weights.  Optimizer state, lr, counters
+    and the seeds are restored and the loop continues with the epoch after the saved one: only those epochs are returned."""
     from .evaluate import evaluate
     from .checkpoint import save_checkpoint
     from .train import TrainStepper, cosine_warm_restarts_lr
     from .utils.data_loading import DeviceBatchLoader
     n_train = len(train_set)
     if train_loader is None:
-        train_loader = DeviceBatchLoader(train_set, batch_size, shuffle=True, drop_last=False, seed=seed, workers=workers,
-                                         device=device)
+        train_loader = DeviceBatchLoader(train_set, batch_size, shuffle=True, drop_last=False,
+                                         seed=seed if resume is None else resume["loader_seed"], workers=workers, device=device)
+    elif resume is not None:
+        train_loader.seed = int(resume["loader_seed"])
     if augment is not None or elastic is not None:
         from .utils.augment import AugmentConfig, BatchAugment
         if isinstance(augment, BatchAugment):
             if elastic is not None:
                 raise ValueError("run_training: a BatchAugment carries its own elastic configuration")
         else:
-            augment = BatchAugment(augment if augment is not None else AugmentConfig(), train_loader.seed, elastic=elastic)
+            aug_seed = train_loader.seed if resume is None or resume["augment_seed"] is None else resume["augment_seed"]
+            augment = BatchAugment(augment if augment is not None else AugmentConfig(), aug_seed, elastic=elastic)
         train_loader.augment = augment
         if log:
             log(f"Training augmentation (seed {augment.seed}): {augment.config.spec()}"
                 + (f"; elastic {augment.elastic.spec()}" if augment.elastic is not None else ""))
     val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
-    stepper = TrainStepper(model, lr=learning_rate, amp=amp, surface_classes=surface.classes if surface is not None else None)
+    stepper = TrainStepper(model, lr=learning_rate, amp=amp, surface_classes=surface.classes if surface is not None else None,
+                           ema=ema)
     lr = learning_rate
     global_step = 0
+    first_epoch = 1
+    if resume is not None:
+        stepper.optimizer.load_state_dict(resume["optimizer"])
+        lr = float(resume["lr"])
+        stepper.optimizer.param_groups[0]["lr"] = lr
+        global_step = int(resume["global_step"])
+        first_epoch = int(resume["epoch"]) + 1
+        train_loader.epoch = int(resume["epoch"])          # the loader's 0-based epoch is also the augmenter's
+        if log:
+            log(f"Resumed after epoch {resume['epoch']} (global step {global_step}, lr {lr:.6g})")
+    tag = " (EMA)" if stepper.ema is not None else ""
+    mask_values = train_set.mask_values + val_set.mask_values
     history = []
-    for epoch in range(1, epochs + 1):
+    for epoch in range(first_epoch, epochs + 1):
         model.train()
         losses, surfaces = [], []
         if surface is not None:
@@ -237,13 +339,14 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                 if metrics:
                     from .utils.contour_metrics import ContourMetrics, format_line
                     acc = ContourMetrics()
-                val_score, val_post, val_min = evaluate(model, val_loader, device, amp, epoch_pred_dir, metrics=acc)  # postprocess=True
+                with (stepper.averaged() if stepper.ema is not None else contextlib.nullcontext()):
+                    val_score, val_post, val_min = evaluate(model, val_loader, device, amp, epoch_pred_dir, metrics=acc)  # postprocess=True
                 lr = cosine_warm_restarts_lr(learning_rate, float(val_score))                    # scheduler.step(val_score)
                 stepper.optimizer.param_groups[0]["lr"] = lr
                 dice = (float(val_score), float(val_post), float(val_min))
                 eval_s += time.perf_counter() - te
                 if log:
-                    log(f"Validation Dice score: {dice[0]}  postprocessed: {dice[1]}  min: {dice[2]}")
+                    log(f"Validation Dice score{tag}: {dice[0]}  postprocessed: {dice[1]}  min: {dice[2]}")
                 if acc is not None:
                     contour = acc.result()
                     if log:
@@ -260,21 +363,50 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
             rec["surface"] = float(torch.stack(surfaces).double().sum().item()) if surfaces else 0.0
         if checkpoint_dir is not None and checkpoint_due(epoch, epochs):
             path = os.path.join(checkpoint_dir, f"checkpoint_epoch{epoch}.pth")
-            save_checkpoint(model, path, mask_values=train_set.mask_values + val_set.mask_values)
+            save_checkpoint(model, path, mask_values=mask_values)
             rec["checkpoint"] = path
+            if stepper.ema is not None:
+                save_checkpoint(model, path[:-len(".pth")] + "_ema.pth", mask_values=mask_values,
+                                state_dict=stepper.ema_state_dict())
+        if save_state and checkpoint_dir is not None:
+            rec["state"] = _write_state(os.path.join(checkpoint_dir, STATE_FILE), model, stepper, epoch, global_step, lr,
+                                        train_loader.seed, augment.seed if augment is not None else None, record)
         history.append(rec)
         if log:
-            log(f"Epoch {epoch}/{epochs}: loss (total) {epoch_loss:.6g}, Dice {dice[0]} / post {dice[1]} / min {dice[2]}, "
+            log(f"Epoch {epoch}/{epochs}: loss (total) {epoch_loss:.6g}, Dice{tag} {dice[0]} / post {dice[1]} / min {dice[2]}, "
                 f"lr {lr:.6g}, {rec['img_s']:.1f} images/s ({seen} images, evaluation {eval_s:.2f} s)"
                 + (f", surface (summed) {rec['surface']:.6g} at weight {rec['surface_weight']:.6g}" if "surface" in rec else "")
                 + (f", checkpoint {rec['checkpoint']}" if "checkpoint" in rec else ""))
+    if stepper.ema is not None and history:
+        history[-1]["ema_state_dict"] = stepper.ema_state_dict()
     stepper.close()
     return history
+
+
+def _write_state(path: str, model, stepper, epoch: int, global_step: int, lr: float, loader_seed: int,
+                 augment_seed: Optional[int], record: Optional[Dict]) -> str:
+    """--save-state: everything --resume needs, written beside `path` and renamed over it (a reader never sees half a file)."""
+    cpu = lambda v: v.detach().cpu() if torch.is_tensor(v) else v
+    state = {"format": 1, "model": {k: cpu(v) for k, v in model.state_dict().items()},
+             "optimizer": {k: cpu(v) for k, v in stepper.optimizer.state_dict().items()},
+             "epoch": int(epoch), "global_step": int(global_step), "lr": float(lr), "loader_seed": int(loader_seed),
+             "augment_seed": int(augment_seed) if augment_seed is not None else None, "args": dict(record or {})}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = path + ".tmp"
+    torch.save(state, tmp)
+    os.replace(tmp, path)
+    return path
 
 
 def main(argv=None) -> int:
     args = get_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s: %(message)s")
+    try:
+        resume = load_resume_state(args)                                      # a refused --resume needs no GPU to say so
+        record = run_record(args) if (args.save_state or resume is not None) else None
+    except ValueError as e:
+        logging.error(f"train: {e}")
+        return 2
     if not torch.cuda.is_available():
         logging.error("train: no GPU found. This port trains on the MI355X through its HIP kernels and has no CPU path.")
         return 2
@@ -309,17 +441,26 @@ def main(argv=None) -> int:
     if args.load:
         load_checkpoint(model, args.load, device="cpu")                       # mask_values dropped (train.py:275-280)
         logging.info(f"Model loaded from {args.load}")
+    if resume is not None:
+        model.load_state_dict(resume["model"])
+        logging.info(f"Training state loaded from {args.resume}")
     model.to(device=device)
     n_train, n_val = len(train_set), len(val_set)
     logging.info(f"Starting training: epochs {args.epochs}, batch size {args.batch_size}, learning rate {args.lr}, "
                  f"training items {n_train}, validation items {n_val}, scale {args.scale}, "
                  f"{'bf16 autocast' if args.amp else 'fp32'}, checkpoints in {args.checkpoint_dir}")
-    run_training(model, device, train_set, val_set, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.lr,
-                 amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed, workers=args.workers, log=logging.info,
-                 pred_dir=args.pred_dir, metrics=args.metrics, augment=augment, surface=args.surface_loss, elastic=elastic)
+    history = run_training(model, device, train_set, val_set, epochs=args.epochs, batch_size=args.batch_size,
+                           learning_rate=args.lr, amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed,
+                           workers=args.workers, log=logging.info, pred_dir=args.pred_dir, metrics=args.metrics,
+                           augment=augment, surface=args.surface_loss, elastic=elastic, ema=args.ema,
+                           save_state=args.save_state, resume=resume, record=record)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")
+    if args.ema is not None:
+        path = f"model_epoch{args.epochs}_ema.pth"
+        torch.save(history[-1]["ema_state_dict"], path)
+        logging.info(f"Averaged model saved to {path}")
     return 0
 
 
