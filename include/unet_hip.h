@@ -706,6 +706,23 @@ int uh_predict_prepare_u8(const uint8_t* img_u8, float* image_out, int* flags_ws
 int uh_logits_to_classes_u8(const void* logits, int64_t npix, int ncls, int dt, uint8_t* classes_out, uh_stream stream);
 int uh_classes_to_grey_u8(const uint8_t* classes, uint8_t* grey_out, const uint8_t* lut, int64_t n, uh_stream stream);
 
+/* ---- test-time augmentation around the eval forward  (csrc/tta.hip; the reference has none) ---------------------------
+ * A view is v = 4 t + 2 fy + fx, "flip, then transpose": a source pixel (y, x) of an H x W image lies in view v at (yy, xx)
+ * for t = 0 and at (xx, yy) of a W x H view for t = 1, with yy = fy ? H-1-y : y and xx = fx ? W-1-x : x.  mask: the views
+ * of a mode as bits over v, one of 0x03 (hflip), 0x0f (flips), 0x69 (rot4: the quarter turns), 0xff (d4); K0 / K1 = its
+ * number of t = 0 / t = 1 views, V = K0 + K1.
+ * uh_tta_views: x DEVICE float32 [B][H][W][C] (C <= 8) -> views0 [K0 B][H][W][C], the t = 0 views in ascending v, view-major
+ *   (entry k B + b), and views1 [K1 B][W][H][C], the t = 1 views likewise (may be null when K1 = 0).  A pure copy.
+ * uh_tta_merge: logits0 [K0 B][H][W][NC] and logits1 [K1 B][W][H][NC] (null when K1 = 0), the logits of those views in dt
+ *   (UH_F32 / UH_BF16).  Per source pixel and view: the fp32 softmax over the classes (NC = 1: the sigmoid) of the logits at
+ *   the pixel's position in the view, quantised as q = (uint32) rintf(p * 2^24); the q of all views are added as integers, so
+ *   the result does not depend on the order of the views.  Outputs, each nullable (one at least): sums uint32 [B][H][W][NC];
+ *   classes uint8 [B][H][W], the first maximum of the sums (NC = 1: sum > V 2^23, the averaged sigmoid > 0.5); probs float32
+ *   [B][H][W][NC] = sum / (V 2^24), exact.  1 <= NC <= 256; B <= 65535. */
+int uh_tta_views(const float* x, float* views0, float* views1, int B, int H, int W, int C, int mask, uh_stream stream);
+int uh_tta_merge(const void* logits0, const void* logits1, int dt, int B, int H, int W, int NC, int mask, unsigned int* sums,
+                 uint8_t* classes, float* probs, uh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,9 @@ table pass per batch on the device (uh_classes_to_grey_u8), the files are encode
 evaluate returns once they are on disk.  Without it nothing of that runs.  With `metrics` (a utils.contour_metrics.ContourMetrics)
 the scored masks of every batch also go through uh_contour_metrics (HD / HD95 / ASSD / IoU); the records stay on the device
 until the accumulator's result() is read.  Without it nothing of that runs either.
+With `tta` (a mode of utils/tta.py) the prediction that is scored is the average over the views of the mode: the views are built on
+the device (uh_tta_views), run through the batch-invariant forward and merged (uh_tta_merge); everything after the argmax /
+threshold runs on the merged classes unchanged.  Without it nothing of that runs.
 `python -m unet_amd.evaluate -m CKPT --data-root DIR` scores a checkpoint without training (evaluate_cli.py)."""
 from __future__ import annotations
 
@@ -47,15 +50,32 @@ class _PredDump:
         self.writer.close()
 
 
+def _tta_classes(net, image, tta):
+    """uint8 [B,H,W]: the classes of the probabilities averaged over the views of `tta` (inside evaluate's autocast).  Each
+    view of the batch is a launch of its own, of the batch's length, under the pinned plan of one image."""
+    from .utils.tta import tta_counts
+    B, _, H, W = image.shape
+    k0, k1 = tta_counts(tta)
+    views0, views1 = ops.tta_views(image, tta)
+    with ops.plan_images(1):
+        logits0 = torch.cat([net(views0[k * B:(k + 1) * B]) for k in range(k0)])
+        logits1 = torch.cat([net(views1[k * B:(k + 1) * B]) for k in range(k1)]) if k1 else None
+    return ops.tta_merge(logits0, logits1, tta, (H, W)).classes
+
+
 @torch.inference_mode()
-def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True, process_group=None, metrics=None):
+def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True, process_group=None, metrics=None, tta=None):
     """evaluate.py:12-171.  `postprocess=True` is the reference's default (evaluate.py:13): the second return value is then
     the Dice after post-processing and the minimum is taken over min(raw, post-processed) per batch (evaluate.py:85).
     Batches are consumed lazily; under torch.distributed (every rank evaluating its shard of the validation set) the Dice
     sums and batch counts are all-reduced so that every rank returns the metric of the whole set.  `metrics`: an accumulator
     that is updated with the contour-metric records of the raw and (postprocess=True) the post-processed masks of every
     batch, P and T being exactly the masks whose Dice is taken, and all-reduced where the Dice sums are; the return value
-    is the same 3-tuple either way."""
+    is the same 3-tuple either way.  `tta`: "hflip", "flips", "rot4" or "d4" -- the masks that are scored, post-processed,
+    measured and dumped are those of the prediction averaged over these views (None: one forward, as the reference)."""
+    if tta is not None:
+        from .utils.tta import tta_mask
+        tta = tta_mask(tta)
     net.eval()
     num_val_batches = 0
     dice_score = torch.zeros((), dtype=torch.float32, device=device)
@@ -68,11 +88,17 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
             image, mask_true = batch["image"], batch["mask"]
             image = image.to(device=device, dtype=torch.float32, memory_format=torch.channels_last)
             mask_true = mask_true.to(device=device, dtype=torch.float32)
-            mask_pred = net(image)
+            if tta is None:
+                mask_pred = net(image)
+            else:
+                merged = _tta_classes(net, image, tta)
             if net.n_classes == 1:
                 mask_true = torch.div(mask_true, 2, rounding_mode="floor")                      # evaluate.py:56
                 assert mask_true.min() >= 0 and mask_true.max() <= 1, "True mask indices should be in [0, 1]"
-                pred = ops.threshold_mask(mask_pred.squeeze(1))    # sigmoid(x) > 0.5  <=>  x > 0   (evaluate.py:60-62)
+                if tta is None:
+                    pred = ops.threshold_mask(mask_pred.squeeze(1))    # sigmoid(x) > 0.5  <=>  x > 0   (evaluate.py:60-62)
+                else:
+                    pred = merged.float()                              # the averaged sigmoid > 0.5
                 d = dice_coeff(pred, mask_true, reduce_batch_first=False)
                 cur = d
                 if postprocess:
@@ -92,7 +118,7 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
                 if dump is not None:                                                            # evaluate.py:88-105
                     dump.add(num_val_batches, pred.to(torch.uint8), "binary", processed_u8 if postprocess else None, "binary")
             else:
-                idx = ops.argmax_classes(mask_pred)                                             # evaluate.py:111
+                idx = ops.argmax_classes(mask_pred) if tta is None else merged.long()           # evaluate.py:111
                 true_c = (mask_true == 2).float()
                 d = dice_coeff((idx == 2).float(), true_c, reduce_batch_first=False)
                 cur = d

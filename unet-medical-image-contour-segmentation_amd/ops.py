@@ -1848,8 +1848,95 @@ def classes_to_grey_u8(classes: torch.Tensor, lut: torch.Tensor, out: Optional[t
     return out
 
 
+# ----------------------------------------------------------------------------- test-time augmentation (csrc/tta.hip)
+class TtaMerged(NamedTuple):
+    classes: torch.Tensor                     # uint8 [B,H,W]
+    sums: Optional[torch.Tensor]              # int32 [B,H,W,NC]: the integer sums of the quantised probabilities (< 2^28)
+    probs: Optional[torch.Tensor]             # float32 [B,H,W,NC] = sums / (V * 2^24)
+
+
+def tta_views(x: torch.Tensor, mode) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The views of a batch of images [B,C,H,W] (fp32, read through its NHWC view) under a mode of utils/tta.py ->
+    (views0 [K0*B,C,H,W], views1 [K1*B,C,W,H] or None), view-major, both channels-last: what the network takes.  The two are
+    slices of one buffer, views1 right behind views0."""
+    from .utils.tta import tta_counts, tta_mask
+    mask = tta_mask(mode)
+    _require_gpu(x, "images")
+    if x.dim() != 4:
+        raise RuntimeError(f"tta_views expects [B,C,H,W] images, got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    v = x.permute(0, 2, 3, 1)
+    if v.dtype != torch.float32:
+        v = v.float()
+    if not v.is_contiguous():
+        v = v.contiguous()
+    k0, k1 = tta_counts(mask)
+    per = B * H * W * C
+    buf = torch.empty((k0 + k1) * per, dtype=torch.float32, device=x.device)
+    views0 = buf[:k0 * per].view(k0 * B, H, W, C)
+    views1 = buf[k0 * per:].view(k1 * B, W, H, C) if k1 else None
+    LIB.call("uh_tta_views", v.data_ptr(), views0.data_ptr(), _p(views1), B, H, W, C, mask, _stream())
+    return views0.permute(0, 3, 1, 2), None if views1 is None else views1.permute(0, 3, 1, 2)
+
+
+def tta_joint_views(views0: torch.Tensor, views1: torch.Tensor) -> torch.Tensor:
+    """The two results of tta_views for SQUARE images as the one batch [(K0+K1)*B,C,H,W] they are in memory."""
+    if views0.shape[1:] != views1.shape[1:] or views0.shape[2] != views0.shape[3]:
+        raise RuntimeError("tta_joint_views: the views have two shapes")
+    n0, n1 = views0.shape[0], views1.shape[0]
+    a = views0.permute(0, 2, 3, 1)
+    if views1.data_ptr() != a.data_ptr() + a.numel() * a.element_size():
+        raise RuntimeError("tta_joint_views takes the pair tta_views returned")
+    return torch.as_strided(a, (n0 + n1,) + tuple(a.shape[1:]), a.stride(), a.storage_offset()).permute(0, 3, 1, 2)
+
+
+def tta_merge(logits0: torch.Tensor, logits1: Optional[torch.Tensor], mode, size: Tuple[int, int], *, sums: bool = False,
+              probs: bool = False) -> TtaMerged:
+    """Merges the logits of the views of tta_views back onto the source grid `size` = (H, W): logits0 [K0*B,NC,H,W], logits1
+    [K1*B,NC,W,H] (fp32 or bf16, read through their NHWC view).  logits1 = None with a mode that has transposed views: the
+    images are square and logits0 holds all (K0+K1)*B views.  -> TtaMerged(classes, sums or None, probs or None)."""
+    from .utils.tta import tta_counts, tta_mask
+    mask = tta_mask(mode)
+    k0, k1 = tta_counts(mask)
+    H, W = int(size[0]), int(size[1])
+    _require_gpu(logits0, "logits")
+    if logits0.dim() != 4 or tuple(logits0.shape[2:]) != (H, W) or logits0.shape[1] > 256:
+        raise RuntimeError(f"tta_merge expects [N,C<=256,{H},{W}] logits of the untransposed views, got {tuple(logits0.shape)}")
+    NC = logits0.shape[1]
+
+    def nhwc(t):
+        v = t.permute(0, 2, 3, 1)
+        if v.dtype not in (torch.float32, torch.bfloat16):
+            v = v.float()
+        return v if v.is_contiguous() else v.contiguous()
+
+    v0 = nhwc(logits0)
+    v1 = None
+    if k1 and logits1 is None:
+        if H != W or v0.shape[0] % (k0 + k1):
+            raise RuntimeError(f"tta_merge: {tuple(logits0.shape)} cannot hold every view of square images in this mode")
+        B = v0.shape[0] // (k0 + k1)
+        v0, v1 = v0[:k0 * B], v0[k0 * B:]
+    else:
+        if v0.shape[0] % k0:
+            raise RuntimeError(f"tta_merge: {v0.shape[0]} untransposed views do not divide by {k0}")
+        B = v0.shape[0] // k0
+        if k1:
+            _require_gpu(logits1, "logits")
+            if tuple(logits1.shape) != (k1 * B, NC, W, H) or logits1.dtype != logits0.dtype:
+                raise RuntimeError(f"tta_merge expects [{k1 * B},{NC},{W},{H}] logits of the transposed views in "
+                                   f"{logits0.dtype}, got {tuple(logits1.shape)} {logits1.dtype}")
+            v1 = nhwc(logits1)
+    dev = v0.device
+    classes = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    s = torch.empty(B, H, W, NC, dtype=torch.int32, device=dev) if sums else None
+    p = torch.empty(B, H, W, NC, dtype=torch.float32, device=dev) if probs else None
+    LIB.call("uh_tta_merge", v0.data_ptr(), _p(v1), _dt(v0), B, H, W, NC, mask, _p(s), classes.data_ptr(), _p(p), _stream())
+    return TtaMerged(classes, s, p)
+
+
 # ----------------------------------------------------------------------------- contour metrics (csrc/contour_metrics.hip)
-CONTOUR_RECORD_DOUBLES = 12          # uh_contour_record: 12 x uint32 (= 6 doubles wide), then 6 x double
+CONTOUR_RECORD_DOUBLES = 12         # uh_contour_record: 12 x uint32 (= 6 doubles wide), then 6 x double
 _EDT_WS = {}
 _CONTOUR_WS = {}
 

@@ -3,7 +3,7 @@
     predict_img(model, full_img, device) -> np.ndarray[H, W] of class indices        predict.py:15-29
     mask_to_image(mask) -> PIL.Image (0 / 128 / 255 grey levels)                      predict.py:52-58
     preprocess_image(pil_img, scale=1.0) -> float32 [C, H, W]                         data_loading.py:65-91 (image branch)
-    BatchPredictor(model, batch=8, postprocess=True, batch_invariant=False)(images) -> [uint8 [H, W] grey]
+    BatchPredictor(model, batch=8, postprocess=True, batch_invariant=False, tta=None)(images) -> [uint8 [H, W] grey]
                                                                                       predict.py:120-135 for a list of images
     python -m unet_amd.predict -m model.pth -i DIR [-o OUT]                           predict.py:31-152 (predict_cli.py)
 
@@ -147,15 +147,26 @@ class BatchPredictor:
     to the kernel one image gets (uh_conv3x3_fwd_affine_relu_plan, uh_convt2x2_mfma_ok_plan), so a launch of any length
     gives every image the bits it gets alone.  `launch_lengths` then asks the pinned queries and returns every B up to
     `batch` that no real-B limit (a tensor past the 2 GiB window: another kernel) excludes.  The masks are those of the
-    default mode; only the number of launches differs."""
+    default mode; only the number of launches differs.
+
+    `tta` (a mode of utils/tta.py: "hflip", "flips", "rot4", "d4"): test-time augmentation.  Every image is predicted in each
+    view of the mode and the views' probabilities are averaged before the argmax (uh_tta_views, the forward, uh_tta_merge;
+    DESIGN.md section 3 "Test-time augmentation").  `batch` stays the number of images per forward launch, so a launch group
+    holds batch // (views per launch) source images (`tta_group`); the view batches are cut by `launch_lengths` and replay
+    captured graphs like any other batch, so every view gets the logits it gets alone and the prediction of a posed image is
+    exactly the posed prediction.  `probabilities(images)` returns the averaged probabilities.  None: nothing of this runs."""
 
     MAX_GRAPHS = 4
 
     def __init__(self, model: torch.nn.Module, batch: int = 8, postprocess: bool = True, amp: bool = True, device=None,
-                 min_area: int = 15000, morph_kernel_size: int = 3, batch_invariant: bool = False):
+                 min_area: int = 15000, morph_kernel_size: int = 3, batch_invariant: bool = False, tta=None):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.batch_invariant = bool(batch_invariant)
+        if tta is not None:
+            from .utils.tta import tta_mask
+            tta = tta_mask(tta)                                          # ValueError for anything but the four modes
+        self.tta = tta
         if getattr(model, "n_classes", None) == 1:
             # predict.py:27 takes argmax(dim=1) of a one-channel tensor: all zeros.  Not reproduced.
             raise ValueError("BatchPredictor needs a multi-class head: predict.py's argmax over one channel is all zeros. "
@@ -284,6 +295,10 @@ class BatchPredictor:
         """One batch of equally sized uint8 [H,W] images -> uint8 [B,H,W] on the host (grey-coded, or class indices), in as
         few launches as launch_lengths allows."""
         H, W = arrays[0].shape
+        if getattr(self, "tta", None) is not None:
+            g = self.tta_group(H, W)
+            out = [self._launch_tta(arrays[s:s + g], grey) for s in range(0, len(arrays), g)]
+            return out[0] if len(out) == 1 else np.concatenate(out)
         lengths = self.launch_lengths(H, W)
         if len(arrays) in lengths:
             return self._launch(arrays, grey)
@@ -306,15 +321,62 @@ class BatchPredictor:
             if tuple(logits.shape[-2:]) != (H, W):
                 raise RuntimeError(f"the network returned {tuple(logits.shape[-2:])} for a {(H, W)} input")     # predict.py:26 is dead at scale 1
             cls = self._mark("classes", ops.logits_to_classes_u8, logits)
-            if self.postprocess:
-                from .utils.post_process import _run as _postprocess_run
-                cls = self._mark("postprocess", _postprocess_run, cls, self.min_area, self.ksize)
-            if grey:
-                self._mark("grey", ops.classes_to_grey_u8, cls, self._lut, cls)
-            out = self._pinned("_pin_out", B * H * W).view(B, H, W)
-            self._mark("download", out.copy_, cls, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            return out.numpy().copy()
+            return self._deliver(cls, grey)
+
+    def _deliver(self, cls: torch.Tensor, grey: bool) -> np.ndarray:
+        """Class maps uint8 [B,H,W] on the device -> post-processed, grey-coded, on the host."""
+        B, H, W = cls.shape
+        if self.postprocess:
+            from .utils.post_process import _run as _postprocess_run
+            cls = self._mark("postprocess", _postprocess_run, cls, self.min_area, self.ksize)
+        if grey:
+            self._mark("grey", ops.classes_to_grey_u8, cls, self._lut, cls)
+        out = self._pinned("_pin_out", B * H * W).view(B, H, W)
+        self._mark("download", out.copy_, cls, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return out.numpy().copy()
+
+    # ---------------------------------------------------------------- test-time augmentation
+    def tta_group(self, H: int, W: int) -> int:
+        """Source images of one size per launch group: `batch` is the number of images per forward launch, and a launch
+        carries every view of a square image, the larger of the two view shapes' counts otherwise."""
+        from .utils.tta import tta_forward_views
+        return max(1, self.batch // tta_forward_views(self.tta, H, W))
+
+    def _forward_cut(self, x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+        """_forward for a view batch of any length, in as few launches as launch_lengths allows."""
+        lengths = self.launch_lengths(*size)
+        n = x.shape[0]
+        if n in lengths:
+            return self._forward(x, size)
+        pieces, s = [], 0
+        while s < n:
+            b = max(v for v in lengths if v <= n - s)
+            pieces.append(self._forward(x[s:s + b], size).clone())    # (a replayed graph returns its static buffer)
+            s += b
+        return torch.cat(pieces)
+
+    def _launch_tta(self, arrays: List[np.ndarray], grey: bool, probs: bool = False) -> np.ndarray:
+        """One launch group under test-time augmentation -> uint8 [B,H,W] as _launch, or (probs) float32 [B,NC,H,W]."""
+        H, W = arrays[0].shape
+        B = len(arrays)
+        with torch.cuda.device(self.device):
+            img = self._mark("upload", self._upload, arrays, H, W)
+            x = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
+            flags = self._flags if B <= self._flags.numel() else torch.empty(B, dtype=torch.int32, device=self.device)
+            self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
+            v0, v1 = self._mark("views", ops.tta_views, x, self.tta)
+            if v1 is not None and H == W:                              # one view shape: one forward
+                l0, l1 = self._mark("forward", self._forward_cut, ops.tta_joint_views(v0, v1), (H, W)), None
+            else:
+                l0 = self._mark("forward", self._forward_cut, v0, (H, W))
+                l1 = self._mark("forward", self._forward_cut, v1, (W, H)) if v1 is not None else None
+            if tuple(l0.shape[-2:]) != (H, W) or (l1 is not None and tuple(l1.shape[-2:]) != (W, H)):
+                raise RuntimeError(f"the network returned {tuple(l0.shape[-2:])} for a {(H, W)} input")
+            merged = self._mark("merge", ops.tta_merge, l0, l1, self.tta, (H, W), probs=probs)
+            if probs:
+                return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
+            return self._deliver(merged.classes, grey)
 
     def _run(self, images, grey: bool) -> List[np.ndarray]:
         arrays = [_as_grey_array(im) for im in images]
@@ -330,6 +392,22 @@ class BatchPredictor:
 
     def classes(self, images) -> List[np.ndarray]:
         return self._run(images, False)
+
+    def probabilities(self, images) -> List[np.ndarray]:
+        """float32 [NC,H,W] per image: the mean over the views of the softmax probabilities (multiples of 2^-24 / V)."""
+        if getattr(self, "tta", None) is None:
+            raise RuntimeError("probabilities() returns the mean over the views of test-time augmentation: build the predictor "
+                               "with tta=...")
+        arrays = [_as_grey_array(im) for im in images]
+        result: List[Optional[np.ndarray]] = [None] * len(arrays)
+        for (H, W), members in plan_batches([a.shape for a in arrays], self.batch):
+            g = self.tta_group(H, W)
+            for s in range(0, len(members), g):
+                part = members[s:s + g]
+                out = self._launch_tta([arrays[i] for i in part], False, probs=True)
+                for k, i in enumerate(part):
+                    result[i] = np.ascontiguousarray(out[k])
+        return result
 
 
 def main(argv=None) -> int:

@@ -2,12 +2,14 @@
 
     python -m unet_amd.predict -m model.pth -i FILE_OR_DIR [-o OUT] [-n] [-v] [--no-postprocess]
                                [--arch UNet] [-c 3] [--bilinear] [--no-amp] [-b 8] [--workers 8] [--no-batch-invariant]
+                               [--tta [hflip|flips|rot4|d4]]
 
 Every image is predicted at its own size (scale 1).  The images of a folder are decoded by a thread pool, grouped by size,
 run through BatchPredictor in batches (prepare, eval forward, classes, post-processing and grey coding on the device, one
 upload and one download per batch) and encoded to PNG by the same pool while the next batch runs.  The forward is
 batch-invariant (BatchPredictor(batch_invariant=True)): a batch is one launch and every image gets the bits it gets alone;
---no-batch-invariant cuts the batches instead, to the same files.
+--no-batch-invariant cuts the batches instead, to the same files.  --tta averages the prediction over the views of a mode
+(utils/tta.py; a bare --tta means d4): -b stays the number of images per forward launch, views included.
 
 Reference behaviour that is kept, awkward parts included:
   - predict.py:33-38  the flags -m, -i (both required), -o, -v, -n, and -p, a store_true whose default is already True;
@@ -65,6 +67,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "(the default; the masks are the same either way)")
     p.add_argument("--no-batch-invariant", dest="batch_invariant", action="store_false",
                    help="Cut every batch into launches in which each layer gets one image's kernel by itself")
+    from .utils.tta import DEFAULT_MODE, MODES
+    p.add_argument("--tta", nargs="?", const=DEFAULT_MODE, default=None, choices=tuple(MODES),
+                   help="Test-time augmentation: average the prediction over these views (a bare --tta: d4; default: off)")
     return p
 
 
@@ -208,7 +213,7 @@ def main(argv=None) -> int:
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info("Using device %s", device)
     predictor = BatchPredictor(model, batch=args.batch_size, postprocess=args.postprocess, amp=args.amp, device=device,
-                               batch_invariant=args.batch_invariant)
+                               batch_invariant=args.batch_invariant, tta=args.tta)
     if args.output is not None and not args.no_save:
         os.makedirs(args.output, exist_ok=True)                       # predict.py:48
     show = (lambda path, img, grey: _show(plt, path, img, grey)) if plt is not None else None
