@@ -31,6 +31,18 @@ def test_header_symbols_all_exported():
     assert LIB.query("uh_conv3x3_wgrad_ws_bytes", 8, 128, 128, 256, 256, 1) > 256 * 9 * 256 * 4
 
 
+def test_consumer_side_batchnorm_conv_calls_are_gone():
+    """The conv variants that applied the previous layer's BatchNorm + ReLU in their loaders were retired (DESIGN.md section
+    3): neither the header nor the library knows a uh_conv3x3_*pre* symbol any more."""
+    import re
+    import unet_amd  # noqa: F401
+    from unet_amd._lib import LIB_PATH, parse_header
+    gone = re.compile(r"uh_conv3x3_\w*pre\w*")
+    header = open(os.path.join(ROOT, "include", "unet_hip.h")).read()
+    assert not gone.findall(header) and not [n for n in parse_header() if gone.fullmatch(n)]
+    assert not gone.findall(open(LIB_PATH, "rb").read().decode("latin-1"))          # dynamic symbol names are plain bytes
+
+
 def test_bad_arguments_return_error_codes_not_crashes():
     import unet_amd  # noqa: F401
     from unet_amd._lib import LIB

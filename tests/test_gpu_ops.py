@@ -504,6 +504,24 @@ def test_bn_relu_forward_backward(dtype, B, H, W, C):
     assert torch.equal(dg2, dgam) and torch.equal(db2, dbet) and torch.equal(dy2, dy)
 
 
+def test_bn_relu_apply_bf16_is_fma_relu_one_rounding():
+    """What uh_bn_relu_apply stores in bf16 is fma(y, scale, shift), then the ReLU, then ONE rounding: within 2**-8 (one bf16
+    rounding) of the largest value.  33 x 17 pixels: partial rows."""
+    from unet_amd._lib import LIB, UH_BF16
+    dev = _dev()
+    B, H, W, C = 2, 33, 17, 64
+    g = torch.Generator().manual_seed(B * 7 + H + C)
+    y = torch.randn(B, H, W, C, generator=g).to(dev, torch.bfloat16)
+    scale = (torch.rand(C, generator=g) + 0.5).to(dev)
+    shift = (torch.randn(C, generator=g) * 0.3).to(dev)
+    z = torch.empty_like(y)
+    LIB.call("uh_bn_relu_apply", y.data_ptr(), C, scale.data_ptr(), shift.data_ptr(), z.data_ptr(), C, B * H * W, C, UH_BF16,
+             torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    want = torch.relu(torch.addcmul(shift, y.float(), scale)).to(torch.bfloat16)
+    assert float((z.float() - want.float()).abs().max()) <= 2 ** -8 * float(want.float().abs().max())
+
+
 def test_rmsprop_clip_flat():
     from unet_amd._lib import LIB
     from oracle import step_ref as S
@@ -802,30 +820,6 @@ def test_narrow_entry_points_reject_bad_arguments():
     with pytest.raises(RuntimeError):      # valid > padded
         LIB.call("uh_conv3x3_fwd_narrow", x.data_ptr(), 64, 128, 16, None, 0, 0, 0, w.data_ptr(), y.data_ptr(), 16, 64, 16,
                  None, None, None, 1, 8, 8, UH_BF16, st)
-
-
-def test_default_library_refuses_the_consumer_side_batchnorm_calls_loudly():
-    """The PRE instantiations (BatchNorm + ReLU applied by the consumer conv's loaders: built, measured a net loss) live behind the
-    build flag UH_BUILD_PRE=1.  The default library must say so -- uh_conv3x3_pre_ok answers 0 and both entry points fail with a
-    message that names the flag -- and never run something else instead."""
-    from unet_amd._lib import LIB, UH_BF16
-    dev = _dev()
-    if LIB.query("uh_conv3x3_pre_ok", 2, 64, 64, 128, 256, 128, 256, UH_BF16):
-        pytest.skip("this library was built with UH_BUILD_PRE=1")
-    x = torch.zeros(2, 64, 64, 128, dtype=torch.bfloat16, device=dev)
-    y = torch.zeros(2, 64, 64, 256, dtype=torch.bfloat16, device=dev)
-    c = torch.zeros(256, device=dev)
-    w = torch.zeros(256 * 9 * 128, dtype=torch.bfloat16, device=dev)
-    st = torch.cuda.current_stream().cuda_stream
-    with pytest.raises(RuntimeError, match="UH_BUILD_PRE"):
-        LIB.call("uh_conv3x3_fwd_pre", x.data_ptr(), 128, 128, c.data_ptr(), c[128:].data_ptr(), w.data_ptr(), y.data_ptr(), 256, 256,
-                 None, 2, 64, 64, UH_BF16, st)
-    dw = torch.zeros(256 * 9 * 128, device=dev)
-    nbytes = LIB.query("uh_conv3x3_wgrad_ws_bytes", 2, 64, 64, 128, 256, UH_BF16)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with pytest.raises(RuntimeError, match="UH_BUILD_PRE"):
-        LIB.call("uh_conv3x3_wgrad_pre", y.data_ptr(), 256, x.data_ptr(), 128, 128, c.data_ptr(), c[128:].data_ptr(), dw.data_ptr(), 256,
-                 ws.data_ptr(), nbytes, 2, 64, 64, UH_BF16, st)
 
 
 def _wgrad_errors(x, dy, dev):

@@ -11,24 +11,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
-# Two libraries of the same C ABI: libunet_hip.so (the product) and libunet_hip_pre.so (own object directory), which also carries
-# the consumer-side BatchNorm + ReLU instantiations of the conv kernels (uh_conv3x3_fwd_pre / uh_conv3x3_wgrad_pre: built,
-# measured, a net loss -- DESIGN.md section 3; the default library carries stubs that fail loudly).  __graft_entry__.build()
-# builds both; tests/test_gpu_pre_fusion.py binds the second one for the length of its module; UH_LIB_PATH selects it for A/B runs.
-# UH_BUILD_PRE=1 makes the flagged library the default target of build_library() (command-line use).
-BUILD_PRE = os.environ.get("UH_BUILD_PRE") == "1"
-
-
-def lib_path(pre: bool = False) -> str:
-    return os.path.join(PKG_DIR, "libunet_hip_pre.so" if pre else "libunet_hip.so")
-
-
-def obj_dir(pre: bool = False) -> str:
-    return os.path.join(CSRC, "build_pre" if pre else "build")
-
-
-LIB_PATH = lib_path(BUILD_PRE)
-OBJ_DIR = obj_dir(BUILD_PRE)
+LIB_PATH = os.path.join(PKG_DIR, "libunet_hip.so")
+OBJ_DIR = os.path.join(CSRC, "build")
 
 SOURCES = ["uh_error.hip", "conv3x3.hip", "bn.hip", "bn_fused.hip", "pool_up.hip", "convt_1x1.hip", "convt_mfma.hip", "loss.hip", "optim.hip", "cc_loss.hip", "infer.hip", "post_process.hip", "data_prep.hip", "stem_mfma.hip", "spatial_attn.hip", "seg_pipeline.hip", "data_rescale.hip", "predict_io.hip", "contour_metrics.hip", "augment.hip", "surface_loss.hip", "tta.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC,
@@ -74,22 +58,20 @@ def check_toolchain() -> None:
     print("WARNING: " + msg + " (UH_ALLOW_UNVALIDATED_ROCM=1): run the parity tests before trusting this build", flush=True)
 
 
-def build_library(force: bool = False, verbose: bool = False, pre: bool = BUILD_PRE) -> str:
+def build_library(force: bool = False, verbose: bool = False) -> str:
     """Compile what is stale, lint the hand-scheduled kernels that were recompiled, link.  Serialised across processes by a
     file lock: every rank of a multi-process launch may call this, one of them builds, the others find everything fresh."""
     import fcntl
-    os.makedirs(obj_dir(pre), exist_ok=True)
-    with open(os.path.join(obj_dir(pre), ".lock"), "w") as lock:
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    with open(os.path.join(OBJ_DIR, ".lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            return _build_locked(force, verbose, pre)
+            return _build_locked(force, verbose)
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(force: bool, verbose: bool, pre: bool) -> str:
-    OBJ_DIR, LIB_PATH = obj_dir(pre), lib_path(pre)
-    EXTRA_DEFINES = ["-DUH_BUILD_PRE=1"] if pre else []
+def _build_locked(force: bool, verbose: bool) -> str:
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers.append(os.path.join(INCLUDE, "unet_hip.h"))
     hipcc = _hipcc()
@@ -102,7 +84,7 @@ def _build_locked(force: bool, verbose: bool, pre: bool) -> str:
         objs.append(o)
         if force or _stale(o, [s] + headers):
             extra = ["-save-temps=obj"] if src in LINTED else []
-            jobs.append([hipcc] + FLAGS + EXTRA_DEFINES + extra + ["-c", s, "-o", o])
+            jobs.append([hipcc] + FLAGS + extra + ["-c", s, "-o", o])
             rebuilt.add(src)
 
     def run(cmd):
@@ -120,17 +102,16 @@ def _build_locked(force: bool, verbose: bool, pre: bool) -> str:
     # the lint reads (and prunes) the -save-temps by-products of THIS call's compile; objects that were not rebuilt were
     # linted when they were (their report is kept beside them)
     lint_isa(verbose, only={src for src in LINTED if src in rebuilt or
-                            not os.path.exists(os.path.join(OBJ_DIR, src.replace(".hip", ".isa_lint.json")))}, pre=pre)
+                            not os.path.exists(os.path.join(OBJ_DIR, src.replace(".hip", ".isa_lint.json")))})
     if force or jobs or _stale(LIB_PATH, objs):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs)
     return LIB_PATH
 
 
-def lint_isa(verbose: bool = False, only=None, pre: bool = BUILD_PRE) -> None:
+def lint_isa(verbose: bool = False, only=None) -> None:
     """Check the ISA of the hand-scheduled kernels (see isa_lint.py); raises on a violation.  `only`: the sources to lint
     (build_library passes the ones it has just recompiled); None = every linted source whose ISA file exists."""
     lint = _lint_module()
-    OBJ_DIR = obj_dir(pre)
     for src, isa in LINTED.items():
         path = os.path.join(OBJ_DIR, isa)
         if (only is not None and src not in only) or not os.path.exists(path):
@@ -155,4 +136,4 @@ def lint_isa(verbose: bool = False, only=None, pre: bool = BUILD_PRE) -> None:
 
 
 if __name__ == "__main__":
-    print(build_library(force="--force" in sys.argv, verbose=True, pre=BUILD_PRE or "--pre" in sys.argv))
+    print(build_library(force="--force" in sys.argv, verbose=True))

@@ -577,12 +577,6 @@ __device__ __forceinline__ int halo_swz(int hx) { return ((hx >> 2) & 1) << 1; }
 // is loaded ONCE and stays in registers for every tile of the persistent workgroup.  The 64 -> 64 layers at 512 x 512 have
 // only 2 chunks per tile, so every 16x16 tile used to re-read the whole 74 KB filter through L1 (590 MB per launch, more
 // than the activations; TA 82 % busy): with it resident the main loop's only vector-memory traffic is the halo DMA.
-// PRE (bf16, source 0 only): x0 is the RAW output of the previous conv and the BatchNorm + ReLU that follows it
-// (unet_parts.py:16-17) is applied here, by the consumer: z = max(y * scale + shift, 0) per channel, rounded to bf16 exactly as
-// uh_bn_relu_apply would have stored it -- so the activation between the two convs of a DoubleConv never exists in HBM.  The
-// halo tile still travels HBM -> LDS by DMA; once a wave's own pieces have landed (its covering vmcnt) every thread rewrites
-// the pieces IT issued in place (ds_read_b128 -> 8 x fma / max -> ds_write_b128) in front of the chunk's barrier.  Pieces
-// outside the image stay zero (the padding of the ACTIVATION is zero, not max(shift, 0)).  The 2 * C0 coefficients sit in LDS.
 // BSUM (bf16 backward-data of the SECOND conv of a DoubleConv): the tensor this launch produces is dz, the gradient of the
 // activation z = ReLU(BatchNorm(q)) between the two convs (q = bs_y: the first conv's raw output, same shape as this launch's
 // output).  The two per-channel sums BatchNorm's backward starts with (unet_parts.py:16-17 differentiated)
@@ -590,10 +584,6 @@ __device__ __forceinline__ int halo_swz(int hx) { return ((hx >> 2) & 1) << 1; }
 // are formed in this kernel's epilogue from the accumulators (rounded to bf16 as stored) and one read of q, like the forward's
 // statistics: one partial row per workgroup, [row][2][Cout] -- the layout uh_bn_bwd_finalize / uh_bn_relu_bwd_apply take.  The
 // uh_bn_relu_bwd_reduce pass (a read of dz and of q) is not launched for that layer.
-#ifndef UH_BUILD_PRE
-#define UH_BUILD_PRE 0        // build.py: UH_BUILD_PRE=1 compiles the PRE instantiations (A/B and tests/test_gpu_pre_fusion.py)
-#endif
-constexpr int PRE_MAX_C = 512;
 // KS = 2 (bf16, NBW = 1, exactly ONE tile per workgroup): the deep layers of a small batch -- 512 channels at 32 x 32 -- have
 // fewer (tile, channel slab) pairs than the chip has CUs and 16+ K-chunks per tile: one 4-wave workgroup per CU, i.e. ONE wave
 // per SIMD working through a serial chain of chunks with nothing to hide its LDS / MFMA latencies behind (40 us for 19 GFLOP
@@ -604,7 +594,7 @@ constexpr int PRE_MAX_C = 512;
 // Under the pinned plan (fwd_plan: plan_B) the form also runs launches far past that range -- a batch of images each of which
 // would get it alone, thousands of one-tile workgroups: nothing in it depends on the tile count (the block mapping below is a
 // bijection for any grid, the hand-over is per workgroup, eval launches write no statistics rows).
-template <typename T, int NBW, bool SPLIT = false, bool WRES = false, bool PRE = false, bool BSUM = false, int KS = 1>
+template <typename T, int NBW, bool SPLIT = false, bool WRES = false, bool BSUM = false, int KS = 1>
 // (three workgroups per CU -- 168 registers -- for the 16-channel-per-wave form; its BSUM instantiation needs more than that for
 // the epilogue's batches and spilled 42 instructions per tile at 168: two per CU, like the other wide-register forms)
 // (round 5: the register-resident-filter form does not fit three per CU either -- at 168 registers hipcc 7.2 spills 36 instructions into its
@@ -614,11 +604,9 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
     const T* __restrict__ w, T* __restrict__ y, int ldy, int Cout, float* __restrict__ stats,
     int B, int H, int W, int tilesX, int tilesY, unsigned x0_bytes, unsigned x1_bytes, unsigned y_bytes,
     const float* __restrict__ ep_scale, const float* __restrict__ ep_shift, int C0v, int C1v, int Coutv, int wfrag,
-    const float* __restrict__ pre_scale = nullptr, const float* __restrict__ pre_shift = nullptr,
     const T* __restrict__ bs_y = nullptr, int bs_ld = 0, unsigned bs_bytes = 0, const float* __restrict__ bs_coef = nullptr) {
-    static_assert(!PRE || (sizeof(T) == 2 && !SPLIT), "PRE is the bf16 training path");
-    static_assert(!BSUM || (sizeof(T) == 2 && !SPLIT && !PRE), "BSUM is the bf16 backward-data path");
-    static_assert(KS == 1 || (KS == 2 && sizeof(T) == 2 && NBW == 1 && !SPLIT && !WRES && !PRE), "KS = 2 is a bf16 NBW = 1 form");
+    static_assert(!BSUM || (sizeof(T) == 2 && !SPLIT), "BSUM is the bf16 backward-data path");
+    static_assert(KS == 1 || (KS == 2 && sizeof(T) == 2 && NBW == 1 && !SPLIT && !WRES), "KS = 2 is a bf16 NBW = 1 form");
     if constexpr (BSUM) {
         // a plain single-source call (the host checks it): folding the second source, the narrow-tensor counts and the inference
         // epilogue away frees the scalar registers the extra arguments take -- the scalar file is full (the base kernel already
@@ -642,17 +630,15 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
     // registers to spare for it (it spills inside its MFMA stream at distance 2) and keeps one row.
     constexpr int PF = WRES ? 1 : 2;
 
-    // TRI (the register-resident-filter form): THREE halo buffers, the DMA runs two chunks = one whole tile ahead.  With 16 channels
+    // WRES (the register-resident-filter form): THREE halo buffers, the DMA runs two chunks = one whole tile ahead.  With 16 channels
     // per wave a chunk is 144 MFMAs, and the two column shifts a double-buffered DMA has to land under (96 MFMAs, ~1 us beside the
     // SIMD's other wave) are shorter than an HBM round trip under load: the 64 -> 64 layers at 512 x 512 waited at every chunk fence
     // (scratch/r4_bsum_bench.sh with the cached-input variant: 141 -> 115 us per launch).  72 KB per workgroup, two per CU.
-    constexpr bool TRI = WRES && !PRE;
-    __shared__ __attribute__((aligned(16))) unsigned char lds_all[(TRI ? 3 : KS * 2) * HALO2_STRIDE];
+    __shared__ __attribute__((aligned(16))) unsigned char lds_all[(WRES ? 3 : KS * 2) * HALO2_STRIDE];
     // BatchNorm statistics of this workgroup's channels over ALL the tiles it processes, as pivot-shifted sums
     // S1 = sum (v - p), S2 = sum (v - p)^2 with p = one stored value of the channel (so that |mean - p| ~ std and the
     // final M2 = S2 - S1^2 / n does not cancel): one partial row per WORKGROUP (<= 768 rows), written once at the end.
     __shared__ float wg_sum[3][BN];          // [0] = S1, [1] = S2, [2] = pivot; slot = channel - co_blk
-    __shared__ __attribute__((aligned(16))) float pre_tab[PRE ? 2 * PRE_MAX_C : 4];     // PRE: (scale, shift) pairs of source 0
     __shared__ __attribute__((aligned(16))) float bs_tab[BSUM ? 4 * BN : 4];            // BSUM: [scale | shift | mean | rstd][slot]
     float n_run = 0.f;
 
@@ -837,55 +823,12 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
         f = u32x4{hi[0], hi[1], lo[0], lo[1]};
     };
 
-    // PRE: BatchNorm + ReLU of the producer, applied to the pieces THIS thread's DMA has just landed in buffer `bufi_t`
-    // (chunk `c`, the tile the scalars d_* describe).  Called behind the wave's vmcnt(0), in front of the chunk's barrier.
-    auto pre_transform = [&](int c, int bufi_t) {
-        if constexpr (PRE) {
-            const int cc = c * CK;
-            if (cc >= C0) return;                               // second source (skip concatenation): stored activated
-            unsigned char* bufp = lds + bufi_t * HALO2_STRIDE;
-            int tid_o = tid;                                     // (opaque: keeps the slot coordinates out of long-lived registers)
-            asm volatile("" : "+v"(tid_o));
-#pragma unroll
-            for (int k = 0; k < NLOAD; ++k) {
-                const int p = tid_o + k * 256, q = p >> 2;
-                const int hy = (q * 3641) >> 16, hx = q - hy * HALO_W;
-                bool ok = q < HALO_PIX;
-                if (!d_in) ok = ok && (unsigned)(d_y0 - 1 + hy) < (unsigned)H && (unsigned)(d_x0 - 1 + hx) < (unsigned)W;
-                if (ok) {
-                    const int part = (p & 3) ^ halo_swz(hx);
-                    u32x4* slot = reinterpret_cast<u32x4*>(bufp + p * 16);
-                    const u32x4 v = *slot;
-                    const f32x4* t = reinterpret_cast<const f32x4*>(pre_tab + (cc + part * VEC) * 2);
-                    const f32x4 t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];       // (s0, h0, s1, h1) ...
-                    float r[8];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        r[2 * e] = __uint_as_float(v[e] << 16);
-                        r[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u);
-                    }
-                    r[0] = uh_relu(fmaf(r[0], t0[0], t0[1])); r[1] = uh_relu(fmaf(r[1], t0[2], t0[3]));
-                    r[2] = uh_relu(fmaf(r[2], t1[0], t1[1])); r[3] = uh_relu(fmaf(r[3], t1[2], t1[3]));
-                    r[4] = uh_relu(fmaf(r[4], t2[0], t2[1])); r[5] = uh_relu(fmaf(r[5], t2[2], t2[3]));
-                    r[6] = uh_relu(fmaf(r[6], t3[0], t3[1])); r[7] = uh_relu(fmaf(r[7], t3[2], t3[3]));
-                    const bf16x8 o = {(bf16_t)r[0], (bf16_t)r[1], (bf16_t)r[2], (bf16_t)r[3],
-                                      (bf16_t)r[4], (bf16_t)r[5], (bf16_t)r[6], (bf16_t)r[7]};
-                    *slot = __builtin_bit_cast(u32x4, o);
-                }
-            }
-        }
-    };
     // end of a chunk: the next buffer's DMA (and the asynchronous filter loads) have landed, every wave is done reading the
-    // current buffer.  PRE: the wave's own pieces are rewritten between its vmcnt(0) and the barrier.
-    auto chunk_fence = [&](int c_next, int bufi_next, bool live_next) {
-        if constexpr (TRI) {
+    // current buffer.
+    auto chunk_fence = [&]() {
+        if constexpr (WRES) {
             // the six pieces of the chunk AFTER the next one stay in flight (vmcnt retires in order: everything older has landed)
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(NLOAD) : "memory");
-        } else if constexpr (PRE) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (live_next) pre_transform(c_next, bufi_next);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
@@ -986,15 +929,9 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
                     wres[c][t][n].v = u32x4{0u, 0u, 0u, 0u};
                     wfrag_async(wres[c][t][n], (int64_t)c * CK + wn_off(n) + (int64_t)t * Cin, n, t, c);
                 }
-        if constexpr (TRI) dma_chunk(1, 1, true);      // (behind the filter: the first fence leaves exactly these six in flight)
+        dma_chunk(1, 1, true);      // (behind the filter: the first fence leaves exactly these six in flight)
     } else {
         load_w(wA, chunk_of(v_first), 0);
-    }
-    if constexpr (PRE) {
-        // the coefficient table must be complete before the first rewrite: one extra barrier, once per kernel
-        for (int i = tid; i < C0; i += 256) { pre_tab[2 * i] = pre_scale[i]; pre_tab[2 * i + 1] = pre_shift[i]; }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (BSUM) {
         // this workgroup's BN channels of [scale | shift | mean | rstd] (Cout entries each); first read in the first epilogue,
@@ -1003,7 +940,7 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
-    chunk_fence(chunk_of(v_first), 0, true);
+    chunk_fence();
 
     for (; tile < ntile; tile += nlanes) {
         if (KS == 2 && tile != tile_lane) break;     // (one tile per workgroup: the host sizes the grid that way)
@@ -1020,26 +957,18 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
             for (int v = 0; v < 2; ++v) {
                 const unsigned char* buf = lds + bufi * HALO2_STRIDE;
                 mma_shift(buf, 0, [&](int r, int n) -> const WFrag& { return wres[v][r * 3 + 0][n]; });
-                if constexpr (TRI) {
-                    // chunk v of the NEXT tile, into the buffer the chunk in front of this one was read from
-                    const int b2 = bufi == 0 ? 2 : bufi - 1;
-                    if (v == 0) {
-                        live_next = next_tile < ntile;
-                        if (live_next) dma_tile(next_tile);
-                    }
-                    dma_chunk(v, b2, live_next);
-                } else if (v == 0) {
-                    dma_chunk(1, bufi ^ 1, true);
-                } else {
+                // chunk v of the NEXT tile, into the buffer the chunk in front of this one was read from
+                const int b2 = bufi == 0 ? 2 : bufi - 1;
+                if (v == 0) {
                     live_next = next_tile < ntile;
                     if (live_next) dma_tile(next_tile);
-                    dma_chunk(0, bufi ^ 1, live_next);
                 }
+                dma_chunk(v, b2, live_next);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_shift(buf, 1, [&](int r, int n) -> const WFrag& { return wres[v][r * 3 + 1][n]; });
                 mma_shift(buf, 2, [&](int r, int n) -> const WFrag& { return wres[v][r * 3 + 2][n]; });
-                chunk_fence(v == 0 ? 1 : 0, TRI ? 0 : (bufi ^ 1), live_next);
-                if constexpr (TRI) bufi = bufi == 2 ? 0 : bufi + 1; else bufi ^= 1;
+                chunk_fence();
+                bufi = bufi == 2 ? 0 : bufi + 1;
             }
         } else {
 #pragma unroll 1
@@ -1067,7 +996,7 @@ __global__ __launch_bounds__(256 * KS, ((NBW == 1 && !WRES && !BSUM && KS == 1) 
             UH_WAIT_VM(NLOAD + NWLOAD);               // WC landed (the DMA and WA' stay in flight)
             mma_shift(buf, 2, wsel(wC));
             // DMA and WA' landed; every wave has finished reading this buffer
-            chunk_fence(next_c, bufi ^ 1, live_next);
+            chunk_fence();
         }
         }
 
@@ -1921,23 +1850,23 @@ struct FwdPlan {
     int slabs, lanes;         // grid: output-channel slabs x tile lanes.  The conv3x3_fwd_mfma_v2 forms write one statistics /
                               // partial row per tile lane, the other kernels one per tile (lanes = tiles)
     int threads;              // workgroup size
-    bool split, pre, bsum;    // the call's family (see conv3x3_fwd_dispatch): bf16x3 products, BatchNorm+ReLU input, BatchNorm sums
+    bool split, bsum;         // the call's family (see conv3x3_fwd_dispatch): bf16x3 products, BatchNorm sums
 };
 
 // The one place that decides which kernel a forward / backward-data call gets and its grid: every entry point below and the
 // queries uh_conv3x3_fwd_kernel, uh_conv3x3_wfrag_ok and uh_conv3x3_dgrad_bnsum_rows take it from here.  es = element size;
 // ptrs16 = x0, x1, w and y are 16-byte aligned; y16 = y is.  The differences between the entry points are inputs: only plain
-// bf16 calls (no bf16x3 products, no narrow tensors) keep the filter in registers or split K, PRE never splits K, and BSUM runs
-// two workgroups per CU.
+// bf16 calls (no bf16x3 products, no narrow tensors) keep the filter in registers or split K, and BSUM runs two workgroups
+// per CU.
 // plan_B > 0 (the pinned plan of the eval forward): the kernel FORM is the one a launch of plan_B images of this H x W gets, or
 // the launch's own where the two add every pixel's products in the same order (fwd_sum_class); everything that sizes the launch
 // -- tiles, lanes, grid, the 2 GiB test -- stays with the real B.  plan_B = 0: the form of the real B.
 static FwdPlan fwd_plan(int es, int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, bool ptrs16, bool y16,
-                        bool split, bool narrow, bool pre, bool bsum, int plan_B = 0) {
+                        bool split, bool narrow, bool bsum, int plan_B = 0) {
     const int tiles1 = ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
     const int ntile = B * tiles1;
     const int ck = 64 / es, Cin = C0 + C1;
-    FwdPlan p = {FWD_SIMT, 0, 1, ntile, 256, split, pre, bsum};
+    FwdPlan p = {FWD_SIMT, 0, 1, ntile, 256, split, bsum};
     const bool mfma = C0 % ck == 0 && C1 % ck == 0 && Cout % 64 == 0 && ptrs16 && (ld0 * es) % 16 == 0 &&
                       (C1 == 0 || (ld1 * es) % 16 == 0) && (ldy * es) % 16 == 0;
     if (!mfma) {
@@ -1968,7 +1897,7 @@ static FwdPlan fwd_plan(int es, int B, int H, int W, int C0, int C1, int Cout, i
         // 128-channel slabs halve the halo re-reads, but small feature maps need the extra workgroups
         if (Cout % 128 == 0 && nt * (Cout / 128) >= 512) return FWD_SLAB128;
         if (bf16 && Cin == 64) return FWD_WRES;
-        if (bf16 && !pre && fwd_ksplit_ok(nt, Cin, Cout)) return FWD_KSPLIT;
+        if (bf16 && fwd_ksplit_ok(nt, Cin, Cout)) return FWD_KSPLIT;
         return FWD_STREAM;
     };
     p.kernel = form(ntile);
@@ -1986,36 +1915,34 @@ static FwdPlan fwd_plan(int es, int B, int H, int W, int C0, int C1, int Cout, i
 }
 
 // One conv3x3_fwd_mfma_v2 launch in the form p.kernel of one family; args = the kernel's arguments.  Only the combinations that
-// exist are instantiated: the register-resident filter and the K split are bf16 forms, and PRE has no K split.
-template <typename T, bool SPLIT, bool PRE, bool BSUM, typename... Args>
+// exist are instantiated: the register-resident filter and the K split are bf16 forms.
+template <typename T, bool SPLIT, bool BSUM, typename... Args>
 static void fwd_v2_form(const FwdPlan& p, hipStream_t st, Args... args) {
     constexpr bool BF16 = sizeof(T) == 2 && !SPLIT;
     const dim3 grid(p.lanes * p.slabs), block(p.threads);
     switch (p.kernel) {
-    case FWD_SLAB128: hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 2, SPLIT, false, PRE, BSUM>), grid, block, 0, st, args...); break;
+    case FWD_SLAB128: hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 2, SPLIT, false, BSUM>), grid, block, 0, st, args...); break;
     case FWD_WRES:
-        if constexpr (BF16) hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, true, PRE, BSUM>), grid, block, 0, st, args...);
+        if constexpr (BF16) hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, true, BSUM>), grid, block, 0, st, args...);
         break;
     case FWD_KSPLIT:
-        if constexpr (BF16 && !PRE) hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, false, false, BSUM, 2>), grid, block, 0, st, args...);
+        if constexpr (BF16) hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, false, false, BSUM, 2>), grid, block, 0, st, args...);
         break;
-    case FWD_STREAM: hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, SPLIT, false, PRE, BSUM>), grid, block, 0, st, args...); break;
+    case FWD_STREAM: hipLaunchKernelGGL((conv3x3_fwd_mfma_v2<T, 1, SPLIT, false, BSUM>), grid, block, 0, st, args...); break;
     default: break;
     }
 }
 
-// The families: fp32 and bf16 plain calls, bf16x3 products (fp32 tensors), PRE (bf16, UH_BUILD_PRE builds only), BSUM (bf16).
+// The families: fp32 and bf16 plain calls, bf16x3 products (fp32 tensors), BSUM (bf16).
 template <typename T, typename... Args>
 static void fwd_v2_launch(const FwdPlan& p, hipStream_t st, Args... args) {
     constexpr bool BF16 = sizeof(T) == 2;
     if (p.split) {
-        if constexpr (!BF16) fwd_v2_form<T, true, false, false>(p, st, args...);
+        if constexpr (!BF16) fwd_v2_form<T, true, false>(p, st, args...);
     } else if (p.bsum) {
-        if constexpr (BF16) fwd_v2_form<T, false, false, true>(p, st, args...);
-    } else if (p.pre) {
-        if constexpr (BF16 && UH_BUILD_PRE) fwd_v2_form<T, false, true, false>(p, st, args...);
+        if constexpr (BF16) fwd_v2_form<T, false, true>(p, st, args...);
     } else {
-        fwd_v2_form<T, false, false, false>(p, st, args...);
+        fwd_v2_form<T, false, false>(p, st, args...);
     }
 }
 
@@ -2027,7 +1954,6 @@ struct ConvCall {
     int dt = UH_F32;                                             // UH_F32X3 = bf16x3 products on fp32 tensors; set by conv_check
     bool wfrag = false;                                          // forward: the filter pack is fragment-major; set by conv_check
     int C0v = -1, C1v = -1, Coutv = -1;                          // narrow tensors: the valid channel counts
-    const float *pre_scale = nullptr, *pre_shift = nullptr;      // PRE: BatchNorm + ReLU of the producer applied to source 0 by the loader
     hipStream_t st = nullptr;
 };
 struct FwdCall : ConvCall {
@@ -2068,24 +1994,19 @@ static int conv3x3_fwd_dispatch(FwdCall& c) {
     const T *x0 = (const T*)c.x0, *x1 = (const T*)c.x1, *w = (const T*)c.w, *bs_y = (const T*)c.bs_y;
     T* y = (T*)c.y;
     const float *ep_scale = c.ep_scale, *ep_shift = c.ep_shift;     // (dropped below where the epilogue cannot load them)
-    const bool split = c.dt == UH_F32X3, narrow = c.C0v >= 0, pre = c.pre_scale != nullptr, bsum = bs_y != nullptr;
+    const bool split = c.dt == UH_F32X3, narrow = c.C0v >= 0, bsum = bs_y != nullptr;
     const int C0v = narrow ? c.C0v : c.C0, C1v = narrow ? c.C1v : c.C1, Coutv = narrow ? c.Coutv : c.Cout;
     c.ep_done = false;
     constexpr int ES = sizeof(T);
     const int tilesX = (c.W + TILE - 1) / TILE, tilesY = (c.H + TILE - 1) / TILE;
     const int Cin = c.C0 + c.C1;
     const bool ptrs16 = uh_aligned16(x0) && (c.C1 == 0 || uh_aligned16(x1)) && uh_aligned16(w) && uh_aligned16(y);
-    const FwdPlan p = fwd_plan(ES, c.B, c.H, c.W, c.C0, c.C1, c.Cout, c.ld0, c.ld1, c.ldy, ptrs16, uh_aligned16(y), split, narrow, pre, bsum, c.plan_B);
+    const FwdPlan p = fwd_plan(ES, c.B, c.H, c.W, c.C0, c.C1, c.Cout, c.ld0, c.ld1, c.ldy, ptrs16, uh_aligned16(y), split, narrow, bsum, c.plan_B);
     if (p.kernel != FWD_SIMT && p.kernel != FWD_LARGE) {
         if (ep_scale && !(uh_aligned16(ep_scale) && uh_aligned16(ep_shift))) ep_scale = ep_shift = nullptr;   // 16-B loads
         UH_REQUIRE(!split || ES == 4, "conv3x3_fwd: bf16x3 needs fp32 tensors");
         UH_REQUIRE(!(split && c.wfrag), "conv3x3_fwd: bf16x3 filters are KRSC packs");
         UH_REQUIRE(!(narrow && c.wfrag), "conv3x3_fwd: narrow-tensor calls take KRSC packs");
-        if (pre) {
-            UH_REQUIRE(UH_BUILD_PRE, "conv3x3_fwd: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
-            UH_REQUIRE(ES == 2, "conv3x3_fwd: the fused BatchNorm+ReLU input is a bf16 path; ask uh_conv3x3_pre_ok first");
-            UH_REQUIRE(!(split || narrow || c.C0 > PRE_MAX_C), "conv3x3_fwd: the fused BatchNorm+ReLU input needs a plain bf16 call with at most %d channels in source 0; ask uh_conv3x3_pre_ok first", PRE_MAX_C);
-        }
         const int64_t px = (int64_t)c.B * c.H * c.W, bq = bsum ? px * c.bs_ld * ES : 0;
         if (bsum) {
             UH_REQUIRE(ES == 2, "uh_conv3x3_dgrad_bnsum: bf16 only; ask uh_conv3x3_dgrad_bnsum_rows first");
@@ -2095,14 +2016,12 @@ static int conv3x3_fwd_dispatch(FwdCall& c) {
         // byte extents of x0, x1, y and q for the buffer descriptors (below 2 GiB: fwd_plan)
         fwd_v2_launch<T>(p, c.st, x0, c.C0, c.ld0, x1, c.C1, c.ld1, w, y, c.ldy, c.Cout, c.stats, c.B, c.H, c.W, tilesX, tilesY, (unsigned)(px * c.ld0 * ES),
                          (unsigned)(c.C1 ? px * c.ld1 * ES : 0), (unsigned)(px * c.ldy * ES), ep_scale, ep_shift, C0v, C1v, Coutv,
-                         c.wfrag ? 1 : 0, c.pre_scale, c.pre_shift, bs_y, c.bs_ld, (unsigned)bq, c.bs_coef);
-        UH_CHECK_LAUNCH(pre ? "conv3x3_fwd_mfma_v2 (BatchNorm+ReLU input)"
-                            : bsum ? "conv3x3_fwd_mfma_v2 (backward-data + BatchNorm sums)" : "conv3x3_fwd_mfma_v2");
+                         c.wfrag ? 1 : 0, bs_y, c.bs_ld, (unsigned)bq, c.bs_coef);
+        UH_CHECK_LAUNCH(bsum ? "conv3x3_fwd_mfma_v2 (backward-data + BatchNorm sums)" : "conv3x3_fwd_mfma_v2");
         c.ep_done = ep_scale != nullptr;
         return UH_OK;
     }
     if (p.kernel == FWD_LARGE) {
-        UH_REQUIRE(!pre, "conv3x3_fwd: the fused BatchNorm+ReLU input needs the LDS-DMA MFMA kernel (tensors below 2 GiB); ask uh_conv3x3_pre_ok first");
         UH_REQUIRE(!bsum, "uh_conv3x3_dgrad_bnsum: needs the LDS-DMA MFMA kernel (tensors below 2 GiB); ask uh_conv3x3_dgrad_bnsum_rows first");
         UH_REQUIRE(!c.wfrag, "conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but this call cannot take the LDS-DMA MFMA kernel (a tensor of 2 GiB or more); ask uh_conv3x3_wfrag_ok first");
         UH_REQUIRE(!split, "conv3x3_fwd: bf16x3 is implemented for tensors below 2 GiB only");
@@ -2116,7 +2035,6 @@ static int conv3x3_fwd_dispatch(FwdCall& c) {
         UH_CHECK_LAUNCH("conv3x3_fwd_mfma");
         return UH_OK;
     }
-    UH_REQUIRE(!pre, "conv3x3_fwd: the fused BatchNorm+ReLU input needs an MFMA-aligned shape; ask uh_conv3x3_pre_ok first");
     UH_REQUIRE(!bsum, "uh_conv3x3_dgrad_bnsum: needs an MFMA-aligned shape; ask uh_conv3x3_dgrad_bnsum_rows first");
     UH_REQUIRE(!c.wfrag, "conv3x3_fwd: the filter is packed fragment-major (UH_WFRAG) but the shape / alignment is outside the MFMA path; ask uh_conv3x3_wfrag_ok first");
     UH_REQUIRE(!split, "conv3x3_fwd: bf16x3 needs an MFMA-aligned shape (Cin %% 16 == 0, Cout %% 64 == 0, 16-byte strides)");
@@ -2183,7 +2101,7 @@ extern "C" int uh_conv3x3_wfrag_ok_plan(int B, int plan_B, int H, int W, int C0,
     if (dt != UH_F32 && dt != UH_BF16) return 0;
     if (B <= 0 || plan_B < 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0) return 0;
     const FwdKernel k = fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, ld0, ld1, ldy, true, true, false, false, false,
-                                 false, plan_B).kernel;
+                                 plan_B).kernel;
     return k != FWD_SIMT && k != FWD_LARGE;
 }
 extern "C" int uh_conv3x3_wfrag_ok(int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int ldy, int dt) {
@@ -2195,8 +2113,7 @@ extern "C" int uh_conv3x3_wfrag_ok(int B, int H, int W, int C0, int C1, int Cout
 extern "C" int uh_conv3x3_fwd_kernel(int B, int H, int W, int C0, int C1, int Cout, int dt) {
     UH_REQUIRE(B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd_kernel: bad shape");
     UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_fwd_kernel: bad dtype %d", dt);
-    return fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, true, true, dt == UH_F32X3, false, false,
-                    false).kernel;
+    return fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, true, true, dt == UH_F32X3, false, false).kernel;
 }
 
 // The same question for the pinned call: the kernel uh_conv3x3_fwd_affine_relu_plan(.., B, plan_B, ..) runs.  plan_B = 0 is
@@ -2205,39 +2122,13 @@ extern "C" int uh_conv3x3_fwd_kernel_plan(int B, int plan_B, int H, int W, int C
     UH_REQUIRE(B > 0 && plan_B >= 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_fwd_kernel_plan: bad shape");
     UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_fwd_kernel_plan: bad dtype %d", dt);
     return fwd_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, true, true, dt == UH_F32X3, false, false,
-                    false, plan_B).kernel;
+                    plan_B).kernel;
 }
 
 // The summation class of a kernel code (fwd_sum_class): two codes with one class give bit-identical outputs.
 extern "C" int uh_conv3x3_fwd_sum_class(int kernel) {
     UH_REQUIRE(kernel >= FWD_SIMT && kernel <= FWD_LARGE, "uh_conv3x3_fwd_sum_class: bad kernel code %d", kernel);
     return fwd_sum_class(kernel);
-}
-
-// Training forward whose input is the RAW output y_prev of the previous conv: the BatchNorm + ReLU between the two convs of a
-// DoubleConv (unet_parts.py:16-17) is applied by this kernel's loader, x = max(y_prev * pre_scale + pre_shift, 0) rounded to the
-// activation dtype exactly as uh_bn_relu_apply stores it -- the activation itself is never written.  bf16, single source of
-// <= 512 channels, LDS-DMA MFMA kernel only: uh_conv3x3_pre_ok says whether a call qualifies (else run uh_bn_relu_apply).
-extern "C" int uh_conv3x3_pre_ok(int B, int H, int W, int C0, int Cout, int ld0, int ldy, int dt) {
-#if !UH_BUILD_PRE
-    return 0;            // the default library does not carry the PRE instantiations (measured a net loss: DESIGN.md section 3)
-#endif
-    if (dt != UH_BF16 || C0 > PRE_MAX_C) return 0;
-    if (C0 % 64 || Cout % 64) return 0;                  // (backward-weights of the same layer works on 64-channel slabs)
-    return uh_conv3x3_wfrag_ok(B, H, W, C0, 0, Cout, ld0, 0, ldy, dt);
-}
-
-extern "C" int uh_conv3x3_fwd_pre(const void* x0, int C0, int ld0, const float* pre_scale, const float* pre_shift, const void* w,
-                                  void* y, int ldy, int Cout, float* stat_partials, int B, int H, int W, int dt,
-                                  uh_stream stream) {
-    UH_REQUIRE(pre_scale && pre_shift, "uh_conv3x3_fwd_pre: null pointer");
-    FwdCall c;
-    c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.w = w; c.y = y; c.ldy = ldy; c.Cout = Cout; c.stats = stat_partials;
-    c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream; c.pre_scale = pre_scale; c.pre_shift = pre_shift;
-    if (const int rc = conv_check("uh_conv3x3_fwd_pre", c, c.w && c.y, c.ldy, dt, CK_BF16_ONLY | CK_WFRAG)) return rc;
-    UH_REQUIRE(UH_BUILD_PRE, "uh_conv3x3_fwd_pre: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
-    UH_REQUIRE(uh_conv3x3_pre_ok(B, H, W, C0, Cout, ld0, ldy, c.dt), "uh_conv3x3_fwd_pre: shape outside the fused path (uh_conv3x3_pre_ok)");
-    return conv3x3_fwd_dispatch<bf16_t>(c);
 }
 
 // Backward-data of the second conv of a DoubleConv together with the first half of the BatchNorm backward of the layer in
@@ -2249,7 +2140,7 @@ extern "C" int uh_conv3x3_dgrad_bnsum_rows(int B, int H, int W, int Cdy, int Cdx
     if (dt != UH_BF16) return 0;
     if (!uh_conv3x3_wfrag_ok(B, H, W, Cdy, 0, Cdx, lddy, 0, lddx, dt)) return 0;
     if (ldq != lddx) return 0;                 // q is addressed with the offsets of the tensor being written
-    return fwd_plan(2, B, H, W, Cdy, 0, Cdx, lddy, 0, lddx, true, true, false, false, false, true).lanes;
+    return fwd_plan(2, B, H, W, Cdy, 0, Cdx, lddy, 0, lddx, true, true, false, false, true).lanes;
 }
 
 extern "C" int uh_conv3x3_dgrad_bnsum(const void* dy, int Cdy, int lddy, const void* w_dgrad, void* dx, int lddx, int Cdx,
@@ -2777,11 +2668,6 @@ __global__ __launch_bounds__(256) void slab_reduce_batched_kernel(const int64_t*
 // 4 -> 128 co x 64 ci, 8 waves, one workgroup per CU: the x halo image (the operand with the 1.4x halo) is staged once for
 // twice the MFMA work, 30 % fewer DMA bytes / pieces per MFMA -- the kernel is bound by the rate at which L2 / Infinity
 // Cache fill the LDS images (TCC hit rate 26 %, 36 GB/s per CU needed at the full MFMA rate), not by the matrix pipe.
-// PRE: x0 is the RAW output of the previous conv; its BatchNorm + ReLU (the layer's real input, never stored: see
-// conv3x3_fwd_mfma_v2) is applied to the x image in LDS by the thread that issued the DMA piece, behind the wave's vmcnt(0) and in
-// front of the tile's barrier.  LDS is full (two workgroups x two stages = 160 KiB), so the 64 (scale, shift) pairs of the
-// workgroup's input-channel slab live in ONE register pair spread over the lanes (lane = channel) and reach the lane that needs
-// them through ds_bpermute (the LDS crossbar, no LDS memory).
 // SLAB16: the per-split partial results go to the workspace as 16-bit PAIRS (u32 = rows co, co + 1 of one (tap, ci)) instead of
 // fp32: half the 75 MB a launch writes and slab_reduce reads back.  Each partial is a sum over >= one tile of pixels accumulated
 // in fp32 by the MFMAs and rounded ONCE, to fp16 (11 significant bits, rms relative error 2^-12.8) after multiplication by a power
@@ -2793,12 +2679,11 @@ __global__ __launch_bounds__(256) void slab_reduce_batched_kernel(const int64_t*
 // the bf16 filter copy): 8-13 x on synthetic region-signed gradients, up to 2.7 x on one layer of a trained UNet, 0.1-0.9 x
 // elsewhere (scratch/r5_slab_structured.py).  Three more bits put all of them at or below the reference's own rounding.)
 // fp32 slabs: UH_WGRAD_SLAB_F32=1.
-template <typename T, int NWR, bool PRE = false, bool SLAB16 = false>
+template <typename T, int NWR, bool SLAB16 = false>
 __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
     const T* __restrict__ dy, int lddy, const T* __restrict__ x0, int C0, int ld0, const T* __restrict__ x1, int C1,
     int ld1, float* __restrict__ slabs, int Cout, int B, int H, int W, int tilesX, int tilesY, int nsplit,
-    unsigned dy_bytes, unsigned x_bytes, int C0v, int C1v, int Coutv, const float* __restrict__ pre_scale = nullptr,
-    const float* __restrict__ pre_shift = nullptr) {
+    unsigned dy_bytes, unsigned x_bytes, int C0v, int C1v, int Coutv) {
     static_assert(sizeof(T) == 2, "v2 is the bf16 kernel");
     constexpr int TH = 8;
     constexpr int NT = 128 * NWR;               // threads
@@ -2928,66 +2813,9 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
         x_hi[s] = rowsel * 4 * (HALO_W * PB) + col_off(s + colh * 8 + rq + 4, b_cbyte);
     }
 
-    // PRE: lane l of every wave holds (scale, shift) of channel ci0 + l of source 0 (loaded -- and waited for -- before the first
-    // asynchronous DMA is in flight, so that the compiler's own wait for these two loads cannot miscount)
-    float pre_s = 0.f, pre_h = 0.f;
-    const bool pre_on = PRE && ci0 < C0;
-    if constexpr (PRE) {
-        if (pre_on) { pre_s = pre_scale[ci0 + lane]; pre_h = pre_shift[ci0 + lane]; }
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(pre_s), "+v"(pre_h) :: "memory");
-    }
-    auto pre_x = [&](int tile, int bufi_t) {
-        if constexpr (PRE) {
-            if (!pre_on) return;
-            int t = tile;
-            const int txt = t % tilesX; t /= tilesX;
-            const int tyt = t % tilesY;
-            const int y0 = tyt * TH, x0p = txt * TILE;
-            const bool inside = y0 >= 1 && y0 + TH + 1 <= H && x0p >= 1 && x0p + TILE + 1 <= W;
-            unsigned char* xs_t = lds + bufi_t * STAGE;
-#pragma unroll
-            for (int k = 0; k < XR; ++k) {
-                bool ok = xg[k] >= 0;
-                const int hy = xg[k] >> 8, hx = xg[k] & 255;
-                if (!inside) ok = ok && (unsigned)(y0 - 1 + hy) < (unsigned)H && (unsigned)(x0p - 1 + hx) < (unsigned)W;
-                // every lane takes part in the permutes (they are cross-lane), only valid pieces are rewritten
-                const int p = tid + k * NT;
-                const int u = (p & 7) ^ (((hx >> 1) & 1) << 2);
-                // (two channel quads in turn: 8 coefficients + 4 values live at a time -- the kernel runs at the register limit)
-                u32x4* slot = reinterpret_cast<u32x4*>(xs_t + p * 16);
-                u32x4 v = {0u, 0u, 0u, 0u};
-                if (ok) v = *slot;
-#pragma unroll
-                for (int hq = 0; hq < 2; ++hq) {
-                    float sc[4], sh[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        sc[e] = __int_as_float(__builtin_amdgcn_ds_bpermute((u * 8 + hq * 4 + e) * 4, __float_as_int(pre_s)));
-                        sh[e] = __int_as_float(__builtin_amdgcn_ds_bpermute((u * 8 + hq * 4 + e) * 4, __float_as_int(pre_h)));
-                    }
-                    const float r0 = uh_relu(fmaf(__uint_as_float(v[2 * hq] << 16), sc[0], sh[0]));
-                    const float r1 = uh_relu(fmaf(__uint_as_float(v[2 * hq] & 0xffff0000u), sc[1], sh[1]));
-                    const float r2 = uh_relu(fmaf(__uint_as_float(v[2 * hq + 1] << 16), sc[2], sh[2]));
-                    const float r3 = uh_relu(fmaf(__uint_as_float(v[2 * hq + 1] & 0xffff0000u), sc[3], sh[3]));
-                    const bf16x4 o = {(bf16_t)r0, (bf16_t)r1, (bf16_t)r2, (bf16_t)r3};
-                    const u32x2 ou = __builtin_bit_cast(u32x2, o);
-                    v[2 * hq] = ou[0];
-                    v[2 * hq + 1] = ou[1];
-                }
-                if (ok) *slot = v;
-            }
-        }
-    };
     // end of a tile: the DMA of the next tile has landed and every wave has finished reading this buffer
-    auto tile_fence = [&](int next_tile, int bufi_next, bool live_next) {
-        if constexpr (PRE) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (live_next) pre_x(next_tile, bufi_next);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
+    auto tile_fence = [&]() {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     };
 
@@ -3000,9 +2828,6 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
         s16x8 both = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
         return __builtin_bit_cast(bf16x8, both);
     };
-    // (the consumer-side BatchNorm variants -- UH_BUILD_PRE -- keep the round-3 loop, one barrier at the very end of a tile: their
-    // rewrite of the x image sits inside the fence, and inside the rotated MFMA stream it spills)
-    if constexpr (!PRE) {
     // ROTATED tile loop.  A tile = six x row pairs a (fragments of pair a + 1 are fetched while pair a is multiplied; dy pair
     // p = a - r meets tap row r); the last LDS reads of a tile are those of pair 5, requested in front of pair 4's MFMAs.  The
     // end-of-tile fence (next tile's DMA landed, everyone done READING this buffer) therefore sits in front of pair 5's twelve
@@ -3041,7 +2866,7 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
         }
     };
     if (t_begin < t_end) issue(t_begin, 0);
-    tile_fence(t_begin, 0, t_begin < t_end);
+    tile_fence();
     ld_d(lds + XBYTES, 0);
     ld_x(lds, 0);
     int bufi = 0;
@@ -3062,7 +2887,7 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
             mma_pair(a);
         }
         // every LDS read of this tile has been issued (pair 5's in front of pair 4's MFMAs)
-        tile_fence(tile + 1, bufi ^ 1, tile + 1 < t_end);
+        tile_fence();
         {
             // (unconditional: behind the last tile these sixteen reads fetch stale LDS contents nobody uses -- a branch here
             // makes the fragments phi nodes of the loop and costs ~20 spilled registers around the fence)
@@ -3072,60 +2897,6 @@ __global__ __launch_bounds__(128 * NWR, 2) void conv3x3_wgrad_mfma_v2(
         }
         __builtin_amdgcn_sched_barrier(0);
         mma_pair(5);
-    }
-    } else {
-    if (t_begin < t_end) issue(t_begin, 0);
-    tile_fence(t_begin, 0, t_begin < t_end);
-    int bufi = 0;
-    for (int tile = t_begin; tile < t_end; ++tile, bufi ^= 1) {
-        const unsigned char* xs = lds + bufi * STAGE;
-        const unsigned char* ds = xs + XBYTES;
-        // fully unrolled over the six x row pairs (a, a + 4): the fragments of pair a + 1 are fetched while pair a is
-        // multiplied; dy pair p = a - r meets tap row r
-        bf16x8 dfr[4][2];
-        bf16x8 xfr[6][3][2];
-        auto ld_x = [&](int a) {
-#pragma unroll
-            for (int sft = 0; sft < 3; ++sft)
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh)
-                    xfr[a][sft][hh] = tr_pair(xs + a * (HALO_W * PB) + hh * 32, x_lo[sft], x_hi[sft]);
-        };
-        auto ld_d = [&](int pr) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) dfr[pr][h] = tr_pair(ds + pr * (TILE * DPB) + h * 32, d_lo, d_hi);
-        };
-        ld_d(0);
-        ld_x(0);
-        // The next tile's DMA (ten pieces per thread, ~150 VALU instructions of address arithmetic) is issued HERE, behind the tile's
-        // first fragment reads: at the top of the tile that arithmetic ran in front of them, with every wave of the workgroup just
-        // released from the barrier and the matrix pipe empty; now it runs under the LDS latency of the reads the first MFMAs wait
-        // for (profiles/r03_wgrad_phase_stamps.txt).  The buffer it writes was released by the barrier at the end of the last tile.
-        __builtin_amdgcn_sched_barrier(0);
-        if (tile + 1 < t_end) issue(tile + 1, bufi ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            if (a + 1 < 6) ld_x(a + 1);
-            if (a + 1 < 4) ld_d(a + 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int pr = a - r;
-                if (pr >= 0 && pr < 4) {
-#pragma unroll
-                    for (int sft = 0; sft < 3; ++sft)
-#pragma unroll
-                        for (int h = 0; h < 2; ++h)
-#pragma unroll
-                            for (int hh = 0; hh < 2; ++hh)
-                                acc[r * 3 + sft][h][hh] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dfr[pr][h], xfr[a][sft][hh],
-                                                                                                 acc[r * 3 + sft][h][hh], 0, 0, 0);
-                }
-            }
-        }
-        tile_fence(tile + 1, bufi ^ 1, tile + 1 < t_end);
-    }
     }
 
     if constexpr (SLAB16) {
@@ -3516,7 +3287,7 @@ struct WgradPlan {
     int nsplit;                   // pixel ranges, one slab of Cout * 9 * Cin partial sums each
     dim3 grid;
     int threads;                  // workgroup size
-    bool slab16, pre;             // the slabs are block-scaled fp16 pairs (see SLAB16), else fp32; the call has a BatchNorm+ReLU input
+    bool slab16;                  // the slabs are block-scaled fp16 pairs (see SLAB16), else fp32
     SlabReduce reduce;
 };
 struct WgradAlign { bool ptrs, dy, dw, ws; };      // 16-byte aligned: dy, x0 and x1 together; dy; the result; the workspace
@@ -3527,12 +3298,12 @@ static size_t wgrad_slab_bytes(const WgradPlan& p) { return (size_t)p.nsplit * p
 // point below and the queries uh_conv3x3_wgrad_plan and uh_conv3x3_wgrad_ws_bytes take it from here.  es = element size.  Of the
 // families only `narrow` decides anything: a narrow call keeps the 64-row tile.
 static WgradPlan wgrad_plan(int es, int B, int H, int W, int C0, int C1, int Cout, int ld0, int ld1, int lddy, WgradAlign a16,
-                            bool narrow, bool pre) {
+                            bool narrow) {
     static const bool slab_f32 = getenv("UH_WGRAD_SLAB_F32") != nullptr && getenv("UH_WGRAD_SLAB_F32")[0] == '1';
     static_assert(WgradCfg<bf16_t>::TH == WgradCfg<float>::TH, "one pixel-tile height for both element types");
     const int Cin = C0 + C1;
     const int64_t n = (int64_t)Cout * 9 * Cin;
-    WgradPlan p = {WG_GENERIC, 0, 0, 0, dim3(Cout * 9), 256, false, pre, {SR_NONE, n, 0, 0, 9 * Cin, 0}};
+    WgradPlan p = {WG_GENERIC, 0, 0, 0, dim3(Cout * 9), 256, false, {SR_NONE, n, 0, 0, 9 * Cin, 0}};
     const bool dy_ok = a16.dy && (lddy * es) % 16 == 0;
     int nwr = 2;
     if (a16.ptrs && dy_ok && (ld0 * es) % 16 == 0 && (C1 == 0 || (ld1 * es) % 16 == 0) && C0 % 64 == 0 && Cin % 64 == 0 && Cout % 64 == 0) {
@@ -3566,38 +3337,31 @@ static WgradPlan wgrad_plan(int es, int B, int H, int W, int C0, int C1, int Cou
 extern "C" size_t uh_conv3x3_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int dt) {
     // alignment and the family are unknown here: dense pitches, everything aligned, the larger of the 128- and 64-row tile plans
     const int es = dt == UH_BF16 ? 2 : 4;
-    const size_t wide = wgrad_slab_bytes(wgrad_plan(es, B, H, W, Cin, 0, Cout, Cin, 0, Cout, WG_ALIGNED, false, false));
-    const size_t narrow = wgrad_slab_bytes(wgrad_plan(es, B, H, W, Cin, 0, Cout, Cin, 0, Cout, WG_ALIGNED, true, false));
+    const size_t wide = wgrad_slab_bytes(wgrad_plan(es, B, H, W, Cin, 0, Cout, Cin, 0, Cout, WG_ALIGNED, false));
+    const size_t narrow = wgrad_slab_bytes(wgrad_plan(es, B, H, W, Cin, 0, Cout, Cin, 0, Cout, WG_ALIGNED, true));
     return (wide > narrow ? wide : narrow) + 16;
 }
 
 extern "C" int uh_conv3x3_wgrad_plan(int B, int H, int W, int C0, int C1, int Cout, int dt, int narrow, int64_t* out) {
     UH_REQUIRE(out && B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0, "uh_conv3x3_wgrad_plan: null pointer or bad shape");
     UH_REQUIRE(dt == UH_F32 || dt == UH_BF16 || dt == UH_F32X3, "uh_conv3x3_wgrad_plan: bad dtype %d", dt);
-    const WgradPlan p = wgrad_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, WG_ALIGNED, narrow != 0, false);
+    const WgradPlan p = wgrad_plan(dt == UH_BF16 ? 2 : 4, B, H, W, C0, C1, Cout, C0, C1, Cout, WG_ALIGNED, narrow != 0);
     out[0] = p.kernel; out[1] = p.nsplit; out[2] = p.grid.x; out[3] = p.grid.y; out[4] = p.threads; out[5] = p.slab16 ? 1 : 0;
     out[6] = p.reduce.kernel; out[7] = p.reduce.blocks;
     return UH_OK;
 }
 
-// One conv3x3_wgrad_mfma_v2 launch in the tile and the slab format the plan names; args = the kernel's arguments.  Only the
-// instantiations that exist: bf16, and the PRE forms in UH_BUILD_PRE builds.
+// One conv3x3_wgrad_mfma_v2 launch in the tile and the slab format the plan names; args = the kernel's arguments.  The
+// kernel is bf16 only: the caller instantiates this for T = bf16.
 template <typename T, typename... Args>
 static void wgrad_v2_launch(const WgradPlan& p, hipStream_t st, Args... args) {
-    auto form = [&](auto pre) {
-        constexpr bool PRE = decltype(pre)::value;
-        const dim3 block(p.threads);
-        switch ((p.kernel == WG_DMA128 ? 2 : 0) + (p.slab16 ? 1 : 0)) {      // the 128-row tile, fp16-pair slabs
-        case 3: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 4, PRE, true>), p.grid, block, 0, st, args...); break;
-        case 2: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 4, PRE, false>), p.grid, block, 0, st, args...); break;
-        case 1: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 2, PRE, true>), p.grid, block, 0, st, args...); break;
-        default: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 2, PRE, false>), p.grid, block, 0, st, args...); break;
-        }
-    };
-    if (p.pre) {
-        if constexpr (UH_BUILD_PRE) form(std::true_type{});
-    } else
-        form(std::false_type{});
+    const dim3 block(p.threads);
+    switch ((p.kernel == WG_DMA128 ? 2 : 0) + (p.slab16 ? 1 : 0)) {      // the 128-row tile, fp16-pair slabs
+    case 3: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 4, true>), p.grid, block, 0, st, args...); break;
+    case 2: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 4, false>), p.grid, block, 0, st, args...); break;
+    case 1: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 2, true>), p.grid, block, 0, st, args...); break;
+    default: hipLaunchKernelGGL((conv3x3_wgrad_mfma_v2<T, 2, false>), p.grid, block, 0, st, args...); break;
+    }
 }
 
 struct WgradCall : ConvCall {
@@ -3614,16 +3378,14 @@ static int conv3x3_wgrad_dispatch(const WgradCall& c) {
     float* slabs = (float*)c.ws;
     constexpr int ES = sizeof(T);
     const int Cin = c.C0 + c.C1;
-    const bool split = c.dt == UH_F32X3, narrow = c.C0v >= 0, pre = c.pre_scale != nullptr;
+    const bool split = c.dt == UH_F32X3, narrow = c.C0v >= 0;
     const int C0v = narrow ? c.C0v : c.C0, C1v = narrow ? c.C1v : c.C1, Coutv = narrow ? c.Coutv : c.Cout;
     const WgradAlign a16 = {uh_aligned16(dy) && uh_aligned16(x0) && (c.C1 == 0 || uh_aligned16(x1)), uh_aligned16(dy), uh_aligned16(c.dw),
                             uh_aligned16(slabs)};
-    const WgradPlan p = wgrad_plan(ES, c.B, c.H, c.W, c.C0, c.C1, c.Cout, c.ld0, c.ld1, c.lddy, a16, narrow, pre);
-    const bool mfma = p.kernel >= WG_MFMA, dma = p.kernel >= WG_DMA64;
+    const WgradPlan p = wgrad_plan(ES, c.B, c.H, c.W, c.C0, c.C1, c.Cout, c.ld0, c.ld1, c.lddy, a16, narrow);
+    const bool mfma = p.kernel >= WG_MFMA;
     UH_REQUIRE(!narrow || mfma, "uh_conv3x3_wgrad_narrow: needs the MFMA path (padded channel counts multiples of 64, 16-byte strides)");
     UH_REQUIRE(!split || mfma, "uh_conv3x3_wgrad: bf16x3 needs an MFMA-aligned shape (channel counts multiples of 64, 16-byte strides)");
-    UH_REQUIRE(!pre || UH_BUILD_PRE, "uh_conv3x3_wgrad_pre: the consumer-side BatchNorm+ReLU instantiations are not in this build (UH_BUILD_PRE=1); uh_conv3x3_pre_ok says so");
-    UH_REQUIRE(!pre || (dma && !narrow && !split), "uh_conv3x3_wgrad_pre: needs the bf16 LDS-DMA kernel (64-aligned channels, tensors below 2 GiB); ask uh_conv3x3_pre_ok first");
     for (int k = 0; c.defer && k < 8; ++k) c.defer[k] = 0;
     if (p.kernel != WG_GENERIC && (c.ws_bytes < wgrad_slab_bytes(p) || !c.ws)) {
         uh_set_error("uh_conv3x3_wgrad: workspace %zu < %zu bytes", c.ws_bytes, wgrad_slab_bytes(p));
@@ -3640,8 +3402,7 @@ static int conv3x3_wgrad_dispatch(const WgradCall& c) {
         // db, xb: byte extents of the (sliced) source views as seen from their base pointers (below 2 GiB: wgrad_plan)
         if constexpr (ES == 2)
             wgrad_v2_launch<T>(p, c.st, dy, c.lddy, x0, c.C0, c.ld0, x1, c.C1, c.ld1, slabs, c.Cout, c.B, c.H, c.W, p.tilesX, p.tilesY, p.nsplit,
-                               (unsigned)(px * c.lddy * 2), (unsigned)(px * (c.ld0 > c.ld1 ? c.ld0 : c.ld1) * 2), C0v, C1v, Coutv, c.pre_scale,
-                               c.pre_shift);
+                               (unsigned)(px * c.lddy * 2), (unsigned)(px * (c.ld0 > c.ld1 ? c.ld0 : c.ld1) * 2), C0v, C1v, Coutv);
         UH_CHECK_LAUNCH("conv3x3_wgrad_mfma_v2");
         break;
     case WG_MFMA:
@@ -3716,21 +3477,6 @@ extern "C" int uh_slab_reduce_batched(const int64_t* table, int nrows, int64_t t
     hipLaunchKernelGGL(slab_reduce_batched_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, table, nrows);
     UH_CHECK_LAUNCH("slab_reduce_batched_kernel");
     return UH_OK;
-}
-
-// Backward-weights of a layer whose forward was uh_conv3x3_fwd_pre: x0 is the RAW output of the previous conv and the layer's
-// real input max(x0 * pre_scale + pre_shift, 0) is rebuilt by the loader (it was never stored).  Same result, bit for bit, as
-// uh_conv3x3_wgrad on the stored activation.  Workspace: uh_conv3x3_wgrad_ws_bytes.
-extern "C" int uh_conv3x3_wgrad_pre(const void* dy, int lddy, const void* x0, int C0, int ld0, const float* pre_scale,
-                                    const float* pre_shift, float* dw_krsc, int Cout, void* ws, size_t ws_bytes, int B, int H,
-                                    int W, int dt, uh_stream stream) {
-    UH_REQUIRE(pre_scale && pre_shift, "uh_conv3x3_wgrad_pre: null pointer");
-    WgradCall c;
-    c.dy = dy; c.lddy = lddy; c.x0 = x0; c.C0 = C0; c.ld0 = ld0; c.dw = dw_krsc; c.Cout = Cout; c.ws = ws; c.ws_bytes = ws_bytes;
-    c.B = B; c.H = H; c.W = W; c.st = (hipStream_t)stream; c.pre_scale = pre_scale; c.pre_shift = pre_shift;
-    if (const int rc = conv_check("uh_conv3x3_wgrad_pre", c, c.dy && c.dw, c.lddy, dt, CK_BF16_ONLY)) return rc;
-    UH_REQUIRE(C0 % 64 == 0 && Cout % 64 == 0, "uh_conv3x3_wgrad_pre: channel counts must be multiples of 64");
-    return conv3x3_wgrad_dispatch<bf16_t>(c);
 }
 
 // ---- the stem with a recomputed output (kernels: stem_mfma.hip): 1 -> 64 channels, bf16, w = KRSC pack [64][9][1]

@@ -483,20 +483,6 @@ def conv3x3_wgrad(dy: torch.Tensor, x0: torch.Tensor, x1: Optional[torch.Tensor]
     return False
 
 
-def conv3x3_wgrad_pre(dy: torch.Tensor, x0_raw: torch.Tensor, pre_coef: torch.Tensor, out_krsc: torch.Tensor):
-    """Backward-weights of a layer whose input is max(x0_raw * scale + shift, 0) (BatchNorm + ReLU of the producer, applied by
-    the loader; pre_coef = [scale | shift | ...] of C0 entries each)."""
-    B, H, W, Cout = dy.shape
-    C0 = x0_raw.shape[3]
-    dt = _dt(dy)
-    nbytes = LIB.query("uh_conv3x3_wgrad_ws_bytes", B, H, W, C0, Cout, dt)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
-    with _Timed("conv3x3_wgrad_mfma", 2.0 * B * H * W * Cout * 9 * C0):
-        LIB.call("uh_conv3x3_wgrad_pre", dy.data_ptr(), pixel_ld(dy), x0_raw.data_ptr(), C0, pixel_ld(x0_raw),
-                 pre_coef.data_ptr(), pre_coef[C0:].data_ptr(), out_krsc.data_ptr(), Cout, ws.data_ptr(), nbytes, B, H, W, dt,
-                 _stream())
-
-
 def bench_double_conv(B: int, H: int, W: int, Cin: int, Cout: int, dtype: torch.dtype, iters: int = 20):
     """Time the conv kernels of one DoubleConv(Cin -> Cout -> Cout) in isolation: preallocated buffers, the C ABI
     called back to back (`iters` launches between two HIP events on the launch stream, so the figure is kernel
@@ -696,26 +682,6 @@ def head_tail_ok(x0: torch.Tensor, Cout: int, head_weight: torch.Tensor) -> bool
                 LIB.query("uh_bn_relu_head_ok", Cout, head_weight.shape[0], _dt(x0)))
 
 
-# BatchNorm + ReLU BETWEEN the two convs of a DoubleConv applied by the second conv's loaders (uh_conv3x3_fwd_pre /
-# uh_conv3x3_wgrad_pre): the first layer's node is asked to `defer` its activation (it returns its raw conv output + the
-# BatchNorm coefficients), the second takes them as `pre_coef`; the activation is never stored.  bf16 training, 64-aligned
-# layers of <= 512 mid channels; bit-identical to the stored-activation path (tests/test_gpu_pre_fusion.py).
-# OFF by default -- measured (round 3, one MI355X, config 2, A/B inside one gpurun call): the nine uh_bn_relu_apply launches it
-# removes cost 0.37 ms / step and 2.0 GB of traffic; rebuilding the activation in LDS costs the nine forward convs +0.15 ms and
-# the nine backward-weights convs +1.0 ms (two workgroups own all of LDS there, so the coefficients travel by ds_bpermute,
-# and the rewrite runs once per 8x16 tile whose halo is 1.4x its pixels): 798 -> 735 images/s.  UH_FUSE_PRE=1 turns it on.
-FUSE_PRE = os.environ.get("UH_FUSE_PRE", "0") == "1"
-
-
-def pre_fuse_ok(x0: torch.Tensor, mid: int, Cout: int) -> bool:
-    """May the (BatchNorm -> ReLU) between a DoubleConv's convs be applied by the second conv's loader?  x0: the block's
-    NHWC input (gives batch, extent, dtype); mid / Cout: channels of the activation in question and of the second conv."""
-    if not FUSE_PRE or x0.dtype != torch.bfloat16:
-        return False
-    B, H, W, _ = x0.shape
-    return bool(LIB.query("uh_conv3x3_pre_ok", B, H, W, mid, Cout, mid, Cout, UH_BF16))
-
-
 # ---- BatchNorm-backward sums formed by the NEXT conv's backward-data (SURVEY.md section 7 step 7).  Inside a DoubleConv the
 # gradient of the activation between the two convs is produced by the second conv's backward-data and read back at once by
 # uh_bn_relu_bwd_reduce (that tensor + the first conv's raw output).  uh_conv3x3_dgrad_bnsum forms the two per-channel sums in the
@@ -747,11 +713,7 @@ class ConvBnOpts(NamedTuple):
     [ncls,Cout,1,1], head_b; unet_parts.py:103) and z is never written; TAIL_UP (up_size = (Ho, Wo)) -> returns the bilinear
     x2 up-sampling of z zero-padded to Ho x Wo (unet_parts.py:70,80,85-88: z's only reader) and z is never written.
     `bnsum_pub` / `bnsum_use` (BnSumLink): this layer is the first / the second conv of a DoubleConv whose
-    BatchNorm-backward sums may be formed by the second conv's backward-data.
-    `defer` (training, no tail): the BatchNorm + ReLU of THIS layer is left to its consumer -- the node returns (y, coef): the raw
-    conv output standing in for the activation (its gradient is the activation's gradient) and the [scale | shift | mean
-    | rstd] coefficients.  `pre_coef`: x0 is such a raw output; its BatchNorm + ReLU is applied by this layer's conv
-    loaders (forward and backward-weights), the activation is never stored.  `c0_true`: see ConvBnReluNarrowFn."""
+    BatchNorm-backward sums may be formed by the second conv's backward-data.  `c0_true`: see ConvBnReluNarrowFn."""
     running_mean: Optional[torch.Tensor] = None
     running_var: Optional[torch.Tensor] = None
     num_batches_tracked: Optional[torch.Tensor] = None
@@ -760,8 +722,6 @@ class ConvBnOpts(NamedTuple):
     eps: float = BN_EPS_DEFAULT
     tail: int = TAIL_NONE
     up_size: Optional[Tuple[int, int]] = None
-    defer: bool = False
-    pre_coef: Optional[torch.Tensor] = None
     bnsum_pub: Optional[BnSumLink] = None
     bnsum_use: Optional[BnSumLink] = None
     c0_true: Optional[int] = None
@@ -800,16 +760,12 @@ class ConvBnReluFn(Function):
         _require_gpu(x0, "activation")
         x0 = dense_nhwc(x0)
         x1 = None if x1 is None else dense_nhwc(x1)
-        training, tail, defer, pre_coef = opts.training, opts.tail, opts.defer, opts.pre_coef
+        training, tail = opts.training, opts.tail
         B, H, W, C0 = x0.shape
         C1 = 0 if x1 is None else x1.shape[3]
         Cout, Cin = weight.shape[0], weight.shape[1]
         if Cin != C0 + C1:
             raise RuntimeError(f"conv expects {Cin} input channels, got {C0}+{C1}")
-        if pre_coef is not None and (x1 is not None or not training or pre_coef.numel() != 4 * C0):
-            raise RuntimeError("ConvBnReluFn: a deferred BatchNorm+ReLU input needs a single-source training-mode layer")
-        if defer and (not training or tail != TAIL_NONE):
-            raise RuntimeError("ConvBnReluFn: defer is a training-mode option of layers without a fused tail")
         ctx.training = training
         if not training:
             if tail != TAIL_NONE:
@@ -826,15 +782,7 @@ class ConvBnReluFn(Function):
         ctx.cdt, ctx.frag_d = cdt, frag_d
         dev = x0.device
         n = B * H * W
-        if pre_coef is None:
-            y, stats, nslab = conv3x3_fwd(x0, x1, wf, Cout, True, cdt, frag_f)
-        else:
-            y = torch.empty((B, H, W, Cout), dtype=x0.dtype, device=dev)
-            nslab = LIB.query("uh_conv3x3_stat_slabs", B, H, W, C0, Cout, cdt)
-            stats = torch.empty(nslab * (2 * Cout + 2), dtype=torch.float32, device=dev)
-            with _Timed("conv3x3_fwd_mfma", 2.0 * B * H * W * Cout * 9 * C0):
-                LIB.call("uh_conv3x3_fwd_pre", x0.data_ptr(), C0, pixel_ld(x0), pre_coef.data_ptr(), pre_coef[C0:].data_ptr(),
-                         wf.data_ptr(), y.data_ptr(), Cout, Cout, stats.data_ptr(), B, H, W, conv_flags(cdt, frag_f), _stream())
+        y, stats, nslab = conv3x3_fwd(x0, x1, wf, Cout, True, cdt, frag_f)
         coef, n_total = _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, opts)
         scale, shift, mean, rstd = coef_views(coef)
         ctx.bn_params = (gamma, beta)
@@ -842,22 +790,17 @@ class ConvBnReluFn(Function):
         ctx.n_total = n_total
         ctx.sync_bn = SYNC_BN                    # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
         ctx.tail = tail
-        ctx.pre = pre_coef is not None
         ctx.bnsum_pub = ctx.bnsum_use = None
         if FUSE_BNSUM and x0.dtype == torch.bfloat16 and cdt == UH_BF16:
             bnsum_pub, bnsum_use = opts.bnsum_pub, opts.bnsum_use
-            if bnsum_pub is not None and tail == TAIL_NONE and not defer:
+            if bnsum_pub is not None and tail == TAIL_NONE:
                 bnsum_pub.y, bnsum_pub.coef = y, coef
                 bnsum_pub.partials = bnsum_pub.dz = None      # (left over when a previous backward never reached this layer)
                 ctx.bnsum_pub = bnsum_pub
-            if bnsum_use is not None and bnsum_use.y is not None and x1 is None and pre_coef is None:
+            if bnsum_use is not None and bnsum_use.y is not None and x1 is None:
                 ctx.bnsum_use = bnsum_use
-        # (pre_coef rides in the saved-tensor slot of the absent second source)
-        saved = [x0, x1 if pre_coef is None else pre_coef, y, coef, wd, weight]
-        if defer:
-            ctx.mark_non_differentiable(coef)
-            out = (y, coef)
-        elif tail == TAIL_HEAD:
+        saved = [x0, x1, y, coef, wd, weight]
+        if tail == TAIL_HEAD:
             ncls = head_w.shape[0]
             hw2 = head_w.reshape(ncls, Cout).contiguous().float()
             hb2 = head_b.contiguous().float()
@@ -897,7 +840,6 @@ class ConvBnReluFn(Function):
         tail = ctx.tail
         x0, x1, y, coef, wd, weight, *hw2 = ctx.saved_tensors          # (hw2: the head tail's fp32 [ncls, Cout] filter)
         B, H, W, C0, C1, Cout = ctx.dims
-        pre_coef, x1 = (x1, None) if ctx.pre else (None, x1)
         Cin = C0 + C1
         n = B * H * W
         dev = y.device
@@ -1000,13 +942,7 @@ class ConvBnReluFn(Function):
             dx1 = dx[..., C0:] if (x1 is not None and need["x1"]) else None
         # weight gradient: straight into the parameter's layout when that IS KRSC (channels_last weights)
         dweight = side_done = None
-
-        def run_wgrad(out_, defer_cb=None):
-            if pre_coef is None:
-                return conv3x3_wgrad(dy, x0, x1, out_, ctx.cdt == UH_F32X3, defer_cb)
-            conv3x3_wgrad_pre(dy, x0, pre_coef, out_)
-            return False
-
+        split = ctx.cdt == UH_F32X3
         if need["weight"]:
             dweight, cb_w = _grad_buffer(weight)
             if cb_w is not None and WGRAD_STREAM is not None and _is_krsc_dense(weight):
@@ -1015,21 +951,21 @@ class ConvBnReluFn(Function):
                 ev.record()                         # dy (and this layer's backward-data) are enqueued before this point
                 side.wait_event(ev)
                 with torch.cuda.stream(side):
-                    run_wgrad(dweight)
+                    conv3x3_wgrad(dy, x0, x1, dweight, split)
                     side_done = torch.cuda.Event()
                     side_done.record()              # the gradient all-reduce of this parameter's bucket waits for THIS
-                for t_ in (dy, x0, x1, pre_coef):
+                for t_ in (dy, x0, x1):
                     if t_ is not None:
                         t_.record_stream(side)      # the caching allocator must not recycle them under the side stream
             elif _is_krsc_dense(weight):
                 # (straight into the optimizer's flat buffer: the closing reduction may wait for the batched launch, and the
                 # "gradient ready" callback with it)
-                if run_wgrad(dweight, cb_w):
+                if conv3x3_wgrad(dy, x0, x1, dweight, split, cb_w):
                     cb_w = None
                     dweight = None
             else:
                 dwk = torch.empty(Cout * 9 * Cin, dtype=torch.float32, device=dev)
-                run_wgrad(dwk)
+                conv3x3_wgrad(dy, x0, x1, dwk, split)
                 _unpack_dw3x3(dwk, dweight)
             if cb_w is not None:
                 cb_w(side_done)

@@ -54,7 +54,7 @@ def _finish_tail(z, tail):
 
 
 def _conv_bn_relu(x0, x1, conv: nn.Conv2d, bn: nn.BatchNorm2d, training: bool, keep_padded: bool = False,
-                  x0_channels: int = None, tail=None, defer: bool = False, pre_coef=None, bnsum_pub=None, bnsum_use=None):
+                  x0_channels: int = None, tail=None, bnsum_pub=None, bnsum_use=None):
     """One (conv3x3 -> BatchNorm -> ReLU) layer, plus its consumer `tail` (see _finish_tail) -- fused into the BatchNorm
     kernels where csrc/bn_fused.hip covers the shape (training, 64-aligned layers), separate kernels otherwise.
     Layers whose channel counts are not multiples of 64 (the small-width UNet_S / UNet_T of unet_model.py:52-126) are computed as the next larger 64-aligned layer with zero filters / unit
@@ -66,7 +66,7 @@ def _conv_bn_relu(x0, x1, conv: nn.Conv2d, bn: nn.BatchNorm2d, training: bool, k
     `x0_channels`: x0 is already such a padded tensor and only its first x0_channels channels are real.
     `keep_padded`: return the padded tensor (DoubleConv hands it to its second conv without a copy)."""
     momentum = 0.1 if bn.momentum is None else bn.momentum
-    opts = ops.ConvBnOpts(bn.running_mean, bn.running_var, bn.num_batches_tracked, training, momentum, bn.eps, pre_coef=pre_coef)
+    opts = ops.ConvBnOpts(bn.running_mean, bn.running_var, bn.num_batches_tracked, training, momentum, bn.eps)
     w = conv.weight
     Cout, Cin = w.shape[0], w.shape[1]
     C0 = x0_channels if x0_channels is not None else x0.shape[-1]
@@ -76,13 +76,11 @@ def _conv_bn_relu(x0, x1, conv: nn.Conv2d, bn: nn.BatchNorm2d, training: bool, k
     Cp1 = _rup(C1) if C1 else 0
     Cop = _rup(Cout)
     if Cp0 == C0 and Cp1 == C1 and Cop == Cout and x0_channels is None:
-        if stem and training and tail is None and not defer and pre_coef is None and ops.stem_recompute_ok(x0, Cin, Cout):
+        if stem and training and tail is None and ops.stem_recompute_ok(x0, Cin, Cout):
             # the network's first layer: its conv output is recomputed by every consumer instead of stored
             return ops.StemConvBnReluFn.apply(x0, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                               momentum, bn.eps)
         args = (x0, x1, w, bn.weight, bn.bias)
-        if defer:      # (the caller has checked ops.pre_fuse_ok: this layer's BatchNorm + ReLU is applied by its consumer)
-            return ops.ConvBnReluFn.apply(*args, None, None, opts._replace(defer=True, pre_coef=None))
         if training:
             opts = opts._replace(bnsum_pub=bnsum_pub, bnsum_use=bnsum_use)      # (ops.BnSumLink: see DoubleConv.nhwc)
             if tail == "pool" and ops.pool_tail_ok(x0, Cout):
@@ -92,8 +90,6 @@ def _conv_bn_relu(x0, x1, conv: nn.Conv2d, bn: nn.BatchNorm2d, training: bool, k
             if _is_up(tail) and ops.up_tail_ok(x0, Cout, tail[1], tail[2]):
                 return ops.ConvBnReluFn.apply(*args, None, None, opts._replace(tail=ops.TAIL_UP, up_size=(tail[1], tail[2])))
         return _finish_tail(ops.ConvBnReluFn.apply(*args, None, None, opts), tail)
-    if defer or pre_coef is not None:
-        raise RuntimeError("a deferred BatchNorm+ReLU needs 64-aligned layers (ops.pre_fuse_ok)")
     if ops.NARROW_IO and x0_channels is None:
         # tensors keep their real channel count in HBM, only the arithmetic is padded (ops.ConvBnReluNarrowFn); the
         # 1- / 3-channel image is widened to one 16-byte piece so that it can be fetched like any other activation
@@ -146,14 +142,6 @@ class DoubleConv(nn.Module):
         (returns its logits)."""
         seq = self.double_conv
         mid = seq[0].weight.shape[0]
-        w1, w2 = seq[0].weight, seq[3].weight
-        cin1 = w1.shape[1]
-        aligned1 = (cin1 <= 4 and x1 is None and mid == 64) or (x0.shape[-1] % CPAD == 0 and (x1 is None or x1.shape[-1] % CPAD == 0))
-        if self.training and aligned1 and mid % CPAD == 0 and w2.shape[0] % CPAD == 0 and ops.pre_fuse_ok(x0, mid, w2.shape[0]):
-            # the activation between the two convs never exists: the second conv's loaders apply the first layer's
-            # BatchNorm + ReLU to its raw output on the way to the MFMAs (SURVEY.md section 7 step 6)
-            y1, coef1 = _conv_bn_relu(x0, x1, seq[0], seq[1], True, defer=True)
-            return _conv_bn_relu(y1, None, seq[3], seq[4], True, tail=tail, pre_coef=coef1)
         # the first layer's BatchNorm-backward sums are formed by the second conv's backward-data where the shapes allow
         # (ops.BnSumLink; bf16 training, 64-aligned layers -- the link stays unused everywhere else)
         link = ops.BnSumLink() if (self.training and ops.FUSE_BNSUM) else None
