@@ -62,10 +62,6 @@ def recording(rows):
             LIB.call = had
 
 
-def _reset(ops):
-    ops.WGRAD_STREAM = ops.WEIGHT_PACK = ops.SYNC_BN = ops.SYNC_BN_BATCH = ops.SLAB_BATCH = None
-
-
 def _batch(B, C, H, W, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.rand(B, C, H, W, generator=g), torch.randint(0, 3, (B, H, W), generator=g)
@@ -149,11 +145,8 @@ def _convt_case(H, W, mode):
     model = unet_amd.UNet(3, 2, bilinear=False)
     g = torch.Generator().manual_seed(12)
     x, cot = torch.randn(2, 3, H, W, generator=g), torch.randn(2, 2, H, W, generator=g)
-    before, ops.FP32_MODE = ops.FP32_MODE, mode
-    try:
+    with ops.step_state(fp32_mode=mode):
         return _plain_case(model, x, cot, False)
-    finally:
-        ops.FP32_MODE = before
 
 
 def case_b(H, W):
@@ -223,12 +216,10 @@ def run_case(name, extent=EXTENT):
     """-> (rows, {result name: sha256})"""
     from unet_amd import ops
     rows = []
-    _reset(ops)
-    try:
-        with recording(rows):
-            res = CASES[name](*extent)
-    finally:
-        _reset(ops)
+    assert ops.STEP == ops.StepState(), "a case must start from the default step state: nothing may be left installed"
+    with recording(rows):
+        res = CASES[name](*extent)
+    assert ops.STEP == ops.StepState(), f"case {name} left a step state installed"
     return rows, {k: digest(v) for k, v in sorted(res.items()) if v is not None}
 
 

@@ -296,23 +296,41 @@ def test_parameter_without_gradient_is_skipped_like_torch_optim():
         assert err <= 2e-3, f"{k}: {err:.2e} from stock RMSprop after three steps (one step moves an element by up to 1e-2)"
 
 
-def test_wgrad_stream_choice_is_per_stepper():
+def _record_step_states(monkeypatch):
+    """-> the list that receives ops.STEP as each train_step of the test begins (what the step runs with)."""
+    import unet_amd.train
+    from unet_amd import ops
+    seen, real = [], unet_amd.train.train_step
+
+    def train_step(*args, **kw):
+        seen.append(ops.STEP)
+        return real(*args, **kw)
+
+    monkeypatch.setattr(unet_amd.train, "train_step", train_step)
+    return seen
+
+
+def test_wgrad_stream_choice_is_per_stepper(monkeypatch):
     import unet_amd
     from unet_amd import ops
     dev = torch.device("cuda:0")
+    seen = _record_step_states(monkeypatch)
     im, mk = unet_amd.ellipse_batch(2, 64, seed=6)
     a = unet_amd.TrainStepper(unet_amd.UNet_T(1, 1, bilinear=True).to(dev), amp=False, wgrad_stream=True)
     b = unet_amd.TrainStepper(unet_amd.UNet_T(1, 1, bilinear=True).to(dev), amp=False, wgrad_stream=False)
     a.step(im.to(dev), mk.to(dev))
-    assert ops.WGRAD_STREAM is a.wgrad_stream and a.wgrad_stream is not None
+    assert len(seen) == 1 and seen[-1].wgrad_stream is a.wgrad_stream and a.wgrad_stream is not None
+    assert ops.STEP == ops.StepState()
     b.step(im.to(dev), mk.to(dev))
-    assert ops.WGRAD_STREAM is None
+    assert len(seen) == 2 and seen[-1].wgrad_stream is None
+    assert ops.STEP == ops.StepState()
     a.step(im.to(dev), mk.to(dev))
-    assert ops.WGRAD_STREAM is a.wgrad_stream           # constructing / stepping b did not take a's side stream away
+    assert len(seen) == 3 and seen[-1].wgrad_stream is a.wgrad_stream           # constructing / stepping b did not take a's side stream away
+    assert ops.STEP == ops.StepState()
     torch.cuda.synchronize()
 
 
-def test_side_stream_is_chosen_per_step_by_default():
+def test_side_stream_is_chosen_per_step_by_default(monkeypatch):
     """TrainStepper() without a wgrad_stream argument: backward-weights goes to the side stream for bf16 steps of at least 2^20 pixels
     per process (where it measured +1.5 % at batch 8 and +2.2 % at batch 4) and stays on the launch stream for small or fp32
     steps (exact fp32 lost 3 %, batch 2 is host-bound); the step is the same step either way."""
@@ -331,14 +349,50 @@ def test_side_stream_is_chosen_per_step_by_default():
     assert unet_amd.TrainStepper(unet_amd.UNet_T(1, 1, bilinear=True).to(dev), amp=True, wgrad_stream=False)._side_for(big) is None
     forced = unet_amd.TrainStepper(unet_amd.UNet_T(1, 1, bilinear=True).to(dev), amp=True, wgrad_stream=True)
     assert forced._side_for(small) is forced.wgrad_stream
-    # a step on each side of the threshold leaves the matching stream installed, and both give finite losses
+    # a step on each side of the threshold runs with the matching stream installed, and both give finite losses
+    seen = _record_step_states(monkeypatch)
     im, mk = unet_amd.ellipse_batch(2, 64, seed=6)
     t = st.step(im.to(dev), mk.to(dev))
-    assert ops.WGRAD_STREAM is None and math.isfinite(float(t["loss"]))
+    assert len(seen) == 1 and seen[-1].wgrad_stream is None and math.isfinite(float(t["loss"]))
+    assert ops.STEP == ops.StepState()
     im, mk = unet_amd.ellipse_batch(4, 512, seed=7)
     t = st.step(im.to(dev), mk.to(dev))
-    assert ops.WGRAD_STREAM is st.wgrad_stream and math.isfinite(float(t["loss"]))
+    assert len(seen) == 2 and seen[-1].wgrad_stream is st.wgrad_stream and math.isfinite(float(t["loss"]))
+    assert ops.STEP == ops.StepState()
     torch.cuda.synchronize()
+
+
+def test_a_step_that_raises_leaves_no_step_state_installed():
+    """train_step refuses a batch with the wrong channel count (a Python AssertionError in front of the forward pass): the side
+    stream, the filter pack, the slab batch and the bf16x3 mode the stepper had installed for it are gone again."""
+    import unet_amd
+    from unet_amd import ops
+    dev = torch.device("cuda:0")
+    st = unet_amd.TrainStepper(unet_amd.UNet_T(1, 1, bilinear=True).to(dev), amp=False, wgrad_stream=True, fp32_mode="bf16x3")
+    with pytest.raises(AssertionError):
+        st.step(torch.zeros(2, 2, 64, 64, device=dev), torch.zeros(2, 64, 64, dtype=torch.long, device=dev))
+    assert ops.STEP == ops.StepState()
+    torch.cuda.synchronize()
+    st.close()
+
+
+def test_graphed_stepper_leaves_no_step_state_installed():
+    """Capture (warm-up steps + the captured one) and replay both end with the default record in ops.STEP."""
+    import unet_amd
+    from unet_amd import ops
+    dev = torch.device("cuda:0")
+    torch.manual_seed(5)
+    st = unet_amd.GraphedTrainStepper(unet_amd.UNet_T(1, 1, bilinear=True).to(dev))
+    im, mk = unet_amd.ellipse_batch(2, 64, seed=6)
+    t = st.step(im.to(dev), mk.to(dev))                        # captures, then replays once
+    assert st._graph is not None and ops.STEP == ops.StepState()
+    assert math.isfinite(float(t["loss"]))
+    graph = st._graph
+    t = st.step(im.to(dev), mk.to(dev))                        # replay only
+    assert st._graph is graph and ops.STEP == ops.StepState()
+    assert math.isfinite(float(t["loss"]))
+    torch.cuda.synchronize()
+    st.close()
 
 
 def _stale_pattern_worker(rank, world, port, q, mode):
@@ -458,6 +512,7 @@ def _rccl_one_rank_syncbn_worker(rank, world, port, q, own_group):
         torch.cuda.set_device(dev)
         dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
         import unet_amd
+        from unet_amd import ops
         torch.manual_seed(0)
         model = unet_amd.UNet_S(1, 1, bilinear=True).to(memory_format=torch.channels_last).to(dev)
         stepper = unet_amd.TrainStepper(model, lr=1e-4, amp=False, wgrad_stream=True, sync_bn=True)
@@ -465,10 +520,11 @@ def _rccl_one_rank_syncbn_worker(rank, world, port, q, own_group):
         im, mk = unet_amd.ellipse_batch(4, 96, seed=3)
         for _ in range(3):
             t = stepper.step(im.to(dev), mk.to(dev))           # no global_batch: the batch-size all-reduce runs too
+            assert ops.STEP.sync_bn is None                    # the group is installed for the step only
         torch.cuda.synchronize()
         out = (rank, "ok", stepper.optimizer.flat_p.cpu().numpy(), float(t["loss"].detach()))
         stepper.close()                                        # destroys the BatchNorm communicator when there is one
-        assert stepper.bn_group is None
+        assert stepper.bn_group is None and ops.STEP.sync_bn is None
         dist.barrier()                                         # the gradient communicator still works afterwards
         q.put(out)
         dist.destroy_process_group()

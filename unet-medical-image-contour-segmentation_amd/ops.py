@@ -136,9 +136,44 @@ def _empty_like_param(p: torch.Tensor) -> torch.Tensor:
     return torch.empty_strided(p.shape, p.stride(), dtype=torch.float32, device=p.device)
 
 
-# Optional second HIP stream for backward-weights (set by TrainStepper): wgrad only feeds the optimizer, so it can run
-# beside the backward-data conv and the HBM-bound BatchNorm-backward kernels of the layers that follow.
-WGRAD_STREAM = None
+class StepState(NamedTuple):
+    """What one training step tells the autograd nodes besides their arguments.  TrainStepper installs a record for the duration
+    of a step (step_state); between steps, and for every call outside a stepper, the defaults hold.
+    `wgrad_stream`: a second HIP stream for backward-weights -- it only feeds the optimizer, so it can run beside the
+    backward-data conv and the HBM-bound BatchNorm-backward kernels of the layers that follow.
+    `sync_bn`: (process group, world size) when BatchNorm statistics are to be those of the GLOBAL batch of a data-parallel job
+    (TrainStepper(sync_bn=True)); None = per-rank statistics (what stock DDP does).  `sync_bn_batch`: (global batch, local
+    batch) of the step under sync_bn; None = equal shards.  `weight_pack`: the ConvWeightPack of the model being trained
+    (ConvBnReluFn packs per layer on a miss).  `slab_batch`: the step's SlabBatch; None = every backward-weights call reduces
+    its own slabs at once.  `fp32_mode`: how fp32 activations are convolved: "exact" = fp32 MFMA (157 TFLOP/s peak, the parity
+    path); "bf16x3" = products on the bf16 matrix pipe with hi/lo splits of both operands (forward / backward-data 3x3 convs
+    of MFMA-aligned layers; ~1e-5 relative, backward-weights stays exact).  TrainStepper(fp32_mode=...) / bench.py --bf16x3."""
+    wgrad_stream: Optional[torch.cuda.Stream] = None
+    sync_bn: Optional[tuple] = None
+    sync_bn_batch: Optional[Tuple[int, int]] = None
+    weight_pack: Optional[ConvWeightPack] = None
+    slab_batch: Optional[SlabBatch] = None
+    fp32_mode: str = "exact"
+
+
+STEP = StepState()
+
+
+@contextlib.contextmanager
+def step_state(**fields):
+    """Install STEP._replace(**fields) for the block; the record that was there on entry is back on leaving it, also after an
+    exception.  Each reader takes its field when its call is enqueued: a graph captured inside the block keeps what was read."""
+    global STEP
+    if fields.get("fp32_mode", "exact") not in ("exact", "bf16x3"):
+        raise ValueError("fp32_mode must be 'exact' or 'bf16x3'")
+    unknown = set(fields) - set(StepState._fields)
+    if unknown:
+        raise TypeError(f"step_state: no such field: {', '.join(sorted(unknown))}")
+    prev, STEP = STEP, STEP._replace(**fields)
+    try:
+        yield
+    finally:
+        STEP = prev
 
 
 # FusedRMSprop registers, per parameter storage, the view of its flat gradient buffer that the backward kernels
@@ -163,15 +198,9 @@ def _is_krsc_dense(w: torch.Tensor) -> bool:
 
 
 # ----------------------------------------------------------------------------- raw op wrappers
-# How fp32 activations are convolved: "exact" = fp32 MFMA (157 TFLOP/s peak, the parity path); "bf16x3" = products on the
-# bf16 matrix pipe with hi/lo splits of both operands (forward / backward-data 3x3 convs of MFMA-aligned layers; ~1e-5
-# relative, backward-weights stays exact).  Set by TrainStepper(fp32_mode=...) / bench.py --bf16x3.
-FP32_MODE = "exact"
-
-
 def conv_dt(x: torch.Tensor, C0: int, C1: int, Cout: int, need_dx: bool) -> int:
     """dtype code for the 3x3 conv calls of one layer (pack + forward + backward-data use the SAME code)."""
-    if x.dtype == torch.float32 and FP32_MODE == "bf16x3":
+    if x.dtype == torch.float32 and STEP.fp32_mode == "bf16x3":
         Cin = C0 + C1
         if Cin > 4 and C0 % 16 == 0 and C1 % 16 == 0 and Cout % 64 == 0 and (not need_dx or Cin % 64 == 0):
             return UH_F32X3
@@ -337,7 +366,7 @@ class ConvWeightPack:
     def lookup(self, weight: torch.Tensor, dtype: torch.dtype, frag_f: bool = False, frag_d: bool = False):
         """-> (w_fwd, w_dgrad) views if the pack holds the CURRENT value of `weight` in `dtype` in the layouts the caller's
         conv calls need (frag_f / frag_d: fragment-major forward / backward-data copy), else None."""
-        if FP32_MODE != "exact" and dtype == torch.float32:
+        if STEP.fp32_mode != "exact" and dtype == torch.float32:
             return None                          # bf16x3 layers pack their own [hi | lo] copies
         i = self.index.get(weight.data_ptr())
         if i is None or dtype != self.dtype or self.epoch != WEIGHT_EPOCH or self.versions[i] != weight._version \
@@ -346,10 +375,6 @@ class ConvWeightPack:
         n = weight.shape[0] * 9 * weight.shape[1]
         o = self.offsets[i]
         return self.wf[o:o + n], self.wd[o:o + n]
-
-
-# set by TrainStepper (one pack per model being trained); ConvBnReluFn falls back to per-layer packing on a miss
-WEIGHT_PACK: Optional[ConvWeightPack] = None
 
 
 def conv3x3_fwd(x0: torch.Tensor, x1: Optional[torch.Tensor], w_packed: torch.Tensor, Cout: int,
@@ -436,9 +461,7 @@ class SlabBatch:
                 cb(None)
 
 
-# set by TrainStepper for the duration of a step; None = every backward-weights call reduces its own slabs at once
-SLAB_BATCH: Optional[SlabBatch] = None
-# OFF by default -- measured (round 4, one MI355X, config 2, three interleaved rounds, bf16 slabs): 873.1 images/s with the
+# Queue the closing reductions in STEP.slab_batch.  OFF by default -- measured (round 4, one MI355X, config 2, three interleaved rounds, bf16 slabs): 873.1 images/s with the
 # per-layer launches, 872.2 with one batched launch behind the backward pass (B=4: 763.0 / 762.2).  The eighteen launches it
 # removes are bandwidth-bound (37 MB each at 5.5 TB/s), not latency-bound, and a layer's slabs are read back from the Infinity
 # Cache when the reduction runs at once, from HBM when it runs a millisecond later.  UH_DEFER_SLABS=1 turns it on.
@@ -446,24 +469,24 @@ DEFER_SLABS = os.environ.get("UH_DEFER_SLABS", "0") == "1"
 
 
 def flush_slabs():
-    if SLAB_BATCH is not None:
-        SLAB_BATCH.flush()
+    if STEP.slab_batch is not None:
+        STEP.slab_batch.flush()
 
 
 def conv3x3_wgrad(dy: torch.Tensor, x0: torch.Tensor, x1: Optional[torch.Tensor], out_krsc: torch.Tensor,
                   split: bool = False, defer_cb=None) -> bool:
     """dW (fp32 KRSC) of a 3x3 conv.  `defer_cb` (a callable taking one argument): the caller allows the closing reduction to be
-    queued in ops.SLAB_BATCH; the callback then fires when it has run.  -> True when the result (and the callback) were deferred."""
+    queued in STEP.slab_batch; the callback then fires when it has run.  -> True when the result (and the callback) were deferred."""
     B, H, W, Cout = dy.shape
     C0 = x0.shape[3]
     C1 = 0 if x1 is None else x1.shape[3]
     dt = _dt(dy)
     nbytes = LIB.query("uh_conv3x3_wgrad_ws_bytes", B, H, W, C0 + C1, Cout, dt)
     if split and dt == UH_F32 and C0 % 64 == 0 and C1 % 64 == 0 and Cout % 64 == 0:
-        dt = UH_F32X3                          # bf16x3 products (ops.FP32_MODE); same workspace as the fp32 plan
+        dt = UH_F32X3                          # bf16x3 products (STEP.fp32_mode); same workspace as the fp32 plan
     name = "conv3x3_wgrad_" + ("mfma" if (C0 % 64 == 0 and C1 % 64 == 0 and Cout % 64 == 0) else
                                 ("stem" if C0 + C1 <= 4 else "generic"))
-    batch = SLAB_BATCH if (defer_cb is not None and DEFER_SLABS and name == "conv3x3_wgrad_mfma") else None
+    batch = STEP.slab_batch if (defer_cb is not None and DEFER_SLABS and name == "conv3x3_wgrad_mfma") else None
     timed = _Timed(name, 2.0 * B * H * W * Cout * 9 * (C0 + C1), ("wgrad", B, H, W, C0 + C1, Cout))
     if batch is not None:
         ws = batch.workspace(out_krsc.data_ptr(), nbytes, dy.device)
@@ -550,13 +573,6 @@ def bench_double_conv(B: int, H: int, W: int, Cin: int, Cout: int, dtype: torch.
 
 
 # ----------------------------------------------------------------------------- conv + BN + ReLU
-# (process group, world size) when BatchNorm statistics are to be those of the GLOBAL batch of a data-parallel job
-# (TrainStepper(sync_bn=True)); None = per-rank statistics (what stock DDP does).
-SYNC_BN = None
-# (global batch, local batch) of the current step when SYNC_BN is on; None = equal shards
-SYNC_BN_BATCH = None
-
-
 def coef_views(coef: torch.Tensor):
     """-> (scale, shift, mean, rstd): the four per-channel views of a [scale | shift | mean | rstd] buffer."""
     C = coef.numel() // 4
@@ -568,7 +584,7 @@ def _sync_bn_forward(coef, m2, n_local, Cout, g32, b32, o, nbt_ptr):
     layer, then the same uh_bn_finalize over `world` rows (Chan merge in double), which also updates the running
     statistics with the global unbiased variance.  Returns the global pixel count."""
     import torch.distributed as dist
-    group, world = SYNC_BN
+    group, world = STEP.sync_bn
     dev = coef.device
     mean = coef_views(coef)[2]
     row = torch.cat([mean, m2, torch.full((1,), float(n_local), dtype=torch.float32, device=dev)])
@@ -580,7 +596,7 @@ def _sync_bn_forward(coef, m2, n_local, Cout, g32, b32, o, nbt_ptr):
     stats[world * 2 * Cout:world * 2 * Cout + world].copy_(g2[:, 2 * Cout])
     # the global pixel count: this rank's count scaled by global batch / local batch (TrainStepper all-reduces the batch
     # sizes once per step, so ragged shards -- the last batch of an epoch -- get the right variance denominator)
-    gb, lb = SYNC_BN_BATCH if SYNC_BN_BATCH is not None else (world, 1)
+    gb, lb = STEP.sync_bn_batch if STEP.sync_bn_batch is not None else (world, 1)
     n_total = int(n_local) * gb // lb
     LIB.call("uh_bn_finalize", stats.data_ptr(), world, Cout, n_total, g32.data_ptr(), b32.data_ptr(), _p(o.running_mean),
              _p(o.running_var), nbt_ptr, float(o.momentum), float(o.eps), *[v.data_ptr() for v in coef_views(coef)], None, _stream())
@@ -604,10 +620,10 @@ def _bn_train_coefficients(stats, nslab, Cout, n, gamma, beta, o, ldc: Optional[
     nbt_ptr = nbt.data_ptr() if fused_nbt else None
     rows = ("uh_bn_finalize", stats.data_ptr(), nslab) if ldc is None else ("uh_bn_finalize_ld", stats.data_ptr(), nslab, ldc)
     # (SyncBN: this call only forms the local mean / M2; the merge below updates the running statistics)
-    m2 = None if SYNC_BN is None else torch.empty(Cout, dtype=torch.float32, device=dev)
-    running = (_p(o.running_mean), _p(o.running_var), nbt_ptr) if SYNC_BN is None else (None, None, None)
+    m2 = None if STEP.sync_bn is None else torch.empty(Cout, dtype=torch.float32, device=dev)
+    running = (_p(o.running_mean), _p(o.running_var), nbt_ptr) if STEP.sync_bn is None else (None, None, None)
     LIB.call(*rows, Cout, n, g32.data_ptr(), b32.data_ptr(), *running, float(o.momentum), float(o.eps), *out, _p(m2), _stream())
-    n_total = n if SYNC_BN is None else _sync_bn_forward(coef, m2, n, Cout, g32, b32, o, nbt_ptr)
+    n_total = n if STEP.sync_bn is None else _sync_bn_forward(coef, m2, n, Cout, g32, b32, o, nbt_ptr)
     if nbt is not None and not fused_nbt:
         nbt.add_(1)
     return coef, n_total
@@ -777,7 +793,8 @@ class ConvBnReluFn(Function):
         # [B,H,W,Cout] with the transposed filter into dx [B,H,W,Cin])
         frag_f = wfrag_ok(B, H, W, C0, C1, Cout, pixel_ld(x0), pixel_ld_or0(x1), Cout, cdt)
         frag_d = need_dx and wfrag_ok(B, H, W, Cout, 0, Cin, Cout, 0, Cin, cdt)
-        hit = WEIGHT_PACK.lookup(weight, x0.dtype, frag_f, frag_d) if (WEIGHT_PACK is not None and cdt != UH_F32X3) else None
+        pack = STEP.weight_pack
+        hit = pack.lookup(weight, x0.dtype, frag_f, frag_d) if (pack is not None and cdt != UH_F32X3) else None
         wf, wd = hit if hit is not None else pack_w3x3(weight, x0.dtype, need_dx, cdt, frag_f, frag_d)
         ctx.cdt, ctx.frag_d = cdt, frag_d
         dev = x0.device
@@ -788,7 +805,7 @@ class ConvBnReluFn(Function):
         ctx.bn_params = (gamma, beta)
         ctx.dims = (B, H, W, C0, C1, Cout)
         ctx.n_total = n_total
-        ctx.sync_bn = SYNC_BN                    # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
+        ctx.sync_bn = STEP.sync_bn               # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
         ctx.tail = tail
         ctx.bnsum_pub = ctx.bnsum_use = None
         if FUSE_BNSUM and x0.dtype == torch.bfloat16 and cdt == UH_BF16:
@@ -945,8 +962,8 @@ class ConvBnReluFn(Function):
         split = ctx.cdt == UH_F32X3
         if need["weight"]:
             dweight, cb_w = _grad_buffer(weight)
-            if cb_w is not None and WGRAD_STREAM is not None and _is_krsc_dense(weight):
-                side = WGRAD_STREAM
+            side = STEP.wgrad_stream
+            if cb_w is not None and side is not None and _is_krsc_dense(weight):
                 ev = torch.cuda.Event()
                 ev.record()                         # dy (and this layer's backward-data) are enqueued before this point
                 side.wait_event(ev)
@@ -1001,7 +1018,7 @@ class StemConvBnReluFn(Function):
         if weight.shape[1] != Cin or not stem_recompute_ok(x0, Cin, Cout):
             raise RuntimeError("StemConvBnReluFn: bf16 single-channel image into 64 output channels only")
         dev = x0.device
-        hit = WEIGHT_PACK.lookup(weight, x0.dtype, False, False) if WEIGHT_PACK is not None else None
+        hit = STEP.weight_pack.lookup(weight, x0.dtype, False, False) if STEP.weight_pack is not None else None
         wf = hit[0] if hit is not None else pack_w3x3(weight, x0.dtype, False)[0]
         n = B * H * W
         nslab = LIB.query("uh_conv3x3_stat_slabs", B, H, W, Cin, Cout, UH_BF16)
@@ -1018,7 +1035,7 @@ class StemConvBnReluFn(Function):
         ctx.bn_params = (gamma, beta)
         ctx.dims = (B, H, W, Cin, Cout)
         ctx.n_total = n_total
-        ctx.sync_bn = SYNC_BN                    # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
+        ctx.sync_bn = STEP.sync_bn               # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
         return z
 
     @staticmethod
@@ -1177,7 +1194,7 @@ class ConvBnReluNarrowFn(Function):
         ctx.dims = (B, H, W, Cout, c0_true)
         ctx.cdt = cdt
         ctx.n_total = n_total
-        ctx.sync_bn = SYNC_BN                    # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
+        ctx.sync_bn = STEP.sync_bn               # (None = per-rank statistics; a one-rank group under UH_DP_FORCE_SYNC still runs the collectives)
         return z
 
     @staticmethod
@@ -1343,7 +1360,7 @@ class ConvTranspose2x2PadFn(Function):
             mfma = bool(LIB.query("uh_convt2x2_mfma_ok_plan", B, PLAN_IMAGES, h, w, Cin, Cout, Ho, Wo, dt))
         else:
             mfma = bool(LIB.query("uh_convt2x2_mfma_ok", B, h, w, Cin, Cout, Ho, Wo, dt))
-        if mfma and dt == UH_F32 and FP32_MODE == "bf16x3":
+        if mfma and dt == UH_F32 and STEP.fp32_mode == "bf16x3":
             dt = UH_F32X3                    # split products on the bf16 matrix pipe (both operands split in registers)
         wd = None
         if mfma:

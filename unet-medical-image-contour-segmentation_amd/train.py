@@ -258,8 +258,8 @@ class FusedRMSprop:
     def abort_step(self):
         """Drop the gradients of the current backward without applying them (NaN loss, train.py:149-151): the side
         stream and any gradient all-reduce already in flight are drained so that the next step starts clean."""
-        if ops.WGRAD_STREAM is not None:
-            torch.cuda.current_stream().wait_stream(ops.WGRAD_STREAM)
+        if ops.STEP.wgrad_stream is not None:
+            torch.cuda.current_stream().wait_stream(ops.STEP.wgrad_stream)
         if self.sync is not None:
             self.sync.wait()
         self._fresh = [False] * len(self.params)
@@ -317,8 +317,8 @@ class FusedRMSprop:
         if self._closed:
             raise RuntimeError("FusedRMSprop.step() after close() (another FusedRMSprop took the parameters over)")
         ops.flush_slabs()
-        if ops.WGRAD_STREAM is not None:
-            torch.cuda.current_stream().wait_stream(ops.WGRAD_STREAM)     # weight gradients written on the side stream
+        if ops.STEP.wgrad_stream is not None:
+            torch.cuda.current_stream().wait_stream(ops.STEP.wgrad_stream)     # weight gradients written on the side stream
         # A parameter that received no gradient this step is SKIPPED, as torch.optim skips parameters whose .grad is None
         # (an unused or frozen parameter must not drift under weight decay / momentum): its slice of the flat gradient is
         # zeroed -- so that it adds nothing to the clipping norm and a data-parallel peer that did produce a gradient still
@@ -580,7 +580,8 @@ class TrainStepper:
         # +1.1 %, transposed-conv variant +0.8 %, three interleaved rounds each -- while exact fp32 loses 3 % and batch 2
         # (host-bound: two more stream switches per layer) 7-20 % (DESIGN.md "Measured (round 4)").  UH_SIDE_STREAM=0 / 1
         # overrides the automatic choice.
-        # (kept on the instance and installed for the duration of step(): another live stepper keeps its own choice)
+        # (kept on the instance and installed in ops.STEP for the duration of step() only: another live stepper keeps its own
+        # choice, and nothing of this one is left behind between steps or after close())
         self._side_auto = wgrad_stream is None
         env = os.environ.get("UH_SIDE_STREAM")
         if self._side_auto and env in ("0", "1"):
@@ -593,7 +594,7 @@ class TrainStepper:
         self.check_nan = check_nan
         if fp32_mode not in ("exact", "bf16x3"):
             raise ValueError("fp32_mode must be 'exact' or 'bf16x3'")
-        self.fp32_mode = fp32_mode          # how fp32 activations are convolved (ops.FP32_MODE); irrelevant under amp
+        self.fp32_mode = fp32_mode          # how fp32 activations are convolved (ops.StepState.fp32_mode); irrelevant under amp
         self.cc_loss = cc_loss
         self.group = process_group
         self.world = dpmod.world_size(process_group)
@@ -702,41 +703,40 @@ class TrainStepper:
         big = images.is_cuda and images.shape[0] * images.shape[-2] * images.shape[-1] >= self.SIDE_MIN_PIXELS
         return self.wgrad_stream if (self.amp and big) else None
 
-    def step(self, images, true_masks, global_batch: Optional[int] = None):
-        """One optimizer step (train.py:113-159).  `global_batch` (data parallel with sync_bn): the sum of the ranks' batch
-        sizes when the caller knows it (equal shards: world * B) -- otherwise it is all-reduced here, which costs a blocking
-        host read per step."""
-        self._refuse_averaged()
+    @contextlib.contextmanager
+    def _step_state(self, images, sync_bn, global_batch: Optional[int] = None):
+        """Everything the autograd nodes read besides their arguments, installed (ops.step_state) for the step over `images`
+        and gone again behind it, also when the step raises.  `sync_bn`: the (group, world) pair of the step or None.
+        Yields the `world` the loss is normalised by."""
         self.model.train()
         side = self._side_for(images)
-        ops.WGRAD_STREAM = side
-        ops.SYNC_BN = self.sync_bn
-        ops.SYNC_BN_BATCH = None
-        world = self.world
-        if self.sync_bn is not None:
+        world, batch = self.world, None
+        if sync_bn is not None:
             lb = int(images.shape[0])
             gb = int(global_batch) if global_batch is not None else dpmod.global_batch(lb, self.group, images.device)
-            ops.SYNC_BN_BATCH = (gb, lb)
+            batch = (gb, lb)
             world = gb / lb               # ragged shards: the loss is normalised by the GLOBAL pixel count n * gb / lb
-        fp32_mode_before, ops.FP32_MODE = ops.FP32_MODE, self.fp32_mode        # (a per-step setting: restored below, so that one
-        # stepper's bf16x3 products do not leak into whatever runs next in the process)
         # one launch packs every 3x3 filter (bf16/fp32 KRSC + backward-data layout) for this step's forward/backward
         dt = torch.bfloat16 if self.amp else getattr(self.model, "compute_dtype", torch.float32)
         if self._pack is None or self._pack.dtype != dt:
             ws = [m.weight for m in self.model.modules() if isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3)]
             self._pack = ops.ConvWeightPack(ws, dt) if ws and all(w.is_cuda for w in ws) else None
         if self._pack is not None:
-            ops.WEIGHT_PACK = self._pack
             self._pack.refresh()
         self._slabs.reset()
-        ops.SLAB_BATCH = self._slabs if side is None else None
-        try:
+        with ops.step_state(wgrad_stream=side, sync_bn=sync_bn, sync_bn_batch=batch, weight_pack=self._pack,
+                            slab_batch=self._slabs if side is None else None, fp32_mode=self.fp32_mode):
+            yield world
+
+    def step(self, images, true_masks, global_batch: Optional[int] = None):
+        """One optimizer step (train.py:113-159).  `global_batch` (data parallel with sync_bn): the sum of the ranks' batch
+        sizes when the caller knows it (equal shards: world * B) -- otherwise it is all-reduced here, which costs a blocking
+        host read per step."""
+        self._refuse_averaged()
+        with self._step_state(images, self.sync_bn, global_batch) as world:
             return train_step(self.model, self.optimizer, images, true_masks, amp=self.amp,
                               reduce_sums=self.reduce_sums, world=world, check_nan=self.check_nan, cc_loss=self.cc_loss,
                               surface_weight=self.surface_weight, surface_classes=self.surface_classes)
-        finally:
-            ops.SLAB_BATCH = None
-            ops.FP32_MODE = fp32_mode_before
 
 
 class GraphedTrainStepper(TrainStepper):
@@ -764,26 +764,9 @@ class GraphedTrainStepper(TrainStepper):
             raise RuntimeError("GraphedTrainStepper does not capture the surface loss (surface_weight must be 0): use TrainStepper")
 
     def _eager_step(self, images, masks):
-        self.model.train()
-        side = self._side_for(images)
-        ops.WGRAD_STREAM = side
-        ops.SYNC_BN = None
-        fp32_mode_before, ops.FP32_MODE = ops.FP32_MODE, self.fp32_mode
-        dt = torch.bfloat16 if self.amp else getattr(self.model, "compute_dtype", torch.float32)
-        if self._pack is None or self._pack.dtype != dt:
-            ws = [m.weight for m in self.model.modules() if isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3)]
-            self._pack = ops.ConvWeightPack(ws, dt) if ws and all(w.is_cuda for w in ws) else None
-        if self._pack is not None:
-            ops.WEIGHT_PACK = self._pack
-            self._pack.refresh()
-        self._slabs.reset()
-        ops.SLAB_BATCH = self._slabs if side is None else None
-        try:
+        with self._step_state(images, None):         # (single process: per-rank BatchNorm statistics, world = self.world)
             return train_step(self.model, self.optimizer, images, masks, amp=self.amp, reduce_sums=self.reduce_sums,
                               world=self.world, check_nan=False)
-        finally:
-            ops.SLAB_BATCH = None
-            ops.FP32_MODE = fp32_mode_before
 
     def _capture(self, images, masks):
         opt = self.optimizer
