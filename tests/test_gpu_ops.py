@@ -1,6 +1,8 @@
 """Op-level GPU parity (through the C ABI wrappers in ops.py) against fp64 stock-PyTorch CPU maths:
 conv3x3 forward / backward-data / backward-weights over a sweep of shapes that exercise every kernel
-variant (MFMA NB=2/4, stem, generic; two-source inputs; partial tiles; odd sizes)."""
+variant (MFMA NB=2/4, stem, generic; two-source inputs; partial tiles; odd sizes).  The bounds here are fractions of a tensor's
+largest value on Gaussian inputs; test_gpu_exact.py holds each kernel form and backward-weights plan, one asserted case per
+answer of uh_conv3x3_fwd_kernel / uh_conv3x3_wgrad_plan, to the float64 reference bit for bit on integer inputs."""
 import pytest
 import torch
 import torch.nn.functional as F
