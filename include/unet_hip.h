@@ -562,7 +562,34 @@ int uh_surface_loss_grad(const float* logits, const int64_t* mask, int mask_div,
                          int W, double n_mean, float w, const float* gscale, float* dlogits, int rebuild, void* ws,
                          size_t ws_bytes, uh_stream stream);
 
-/* ---- input pipeline, device stage  (utils/data_loading.py:65-132, train.py:113-114) ---------------------------
+/* ---- focal + Tversky loss  (no counterpart in the reference; DESIGN.md section 3 "Focal / Tversky loss"; csrc/focal_loss.hip) ----
+ * The class-weighted replacement of the CE + Dice pair for imbalanced classes.  A head of C classes: ncls = 2..8 is a softmax
+ * head (C = ncls, logits fp32 [npix][ncls], labels mask / mask_div); ncls = 1 is the one-channel head, the two-class form
+ * (C = 2) on the logits (0, z): logits fp32 [npix], labels mask / mask_div (the binary loss's mask_div = 2).  With p = softmax:
+ *   u        = sum_{c != t} p_c                                   (1 - p_t, formed without the cancellation)
+ *   focal    = sum_x w_t u^gamma (-log p_t) / sum_x w_t           (-log p_t = logsumexp - z_t; gamma = 0: u^gamma = 1, also at u = 0)
+ *   TI_c     = (TP_c + eps) / ((1 - alpha - beta) TP_c + alpha P_c + beta T_c + eps),  eps = 1e-6
+ *   tversky  = 1 / K sum_{c in classes} (1 - TI_c);   total = focal + tversky
+ * weights: HOST fp32 [C], each finite and > 0.  classes: HOST int [K], distinct ids in [0, C).  gamma >= 0; alpha, beta >= 0
+ * with alpha + beta > 0.  UH_EINVAL for anything else, for ncls outside 1..8, a null pointer or a workspace that is too small.
+ * uh_focal_tversky_nsums: the length of the sums vector, 2 + 3 C (0 for a bad ncls).
+ * uh_focal_tversky_sums:  sums DEVICE fp32 [2 + 3 C] = { sum w_t u^gamma (-log p_t), sum w_t, TP_c.., P_c.., T_c.. }; after a sum
+ *   over data-parallel ranks they are the global batch's, and value and gradient follow from them.  ws: uh_loss_ws_bytes(npix).
+ * uh_focal_tversky_finish: out DEVICE fp32 [3] = { total, focal, tversky } from the sums, in double.
+ * uh_focal_tversky_grad:   WRITES dlogits (every element) = gscale[0] * d total / d logits (gscale DEVICE or NULL = 1):
+ *   w_t / W s (tau_k - p_k) + p_k (g_k - sum_c p_c g_c), s = gamma u^gamma q r - u^gamma, r = log(q) / u (-1 at u = 0).
+ * No floating-point atomics: a call gives the same bits every time, and a pixel's gradient depends on its own logits and label,
+ * the sums and gscale only.  u^gamma takes multiplications for gamma in {0, 1, 2}, exp2(gamma log2 u) otherwise. */
+int uh_focal_tversky_nsums(int ncls);
+int uh_focal_tversky_sums(const float* logits, const int64_t* mask, int mask_div, int64_t npix, int ncls, const float* weights,
+                          float gamma, float* sums, void* ws, size_t ws_bytes, uh_stream stream);
+int uh_focal_tversky_finish(const float* sums, int ncls, double alpha, double beta, const int* classes, int K, float* out,
+                            uh_stream stream);
+int uh_focal_tversky_grad(const float* logits, const int64_t* mask, int mask_div, int64_t npix, int ncls, const float* weights,
+                          float gamma, double alpha, double beta, const int* classes, int K, const float* sums, const float* gscale,
+                          float* dlogits, uh_stream stream);
+
+/* ---- input pipeline, device stage (utils/data_loading.py:65-132, train.py:113-114) ---------------------------
  * What BasicDataset.__getitem__ does to a DECODED image / mask pair, for a whole batch in one pass:
  *   img_u8   DEVICE uint8 [B][Hin][Win][C] (C = 1..4, what np.asarray(PIL image) holds), or NULL (masks only)
  *   mask_u8  DEVICE uint8 [B][Hin][Win] grey levels (255 contour / 128 background / 0 ghost), or NULL (images only)

@@ -6,6 +6,7 @@ from .utils.dice_score import dice_coeff, multiclass_dice_coeff, dice_loss  # no
 from .utils.boundary_loss import boundary_loss  # noqa: F401
 from .utils.connected_component_loss import connected_component_loss  # noqa: F401
 from .utils.surface_loss import surface_loss, surface_distance_map  # noqa: F401
+from .utils.focal_loss import LossConfig, focal_tversky_loss  # noqa: F401
 from .train import FusedRMSprop, seg_loss, train_step, TrainStepper, GraphedTrainStepper, EmaConfig  # noqa: F401
 from .evaluate import evaluate  # noqa: F401
 from .utils.contour_metrics import contour_metrics, ContourMetrics  # noqa: F401

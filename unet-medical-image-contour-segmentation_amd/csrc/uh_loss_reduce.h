@@ -1,0 +1,54 @@
+// The reduction scheme the loss passes share (loss.hip, focal_loss.hip): per-thread -> wave shuffle -> LDS -> one partial row per
+// block -> one finishing block that sums the rows' columns in double.  No atomics: a shape gives the same bits every time.
+#pragma once
+#include "uh_common.h"
+
+constexpr int LOSS_MAXBLK = 1024;
+constexpr int LOSS_ROW = 32;     // floats per partial row
+
+static inline int loss_nblk(int64_t n) {
+    int64_t b = (n + 2047) / 2048;
+    if (b > LOSS_MAXBLK) b = LOSS_MAXBLK;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+// block-reduce K values held per thread; thread 0 writes them to row[]
+template <int K>
+__device__ __forceinline__ void block_reduce_store(float (&v)[K], float* row) {
+    __shared__ float red[4][K];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = uh_wave_sum(v[k]);
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[wave][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x < K) row[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// one block of 256 threads: column sums of partials[nblk][LOSS_ROW] in double (tree reduction)
+__device__ __forceinline__ double column_sum_256(const float* __restrict__ partials, int nblk, int k, double* red) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 256) s += (double)partials[(int64_t)b * LOSS_ROW + k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// mask / mask_div as the reference's `true_masks //= 2` leaves it for the class indices a mask holds (train.py:119).  A 64-bit
+// integer division is ~100 instructions on this chip and these kernels are instruction-bound (2 M elements, a few bytes each):
+// values in [0, 2^31) -- every real mask -- take a shift (divisor 2) or a 32-bit division; anything else the full division.
+__device__ __forceinline__ float uh_mask_quot(int64_t m, int mask_div) {
+    if ((uint64_t)m < (1ull << 31)) {
+        const int v = (int)m;
+        return (float)(mask_div == 2 ? (v >> 1) : (mask_div == 1 ? v : v / mask_div));
+    }
+    return (float)(m / mask_div);
+}

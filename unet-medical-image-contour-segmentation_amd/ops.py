@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 from typing import NamedTuple, Optional, Tuple
 
@@ -1556,6 +1557,25 @@ def boundary_loss_value(pred: torch.Tensor, pstride: int, bstride: int, target: 
     return out
 
 
+def boundary_loss_mask_value(logits: torch.Tensor, mask: torch.Tensor, mask_div: int, edge_width: int, edge_weight: float,
+                             smooth: float = 1e-6) -> torch.Tensor:
+    """boundary_loss(logits, (mask // mask_div).float(), edge_width, edge_weight) of train.py:134 for logits [B,H,W]: the kernel
+    divides the int64 mask itself.  A value without gradient, fp32 [1]."""
+    _require_gpu(logits, "logits")
+    lg = logits.detach().float().contiguous()
+    mk = mask.contiguous()
+    if mk.dtype != torch.int64:
+        mk = mk.long()
+    if mk.dim() != 3 or tuple(lg.shape) != tuple(mk.shape):
+        raise RuntimeError(f"boundary loss expects logits and mask [B,H,W], got {tuple(logits.shape)} and {tuple(mask.shape)}")
+    B, H, W = mk.shape
+    out = torch.empty(1, dtype=torch.float32, device=lg.device)
+    ws = loss_workspace(lg.device)
+    LIB.call("uh_boundary_loss_mask", lg.data_ptr(), 1, H * W, mk.data_ptr(), int(mask_div), B, H, W, int(edge_width),
+             float(edge_weight), float(smooth), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
 # Single-process binary loss as three launches (uh_seg_loss_binary_fused) instead of six + glue; False: the separate calls
 # (what data-parallel runs use anyway: their sums are all-reduced between the calls).  The two are bit-identical (tests).
 FUSE_LOSS = os.environ.get("UH_FUSE_LOSS", "1") != "0"
@@ -2068,3 +2088,88 @@ class SurfaceLossFn(Function):
         if dtype != torch.float32:
             dl = dl.to(dtype)
         return dl, None, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------- focal + Tversky loss (csrc/focal_loss.hip)
+FOCAL_MAX_CLASSES = 8
+
+
+def focal_head(n_classes: int, weights=None, classes=None) -> Tuple[Tuple[float, ...], Tuple[int, ...]]:
+    """Class weights and Tversky classes checked against a head: `n_classes` = 1 (the one-channel head: two classes, labels
+    mask // 2) or 2..8.  Defaults: all weights 1, classes 1..C-1."""
+    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= n_classes <= FOCAL_MAX_CLASSES:
+        raise ValueError(f"focal / Tversky loss: heads of 1 to {FOCAL_MAX_CLASSES} classes, got {n_classes!r}")
+    C = 2 if n_classes == 1 else int(n_classes)
+    w = (1.0,) * C if weights is None else tuple(float(v) for v in weights)
+    if len(w) != C:
+        raise ValueError(f"focal / Tversky loss: {len(w)} class weights for a head of {C} classes"
+                         + (" (the one-channel head has two: background, foreground)" if n_classes == 1 else ""))
+    if not all(math.isfinite(v) and v > 0.0 for v in w):
+        raise ValueError(f"focal / Tversky loss: class weights must be finite and > 0, got {w}")
+    cls = tuple(range(1, C)) if classes is None else tuple(int(c) for c in classes)
+    if not cls or len(set(cls)) != len(cls) or min(cls) < 0 or max(cls) >= C:
+        raise ValueError(f"focal / Tversky loss: classes {cls} must be distinct ids in [0, {C})")
+    return w, cls
+
+
+class FocalTverskyLossFn(Function):
+    """The focal + Tversky loss of DESIGN.md section 3 in one node: logits [B,H,W] (the one-channel head: two classes on the
+    logits (0, z), labels mask // mask_div) or NHWC [B,H,W,C] (softmax), int64 labels [B,H,W]; `weights` one per class (two for
+    the one-channel head), `classes` the Tversky subset.  Returns (total, focal, tversky) as 0-dim tensors; only `total` carries
+    gradient.  `reduce_sums` sums the 2 + 3 C partial sums over data-parallel ranks between the two passes: value and gradient
+    are then those of the GLOBAL batch (`world` is accepted for symmetry with the other loss nodes: the focal term is
+    normalised by the reduced sum of weights, not by a pixel count).  Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, logits, mask, mask_div: int, weights, gamma: float, alpha: float, beta: float, classes,
+                reduce_sums=None, world: float = 1):
+        _require_gpu(logits, "logits")
+        lg = logits.float().contiguous()
+        mk = _label_batch(mask)
+        B, H, W = mk.shape
+        if lg.dim() not in (3, 4) or tuple(lg.shape[:3]) != (B, H, W):
+            raise RuntimeError(f"focal / Tversky loss expects logits [B,H,W] or [B,H,W,C] matching labels {tuple(mk.shape)}, got "
+                               f"{tuple(logits.shape)}")
+        ncls = 1 if lg.dim() == 3 else int(lg.shape[-1])
+        if ncls == 1 and lg.dim() == 4:
+            raise RuntimeError("focal / Tversky loss: the one-channel head passes its logits as [B,H,W]")
+        w, cls = focal_head(ncls, weights, classes)
+        gamma, alpha, beta = float(gamma), float(alpha), float(beta)
+        if not (math.isfinite(gamma) and gamma >= 0.0):
+            raise ValueError(f"focal / Tversky loss: gamma must be finite and >= 0, got {gamma}")
+        if not (math.isfinite(alpha) and math.isfinite(beta) and alpha >= 0.0 and beta >= 0.0 and alpha + beta > 0.0):
+            raise ValueError(f"focal / Tversky loss: alpha and beta must be finite and >= 0 with alpha + beta > 0, got {alpha}, {beta}")
+        npix = B * H * W
+        dev = lg.device
+        warr = (ctypes.c_float * len(w))(*w)
+        sums = torch.empty(LIB.query("uh_focal_tversky_nsums", ncls), dtype=torch.float32, device=dev)
+        ws = loss_workspace(dev)
+        LIB.call("uh_focal_tversky_sums", lg.data_ptr(), mk.data_ptr(), int(mask_div), npix, ncls, warr, gamma, sums.data_ptr(),
+                 ws.data_ptr(), ws.numel(), _stream())
+        if reduce_sums is not None:
+            reduce_sums(sums)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        LIB.call("uh_focal_tversky_finish", sums.data_ptr(), ncls, alpha, beta, _class_array(cls), len(cls), out.data_ptr(), _stream())
+        ctx.save_for_backward(lg, mk, sums)
+        ctx.meta = (int(mask_div), npix, ncls, w, gamma, alpha, beta, cls, logits.shape, logits.dtype)
+        ctx.set_materialize_grads(False)
+        total, focal, tversky = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(focal, tversky)
+        return total, focal, tversky
+
+    @staticmethod
+    def backward(ctx, g_total, *_unused):
+        if g_total is None:
+            return (None,) * 10
+        lg, mk, sums = ctx.saved_tensors
+        mask_div, npix, ncls, w, gamma, alpha, beta, cls, shape, dtype = ctx.meta
+        g0 = g_total.reshape(1)
+        if g0.dtype != torch.float32 or not g0.is_contiguous():
+            g0 = g0.contiguous().float()
+        dl = torch.empty_like(lg)
+        LIB.call("uh_focal_tversky_grad", lg.data_ptr(), mk.data_ptr(), mask_div, npix, ncls, (ctypes.c_float * len(w))(*w), gamma,
+                 alpha, beta, _class_array(cls), len(cls), sums.data_ptr(), g0.data_ptr(), dl.data_ptr(), _stream())
+        dl = dl.view(shape)
+        if dtype != torch.float32:
+            dl = dl.to(dtype)
+        return (dl,) + (None,) * 9

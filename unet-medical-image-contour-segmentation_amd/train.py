@@ -42,12 +42,44 @@ def _add_surface(terms: Dict[str, torch.Tensor], lg: torch.Tensor, true_masks: t
     return terms
 
 
+def _focal_tversky_terms(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int, loss, w_b: float, reduce_sums,
+                         world) -> Dict[str, torch.Tensor]:
+    """The loss node of seg_loss with `loss` (a LossConfig): focal + tversky (DESIGN.md section 3 "Focal / Tversky loss") in
+    place of the CE + Dice pair, + w_b * boundary_loss as the pair has it (a value without gradient, per rank)."""
+    from .utils.focal_loss import focal_tversky_terms
+    total, focal, tversky = focal_tversky_terms(masks_pred, true_masks, n_classes, loss, reduce_sums=reduce_sums, world=world)
+    terms = {"loss": total, "focal": focal, "tversky": tversky}
+    if w_b != 0.0:
+        B, _, H, W = masks_pred.shape
+        if n_classes == 1:
+            bnd = ops.boundary_loss_mask_value(masks_pred.detach().squeeze(1), true_masks, 2, 51, 15.0)[0]      # train.py:134
+        else:
+            lg = masks_pred.detach().permute(0, 2, 3, 1).float().contiguous()
+            bnd = ops.boundary_loss_value(lg[..., 1], n_classes, H * W * n_classes, true_masks.float(), B, H, W, 51, 7.0)[0]
+        terms["loss"] = total + w_b * bnd
+        terms["boundary"] = bnd
+    else:
+        terms["boundary"] = torch.zeros((), dtype=torch.float32, device=total.device)
+    return terms
+
+
 def seg_loss(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int, *, reduce_sums=None, world: float = 1,
-             boundary_weight: Optional[float] = None, surface_weight: float = 0.0, surface_classes=None) -> Dict[str, torch.Tensor]:
+             boundary_weight: Optional[float] = None, surface_weight: float = 0.0, surface_classes=None,
+             loss=None) -> Dict[str, torch.Tensor]:
     """train.py:118-142.  masks_pred: logits [B,n_classes,H,W] (as returned by the model);
     true_masks: int64 [B,H,W] with the dataset's values {0,1,2,..} (NOT yet // 2).
     surface_weight != 0 adds surface_weight * surface loss over `surface_classes` (default: the class evaluate scores) and the
-    term "surface"; with 0 nothing else is launched and the result is what it is without the option."""
+    term "surface"; with 0 nothing else is launched and the result is what it is without the option.
+    loss (a utils.focal_loss.LossConfig or its spec string; default None: the code path, the launches and the results are what
+    they are without the option): the class-weighted focal + Tversky node replaces the CE + Dice pair, and the terms carry
+    "focal" and "tversky" in place of "ce" / "bce" and "dice"; the boundary and surface terms stay on top."""
+    if loss is not None:
+        w_b = (0.25 if n_classes == 1 else 0.0) if boundary_weight is None else float(boundary_weight)
+        terms = _focal_tversky_terms(masks_pred, true_masks, n_classes, loss, w_b, reduce_sums, world)
+        if surface_weight:
+            lg = masks_pred.squeeze(1) if n_classes == 1 else masks_pred.permute(0, 2, 3, 1)
+            _add_surface(terms, lg, true_masks, n_classes, surface_weight, surface_classes, reduce_sums, world)
+        return terms
     if n_classes == 1:
         w_b = 0.25 if boundary_weight is None else boundary_weight          # train.py:134
         lg = masks_pred.squeeze(1)
@@ -490,17 +522,19 @@ def _pinned_flag(device, n: int = 1) -> torch.Tensor:
 def train_step(model: nn.Module, optimizer, images: torch.Tensor, true_masks: torch.Tensor, *, amp: bool = True,
                gradient_clipping: float = 1.0, reduce_sums=None, world: int = 1, check_nan: bool = True,
                boundary_weight: Optional[float] = None, cc_loss: bool = False, surface_weight: float = 0.0,
-               surface_classes=None) -> Dict[str, torch.Tensor]:
+               surface_classes=None, loss=None) -> Dict[str, torch.Tensor]:
     """Statement sequence of train.py:113-159.  `optimizer` is a FusedRMSprop (clipping fused into
     its step) or any torch.optim optimizer (then clip_grad_norm_ is applied as in the reference).
-    surface_weight / surface_classes: the surface term of seg_loss (0: off, the step is what it is without the option)."""
+    surface_weight / surface_classes: the surface term of seg_loss (0: off, the step is what it is without the option).
+    loss: the focal + Tversky configuration of seg_loss (None: off, likewise)."""
     assert images.shape[1] == model.n_channels, \
         f"Network has been defined with {model.n_channels} input channels, but loaded images have " \
         f"{images.shape[1]} channels. Please check that the images are loaded correctly."   # train.py:108-111
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
         masks_pred = model(images)
         terms = seg_loss(masks_pred, true_masks, model.n_classes, reduce_sums=reduce_sums, world=world,
-                         boundary_weight=boundary_weight, surface_weight=surface_weight, surface_classes=surface_classes)
+                         boundary_weight=boundary_weight, surface_weight=surface_weight, surface_classes=surface_classes,
+                         **({} if loss is None else {"loss": loss}))
     if cc_loss and model.n_classes == 1:
         # the block train.py:124-132 keeps commented out (BASELINE config 5 turns it on): a Python float, no gradient.
         # sigmoid(x) > 0.5 <=> x > 0, so the 0/1 threshold mask stands in for the probabilities.  The masks stay on the
@@ -563,8 +597,15 @@ class TrainStepper:
     def __init__(self, model: nn.Module, lr: float = 1e-5, weight_decay: float = 1e-8, momentum: float = 0.999,
                  gradient_clipping: float = 1.0, amp: bool = True, process_group=None, check_nan: bool = True,
                  wgrad_stream: Optional[bool] = None, cc_loss: bool = False, sync_bn: bool = False, fp32_mode: str = "exact",
-                 surface_weight: float = 0.0, surface_classes=None, ema: Union[None, str, EmaConfig] = None):
+                 surface_weight: float = 0.0, surface_classes=None, ema: Union[None, str, EmaConfig] = None, loss=None):
         self.model = model
+        # loss: a utils.focal_loss.LossConfig or its spec string: the focal + Tversky node replaces the CE + Dice pair of every
+        # step, checked against the model's head here.  None (default): the step is what it is without the option.
+        self.loss = None
+        if loss is not None:
+            from .utils.focal_loss import LossConfig
+            self.loss = LossConfig.of(loss)
+            self.loss.for_head(model.n_classes)
         # ema: an EmaConfig or a spec string ("0.999,warmup=10"): the optimizer keeps a moving average of the parameters
         # (FusedRMSprop), averaged() computes with it.  None (default): nothing is allocated or launched for it.
         self.ema = EmaConfig.of(ema)
@@ -736,7 +777,8 @@ class TrainStepper:
         with self._step_state(images, self.sync_bn, global_batch) as world:
             return train_step(self.model, self.optimizer, images, true_masks, amp=self.amp,
                               reduce_sums=self.reduce_sums, world=world, check_nan=self.check_nan, cc_loss=self.cc_loss,
-                              surface_weight=self.surface_weight, surface_classes=self.surface_classes)
+                              surface_weight=self.surface_weight, surface_classes=self.surface_classes,
+                              **({} if self.loss is None else {"loss": self.loss}))
 
 
 class GraphedTrainStepper(TrainStepper):
@@ -755,6 +797,7 @@ class GraphedTrainStepper(TrainStepper):
         if self.cc_loss:
             raise RuntimeError("connected_component_loss returns a Python float (a device read-back every step): not capturable")
         self._refuse_surface()
+        self._refuse_loss()
         self._warmup = max(1, warmup)
         self._graph = None
         self._key = None
@@ -762,6 +805,10 @@ class GraphedTrainStepper(TrainStepper):
     def _refuse_surface(self):
         if self.surface_weight:
             raise RuntimeError("GraphedTrainStepper does not capture the surface loss (surface_weight must be 0): use TrainStepper")
+
+    def _refuse_loss(self):
+        if self.loss is not None:
+            raise RuntimeError("GraphedTrainStepper does not capture the focal / Tversky loss (loss must be None): use TrainStepper")
 
     def _eager_step(self, images, masks):
         with self._step_state(images, None):         # (single process: per-rank BatchNorm statistics, world = self.world)
@@ -799,6 +846,7 @@ class GraphedTrainStepper(TrainStepper):
 
     def step(self, images, true_masks):
         self._refuse_surface()
+        self._refuse_loss()
         self._refuse_averaged()
         key = (tuple(images.shape), tuple(true_masks.shape), float(self.optimizer.param_groups[0]["lr"]))
         if self._graph is None or key != self._key:

@@ -3,7 +3,7 @@
     python -m unet_amd.train -e 5 -b 1 -l 1e-5 -s 0.5 -c 3 [--bilinear] [-f model.pth] [--no-amp]
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
                              [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--elastic [SPEC]] [--surface-loss [SPEC]]
-                             [--ema [DECAY[,warmup=N]]] [--save-state] [--resume STATE]
+                             [--loss [SPEC]] [--ema [DECAY[,warmup=N]]] [--save-state] [--resume STATE]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -28,6 +28,11 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     csrc/surface_loss.hip) to every training step, its distance maps rebuilt on the device from the step's own (augmented)
     labels.  The weight of epoch e (1-based) is min(1, W + R (e - 1)); bare --surface-loss is "0.01,ramp=0.01"; classes default
     to the one evaluate scores.  One log line per epoch gives the weight, the epoch line the summed term;
+  - --loss [focal=G[,weights=w0+w1+..][,tversky=A/B][,classes=a+b]] (default: off; bare: "focal=2,tversky=0.3/0.7") replaces the
+    CE + Dice pair of every training step by the class-weighted focal + Tversky loss (utils/focal_loss.py, csrc/focal_loss.hip):
+    G the focusing exponent, one weight per class of the head (two for -c 1), A / B the prices of false positives / false
+    negatives, classes the Tversky subset (default 1..C-1).  The boundary and surface terms stay on top.  A spec that does not
+    fit --classes ends the command with status 2 before anything is loaded; the epoch line reports the summed terms;
   - --ema [DECAY[,warmup=N]] (default: off; bare: "0.999,warmup=10") keeps an exponential moving average of the parameters
     inside the optimizer pass (train.EmaConfig, csrc/optim.hip).  Every evaluation of the loop then runs ONCE, on the
     averaged weights (TrainStepper.averaged()): its Dice is what the log prints, marked "(EMA)", and what the learning-rate
@@ -61,6 +66,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import torch
 
 from .train import EmaConfig
+from .utils.focal_loss import LOSS_BARE, LossConfig
 
 MODELS = ("UNet_S", "UNet", "UNet_T", "UNet_SA")
 
@@ -78,7 +84,7 @@ STATE_FILE = "train_state.pth"
 # the arguments that determine a run, as --save-state records and --resume compares them: (record key, command-line name)
 RECORDED = (("model", "--model"), ("classes", "--classes"), ("bilinear", "--bilinear"), ("batch_size", "--batch-size"),
             ("scale", "--scale"), ("amp", "--amp / --no-amp"), ("lr", "--learning-rate"), ("augment", "--augment"),
-            ("elastic", "--elastic"), ("surface", "--surface-loss"), ("ema", "--ema"))
+            ("elastic", "--elastic"), ("surface", "--surface-loss"), ("ema", "--ema"), ("loss", "--loss"))
 
 
 def parse_surface_spec(text: str) -> SurfaceSpec:
@@ -140,6 +146,13 @@ def _ema_arg(text: str):
         raise argparse.ArgumentTypeError(f"bad --ema {text!r}: {e}") from None
 
 
+def _loss_arg(text: str):
+    try:
+        return LossConfig.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"bad --loss {text!r}: {e}") from None
+
+
 def run_record(args: argparse.Namespace) -> Dict:
     """The arguments that determine what a run computes (RECORDED), specs in their canonical form, None for an option that is
     off.  ValueError for a spec that does not parse."""
@@ -149,7 +162,8 @@ def run_record(args: argparse.Namespace) -> Dict:
             "augment": AugmentConfig.parse(args.augment).spec() if args.augment is not None else None,
             "elastic": ElasticConfig.parse(args.elastic).spec() if args.elastic is not None else None,
             "surface": surface_spec_text(args.surface_loss),
-            "ema": args.ema.spec() if args.ema is not None else None}
+            "ema": args.ema.spec() if args.ema is not None else None,
+            "loss": args.loss.spec() if getattr(args, "loss", None) is not None else None}
 
 
 def load_resume_state(args: argparse.Namespace) -> Optional[Dict]:
@@ -210,6 +224,11 @@ def build_parser() -> argparse.ArgumentParser:
                    metavar="W[,ramp=R][,classes=a+b]",
                    help="Add W * surface loss (distance to the true contour, maps built on the device each step); the weight of "
                         f"epoch e is min(1, W + R (e - 1)) (bare flag: '{SURFACE_BARE}'; default: off)")
+    p.add_argument("--loss", nargs="?", const=LOSS_BARE, default=None, type=_loss_arg,
+                   metavar="focal=G[,weights=w0+w1+..][,tversky=A/B][,classes=a+b]",
+                   help="Replace the CE + Dice pair by the class-weighted focal + Tversky loss: focusing exponent G, one weight per "
+                        f"class, false-positive / false-negative prices A / B over the given classes (bare flag: '{LOSS_BARE}'; "
+                        "default: off)")
     p.add_argument("--ema", nargs="?", const=EMA_BARE, default=None, type=_ema_arg, metavar="DECAY[,warmup=N]",
                    help="Keep an exponential moving average of the weights in the optimizer pass; evaluations run on it and "
                         f"*_ema.pth files are written beside the usual ones (bare flag: '{EMA_BARE}'; default: off)")
@@ -256,7 +275,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
                  train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
                  augment=None, surface: Optional[SurfaceSpec] = None, elastic=None, ema=None, save_state: bool = False,
-                 resume: Optional[Dict] = None, record: Optional[Dict] = None) -> List[Dict]:
+                 resume: Optional[Dict] = None, record: Optional[Dict] = None, loss=None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
@@ -268,6 +287,8 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     `ema`: an EmaConfig or a spec string; every evaluation then runs inside stepper.averaged() (once, on the averaged
     weights: that Dice is logged, marked "(EMA)", and drives the lr), every checkpoint gets a *_ema.pth twin, and the last
     record returned carries the averaged model as "ema_state_dict" (TrainStepper.ema_state_dict(), on the CPU).
+    `loss`: a LossConfig or a spec string; every step runs the focal + Tversky node in place of the CE + Dice pair, and the record
+    gains the summed "focal" and "tversky" terms.
     `save_state`: write checkpoint_dir/train_state.pth after every epoch, holding `record` (run_record) as its "args".
     `resume`: such a state (load_resume_state); the model must already hold its weights.  Optimizer state, lr, counters
     and the seeds are restored and the loop continues with the epoch after the saved one: only those epochs are returned."""
@@ -295,7 +316,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                 + (f"; elastic {augment.elastic.spec()}" if augment.elastic is not None else ""))
     val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
     stepper = TrainStepper(model, lr=learning_rate, amp=amp, surface_classes=surface.classes if surface is not None else None,
-                           ema=ema)
+                           ema=ema, loss=loss)
     lr = learning_rate
     global_step = 0
     first_epoch = 1
@@ -313,7 +334,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     history = []
     for epoch in range(first_epoch, epochs + 1):
         model.train()
-        losses, surfaces = [], []
+        losses, surfaces, focals, tverskys = [], [], [], []
         if surface is not None:
             stepper.surface_weight = surface_weight_at(surface, epoch)
             if log:
@@ -329,6 +350,9 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
             losses.append(terms["loss"].detach())
             if "surface" in terms:
                 surfaces.append(terms["surface"].detach())
+            if "focal" in terms:
+                focals.append(terms["focal"].detach())
+                tverskys.append(terms["tversky"].detach())
             seen += images.shape[0]
             global_step += 1
             if eval_due(global_step, n_train, batch_size):
@@ -361,6 +385,9 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
         if surface is not None:
             rec["surface_weight"] = stepper.surface_weight
             rec["surface"] = float(torch.stack(surfaces).double().sum().item()) if surfaces else 0.0
+        if stepper.loss is not None:
+            rec["focal"] = float(torch.stack(focals).double().sum().item()) if focals else 0.0
+            rec["tversky"] = float(torch.stack(tverskys).double().sum().item()) if tverskys else 0.0
         if checkpoint_dir is not None and checkpoint_due(epoch, epochs):
             path = os.path.join(checkpoint_dir, f"checkpoint_epoch{epoch}.pth")
             save_checkpoint(model, path, mask_values=mask_values)
@@ -376,6 +403,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
             log(f"Epoch {epoch}/{epochs}: loss (total) {epoch_loss:.6g}, Dice{tag} {dice[0]} / post {dice[1]} / min {dice[2]}, "
                 f"lr {lr:.6g}, {rec['img_s']:.1f} images/s ({seen} images, evaluation {eval_s:.2f} s)"
                 + (f", surface (summed) {rec['surface']:.6g} at weight {rec['surface_weight']:.6g}" if "surface" in rec else "")
+                + (f", focal (summed) {rec['focal']:.6g}, tversky (summed) {rec['tversky']:.6g}" if "focal" in rec else "")
                 + (f", checkpoint {rec['checkpoint']}" if "checkpoint" in rec else ""))
     if stepper.ema is not None and history:
         history[-1]["ema_state_dict"] = stepper.ema_state_dict()
@@ -402,6 +430,11 @@ def main(argv=None) -> int:
     args = get_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s: %(message)s")
     try:
+        if args.loss is not None:
+            try:
+                args.loss.for_head(args.classes)                              # against the head, before anything is loaded
+            except ValueError as e:
+                raise ValueError(f"--loss: {e}") from None
         resume = load_resume_state(args)                                      # a refused --resume needs no GPU to say so
         record = run_record(args) if (args.save_state or resume is not None) else None
     except ValueError as e:
@@ -453,7 +486,7 @@ def main(argv=None) -> int:
                            learning_rate=args.lr, amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed,
                            workers=args.workers, log=logging.info, pred_dir=args.pred_dir, metrics=args.metrics,
                            augment=augment, surface=args.surface_loss, elastic=elastic, ema=args.ema,
-                           save_state=args.save_state, resume=resume, record=record)
+                           save_state=args.save_state, resume=resume, record=record, loss=args.loss)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")
