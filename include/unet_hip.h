@@ -733,6 +733,30 @@ int uh_tta_views(const float* x, float* views0, float* views1, int B, int H, int
 int uh_tta_merge(const void* logits0, const void* logits1, int dt, int B, int H, int W, int NC, int mask, unsigned int* sums,
                  uint8_t* classes, float* probs, uh_stream stream);
 
+/* ---- sliding-window tiled prediction  (csrc/tiling.hip; the reference has none) ----------------------------------------
+ * Config: size, the tile side, a multiple of 16 in [16, 1024]; overlap, 0 <= overlap <= size / 2.  Per axis of length L the
+ * tile length is t = min(size, L) (no padding); L <= size: one tile at origin 0; otherwise the stride is S = size - overlap,
+ * there are n = ceil((L - size) / S) + 1 tiles and tile k starts at o_k = min(k S, L - size), so a position lies in at most 3
+ * tiles of an axis.  Position i of a tile has the weight w(i) = max(1, min(i + 1, t - i, overlap)); a tile's weight at a pixel
+ * is wy wx <= 2^18.  ny, nx: the tile counts of an H x W image; th = min(size, H), tw = min(size, W): its tile shape.
+ * uh_tile_grid: host only, no launch.  Fills *ny, *nx, *th, *tw and the origins oy[ny], ox[nx]; every output may be null
+ *   (ask for the counts first).  UH_EINVAL for a bad config or H, W < 1.
+ * uh_tile_gather: x DEVICE float32 [B][H][W][C] (C <= 8; the output of uh_predict_prepare_u8 for the WHOLE images) -> tiles
+ *   [B ny nx][th][tw][C], image-major, then row-major over the grid.  A pure copy, one launch for the batch.
+ * uh_tile_merge: src [B ny nx][th][tw][NC], the tiles' results: kind UH_F32 / UH_BF16 = logits, quantised per tile pixel as
+ *   uh_tta_merge quantises a view (q = (uint32) rintf(p 2^24), p the fp32 softmax, NC = 1: the sigmoid; the same device
+ *   function), views = 1; kind UH_TILE_SUMS_I32 = the int32 sums of uh_tta_merge over `views` (1, 2, 4 or 8) views, < 2^28.
+ *   Per image pixel the covering tiles' wy wx q are added in 64-bit integers (< 9 2^18 2^27 < 2^49): no atomics, no float in a
+ *   sum, the result is bit-reproducible.  Outputs, each nullable (one at least): sums uint64 [B][H][W][NC]; den uint32
+ *   [B][H][W] = the sum of wy wx; classes uint8 [B][H][W], the first maximum of the sums (NC = 1: 2 sum > den views 2^24);
+ *   probs float32 [B][H][W][NC] = (float)((double) sum / ((double) den views 2^24)).  1 <= NC <= 256; B <= 65535.
+ * Null or misaligned pointers, a bad kind, views or config: UH_EINVAL before any launch. */
+enum { UH_TILE_SUMS_I32 = 3 };
+int uh_tile_grid(int H, int W, int size, int overlap, int* ny, int* nx, int* th, int* tw, int* oy, int* ox);
+int uh_tile_gather(const float* x, float* tiles, int B, int H, int W, int C, int size, int overlap, uh_stream stream);
+int uh_tile_merge(const void* src, int kind, int views, int B, int H, int W, int NC, int size, int overlap,
+                  unsigned long long* sums, unsigned int* den, uint8_t* classes, float* probs, uh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -359,6 +359,16 @@ static inline CtmGeom ctm_geom(int B, int h, int w_, int Cin, int Cout, int Ho, 
 
 constexpr long long CT_MAX_BYTES = (1ll << 31) - 4096;
 
+// Zeroes n8 8-byte units at y (16-byte aligned): the F.pad border of a padded forward output, which the GEMM does not write.
+// A kernel rather than hipMemsetAsync: inside a captured eval forward (GraphedForward) the memset node left the border of
+// later replays unwritten, so a replay read what the graph's pool held there from the one before.
+__global__ __launch_bounds__(256) void ctm_zero_kernel(u32x2* __restrict__ y, size_t n8) {
+    const size_t n16 = n8 >> 1;
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride) ((u32x4*)y)[i] = u32x4{0u, 0u, 0u, 0u};
+    if ((n8 & 1) && blockIdx.x == 0 && threadIdx.x == 0) y[n8 - 1] = u32x2{0u, 0u};
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------ C ABI (MFMA path)
@@ -412,7 +422,10 @@ extern "C" int uh_convt2x2_fwd_mfma(const void* x, int ldx, const void* w_fwd, c
         UH_REQUIRE((ldx * (int)sizeof(T)) % 16 == 0 && (ldy * (int)sizeof(T)) % 8 == 0, "uh_convt2x2_fwd_mfma: strides");
         if (border) {
             UH_REQUIRE(ldy == Cout, "uh_convt2x2_fwd_mfma: a padded output must be pixel-dense");
-            (void)hipMemsetAsync(y, 0, (size_t)B * Ho * Wo * Cout * sizeof(T), st);
+            const size_t n8 = (size_t)B * Ho * Wo * Cout * sizeof(T) / 8;     // (ldy sizeof(T) % 8 == 0: whole units)
+            const size_t blocks = (n8 / 2 + 255) / 256;
+            hipLaunchKernelGGL(ctm_zero_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 4096 ? 4096 : blocks)), dim3(256), 0, st,
+                               (u32x2*)y, n8);
         }
         CtmArgs<T> a{};
         a.A = (const T*)w_fwd; a.lda = Cin; a.arows = 4 * Cout;

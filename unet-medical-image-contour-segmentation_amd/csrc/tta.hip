@@ -6,6 +6,7 @@
 //   uh_tta_merge   the views' logits -> per pixel the integer sum over the views of rint(p * 2^24), its first maximum, its mean
 // Nothing here synchronises with the host or allocates.
 #include "uh_common.h"
+#include "uh_quantise.h"
 
 namespace {
 
@@ -64,10 +65,7 @@ __global__ __launch_bounds__(256) void tta_views_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------ merge
-constexpr float TTA_ONE = 16777216.0f;          // 2^24: the unit of a quantised probability
-
-__device__ __forceinline__ unsigned tta_quantise(float p) { return (unsigned)rintf(p * TTA_ONE); }
-
+// (the quantised probability, tta_quantise and its softmax: uh_quantise.h, shared with tiling.hip)
 // the logits of source pixel (b, y, xs) in view v; k0 / k1 = how many t = 0 / t = 1 views of the mask precede v
 template <typename T>
 __device__ __forceinline__ const T* tta_at(const T* __restrict__ l0, const T* __restrict__ l1, int v, int k0, int k1, int B, int b,
@@ -106,21 +104,10 @@ __global__ __launch_bounds__(256) void tta_merge_kernel(const T* __restrict__ l0
         if (!((mask >> v) & 1)) continue;
         const T* p = tta_at<T>(l0, l1, v, k0, k1, B, b, H, W, y, xs, NC);
         if (v & 4) ++k1; else ++k0;
-        float l[NC];
+        unsigned q[NC];
+        tta_quantised_probs<T, NC>(p, q);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) l[c] = uh_to_f32(p[c]);
-        if (NC == 1) {
-            acc[0] += tta_quantise(1.0f / (1.0f + expf(-l[0])));
-        } else {
-            float m = l[0];
-#pragma unroll
-            for (int c = 1; c < NC; ++c) m = fmaxf(m, l[c]);
-            float s = 0.f;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) { l[c] = expf(l[c] - m); s += l[c]; }
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[c] += tta_quantise(l[c] / s);
-        }
+        for (int c = 0; c < NC; ++c) acc[c] += q[c];
     }
     const int V = k0 + k1;
     const int64_t pix = ((int64_t)b * H + y) * W + xs;
@@ -166,13 +153,8 @@ __global__ __launch_bounds__(256) void tta_merge_generic_kernel(const T* __restr
         if (!((mask >> v) & 1)) continue;
         const T* p = tta_at<T>(l0, l1, v, k0, k1, B, b, H, W, y, xs, NC);
         if (v & 4) ++k1; else ++k0;
-        float m = uh_to_f32(p[0]);
-        for (int c = 1; c < NC; ++c) m = fmaxf(m, uh_to_f32(p[c]));
-        float s = 0.f;
-        for (int c = 0; c < NC; ++c) s += expf(uh_to_f32(p[c]) - m);
         ptr[v] = p;
-        mx[v] = m;
-        den[v] = s;
+        tta_softmax_stats<T>(p, NC, mx[v], den[v]);
     }
     const int V = k0 + k1;
     const float inv = 1.0f / ((float)V * TTA_ONE);
@@ -183,7 +165,7 @@ __global__ __launch_bounds__(256) void tta_merge_generic_kernel(const T* __restr
 #pragma unroll
         for (int v = 0; v < 8; ++v) {
             if (!((mask >> v) & 1)) continue;
-            a += tta_quantise(expf(uh_to_f32(ptr[v][c]) - mx[v]) / den[v]);
+            a += tta_quantised_prob<T>(ptr[v][c], mx[v], den[v]);
         }
         if (sums) sums[pix * NC + c] = a;
         if (probs) probs[pix * NC + c] = (float)a * inv;

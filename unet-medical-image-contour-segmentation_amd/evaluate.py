@@ -9,6 +9,10 @@ until the accumulator's result() is read.  Without it nothing of that runs eithe
 With `tta` (a mode of utils/tta.py) the prediction that is scored is the average over the views of the mode: the views are built on
 the device (uh_tta_views), run through the batch-invariant forward and merged (uh_tta_merge); everything after the argmax /
 threshold runs on the merged classes unchanged.  Without it nothing of that runs.
+With `tile` (a utils.tiling.TileConfig or its spec) a batch whose images are larger than one tile is cut into tiles on the device
+(uh_tile_gather), the tiles run through the batch-invariant forward a batch at a time and uh_tile_merge puts the class map
+back together (with `tta`: per tile the views, the forward and uh_tta_merge, then the tile merge of the integer sums); a batch
+whose images fit in one tile takes the statements it takes without `tile`.  Without it nothing of that runs.
 `python -m unet_amd.evaluate -m CKPT --data-root DIR` scores a checkpoint without training (evaluate_cli.py)."""
 from __future__ import annotations
 
@@ -63,8 +67,34 @@ def _tta_classes(net, image, tta):
     return ops.tta_merge(logits0, logits1, tta, (H, W)).classes
 
 
+def _tile_classes(net, image, tile, tta):
+    """uint8 [B,H,W]: the classes of the tiled prediction of a batch (inside evaluate's autocast).  The tiles go through the
+    network len(image) at a time under the pinned plan of one image; with `tta` every such launch group goes through
+    _tta_classes' route and the tile merge adds the views' integer sums."""
+    B, _, H, W = image.shape
+    tiles = ops.tile_gather(image, tile)
+    th, tw = tiles.shape[-2:]
+    if tta is None:
+        with ops.plan_images(1):
+            src = torch.cat([net(tiles[s:s + B]) for s in range(0, tiles.shape[0], B)])
+        return ops.tile_merge(src, tile, (H, W)).classes
+    from .utils.tta import tta_counts
+    k0, k1 = tta_counts(tta)
+    sums = []
+    for s in range(0, tiles.shape[0], B):
+        part = tiles[s:s + B]
+        n = part.shape[0]
+        views0, views1 = ops.tta_views(part, tta)
+        with ops.plan_images(1):
+            logits0 = torch.cat([net(views0[k * n:(k + 1) * n]) for k in range(k0)])
+            logits1 = torch.cat([net(views1[k * n:(k + 1) * n]) for k in range(k1)]) if k1 else None
+        sums.append(ops.tta_merge(logits0, logits1, tta, (th, tw), sums=True).sums)
+    return ops.tile_merge(torch.cat(sums), tile, (H, W), k0 + k1).classes
+
+
 @torch.inference_mode()
-def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True, process_group=None, metrics=None, tta=None):
+def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True, process_group=None, metrics=None, tta=None,
+             tile=None):
     """evaluate.py:12-171.  `postprocess=True` is the reference's default (evaluate.py:13): the second return value is then
     the Dice after post-processing and the minimum is taken over min(raw, post-processed) per batch (evaluate.py:85).
     Batches are consumed lazily; under torch.distributed (every rank evaluating its shard of the validation set) the Dice
@@ -72,10 +102,15 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
     that is updated with the contour-metric records of the raw and (postprocess=True) the post-processed masks of every
     batch, P and T being exactly the masks whose Dice is taken, and all-reduced where the Dice sums are; the return value
     is the same 3-tuple either way.  `tta`: "hflip", "flips", "rot4" or "d4" -- the masks that are scored, post-processed,
-    measured and dumped are those of the prediction averaged over these views (None: one forward, as the reference)."""
+    measured and dumped are those of the prediction averaged over these views (None: one forward, as the reference).
+    `tile`: a TileConfig or a spec like "512,overlap=128" -- images larger than one tile are predicted tile by tile and merged
+    with the overlap blended (None: whole images)."""
     if tta is not None:
         from .utils.tta import tta_mask
         tta = tta_mask(tta)
+    if tile is not None:
+        from .utils.tiling import tile_config, tile_count
+        tile = tile_config(tile)
     net.eval()
     num_val_batches = 0
     dice_score = torch.zeros((), dtype=torch.float32, device=device)
@@ -88,17 +123,20 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
             image, mask_true = batch["image"], batch["mask"]
             image = image.to(device=device, dtype=torch.float32, memory_format=torch.channels_last)
             mask_true = mask_true.to(device=device, dtype=torch.float32)
-            if tta is None:
+            tiled = tile is not None and tile_count(image.shape[2], image.shape[3], tile) > 1
+            if tiled:
+                merged = _tile_classes(net, image, tile, tta)
+            elif tta is None:
                 mask_pred = net(image)
             else:
                 merged = _tta_classes(net, image, tta)
             if net.n_classes == 1:
                 mask_true = torch.div(mask_true, 2, rounding_mode="floor")                      # evaluate.py:56
                 assert mask_true.min() >= 0 and mask_true.max() <= 1, "True mask indices should be in [0, 1]"
-                if tta is None:
+                if tta is None and not tiled:
                     pred = ops.threshold_mask(mask_pred.squeeze(1))    # sigmoid(x) > 0.5  <=>  x > 0   (evaluate.py:60-62)
                 else:
-                    pred = merged.float()                              # the averaged sigmoid > 0.5
+                    pred = merged.float()                              # the averaged (or blended) sigmoid > 0.5
                 d = dice_coeff(pred, mask_true, reduce_batch_first=False)
                 cur = d
                 if postprocess:
@@ -118,7 +156,7 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
                 if dump is not None:                                                            # evaluate.py:88-105
                     dump.add(num_val_batches, pred.to(torch.uint8), "binary", processed_u8 if postprocess else None, "binary")
             else:
-                idx = ops.argmax_classes(mask_pred) if tta is None else merged.long()           # evaluate.py:111
+                idx = ops.argmax_classes(mask_pred) if tta is None and not tiled else merged.long()   # evaluate.py:111
                 true_c = (mask_true == 2).float()
                 d = dice_coeff((idx == 2).float(), true_c, reduce_batch_first=False)
                 cur = d

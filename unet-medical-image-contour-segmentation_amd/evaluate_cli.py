@@ -3,6 +3,7 @@
     python -m unet_amd.evaluate -m CKPT --data-root DIR [--split val] [--arch UNet_S|UNet|UNet_T|UNet_SA] [-c 3] [--bilinear]
                                 [-b 8] [-s 0.5] [--no-postprocess] [--no-amp] [--no-metrics] [--spacing 1.0]
                                 [--pred-dir DIR] [--workers 8] [--json OUT] [--tta [hflip|flips|rot4|d4]]
+                                [--tile [SIZE[,overlap=N]]]
 
 It reads DIR/imgs/SPLIT and DIR/masks/SPLIT through the loader the train command builds for validation (BasicDataset with
 its x4 quarter-turn augmentation, in order, drop_last=True: a trailing partial batch is not scored), loads the checkpoint
@@ -11,6 +12,7 @@ minimum -- and, unless --no-metrics, the contour metrics HD95 / HD / ASSD / IoU 
 (utils/contour_metrics.py).  --spacing is the isotropic pixel pitch the distances are reported in.  --pred-dir writes the
 predictions as grey-coded PNGs, as evaluate(epoch_pred_dir=...) does.  --json writes the set results and the per-image table.
 --tta scores the prediction averaged over the views of a mode (utils/tta.py; a bare --tta means d4) and records it in --json.
+--tile scores the sliding-window prediction (utils/tiling.py; a bare --tile means 512,overlap=128) and records its spec in --json.
 Exit status 1: a missing directory, an empty split (or one shorter than a batch), a checkpoint that does not load.  There is
 no CPU fallback: without a GPU the command exits with status 2, after those checks."""
 from __future__ import annotations
@@ -45,6 +47,17 @@ def build_parser() -> argparse.ArgumentParser:
     from .utils.tta import DEFAULT_MODE, MODES
     p.add_argument("--tta", nargs="?", const=DEFAULT_MODE, default=None, choices=tuple(MODES),
                    help="Test-time augmentation: average the prediction over these views (a bare --tta: d4; default: off)")
+    from .utils.tiling import DEFAULT_SPEC, parse_tile_spec
+
+    def tile_spec(text):
+        try:
+            return parse_tile_spec(text).spec
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e))
+
+    p.add_argument("--tile", nargs="?", const=DEFAULT_SPEC, default=None, type=tile_spec, metavar="SPEC",
+                   help="Sliding-window prediction: cut every image into tiles of SIZE[,overlap=N] pixels and blend the overlap "
+                        f"(a bare --tile: {DEFAULT_SPEC}; default: off)")
     return p
 
 
@@ -65,11 +78,14 @@ def _plain(v):
     return v
 
 
-def report(dice, contour, tta=None) -> dict:
-    """What --json writes: {"dice": {...}, "metrics": {"raw": {...}, "post": {...}} or null}, and "tta": mode under --tta."""
+def report(dice, contour, tta=None, tile=None) -> dict:
+    """What --json writes: {"dice": {...}, "metrics": {"raw": {...}, "post": {...}} or null}, "tta": mode under --tta and
+    "tile": spec under --tile."""
     out = {"dice": {"mean": float(dice[0]), "postprocessed": float(dice[1]), "min": float(dice[2])}, "metrics": None}
     if tta is not None:
         out["tta"] = tta
+    if tile is not None:
+        out["tile"] = tile
     if contour is not None:
         out["metrics"] = _plain(contour)
     return out
@@ -123,7 +139,7 @@ def main(argv=None) -> int:
     model.to(device=device)
     loader = DeviceBatchLoader(val_set, args.batch_size, shuffle=False, drop_last=True, workers=args.workers, device=device)
     acc = ContourMetrics(spacing=args.spacing) if args.metrics else None
-    dice = evaluate(model, loader, device, args.amp, args.pred_dir, postprocess=args.postprocess, metrics=acc, tta=args.tta)
+    dice = evaluate(model, loader, device, args.amp, args.pred_dir, postprocess=args.postprocess, metrics=acc, tta=args.tta, tile=args.tile)
     dice = tuple(float(v) for v in dice)
     logging.info("Validation Dice score: %s  postprocessed: %s  min: %s", *dice)
     contour = None
@@ -132,7 +148,7 @@ def main(argv=None) -> int:
         logging.info(format_line(contour, args.postprocess))
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(report(dice, contour, args.tta), f, indent=1)
+            json.dump(report(dice, contour, args.tta, args.tile), f, indent=1)
         logging.info("Results written to %s", args.json)
     return 0
 

@@ -1908,6 +1908,84 @@ def tta_merge(logits0: torch.Tensor, logits1: Optional[torch.Tensor], mode, size
     return TtaMerged(classes, s, p)
 
 
+# ----------------------------------------------------------------------------- tiled prediction (csrc/tiling.hip)
+UH_TILE_SUMS_I32 = 3                          # include/unet_hip.h: the int32 sums of uh_tta_merge as the source of uh_tile_merge
+
+
+class TileMerged(NamedTuple):
+    classes: torch.Tensor                     # uint8 [B,H,W]
+    sums: Optional[torch.Tensor]              # int64 [B,H,W,NC]: the weighted integer sums (< 2^49; uint64 in the library)
+    den: Optional[torch.Tensor]               # int32 [B,H,W]: the sum of the covering tiles' weights (< 2^22; uint32 in the library)
+    probs: Optional[torch.Tensor]             # float32 [B,H,W,NC] = sums / (den * views * 2^24)
+
+
+def tile_gather(x: torch.Tensor, cfg) -> torch.Tensor:
+    """The tiles of a batch of images [B,C,H,W] (fp32, read through its NHWC view) under a TileConfig / spec of utils/tiling.py
+    -> [B*ny*nx,C,th,tw], image-major then row-major over the grid, channels-last: what the network takes.  A pure copy."""
+    from .utils.tiling import tile_config, tile_grid
+    cfg = tile_config(cfg)
+    if cfg is None:
+        raise ValueError("tile_gather needs a tile config")
+    _require_gpu(x, "images")
+    if x.dim() != 4:
+        raise RuntimeError(f"tile_gather expects [B,C,H,W] images, got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    v = x.permute(0, 2, 3, 1)
+    if v.dtype != torch.float32:
+        v = v.float()
+    if not v.is_contiguous():
+        v = v.contiguous()
+    ny, nx, th, tw, _, _ = tile_grid(H, W, cfg)
+    tiles = torch.empty(B * ny * nx, th, tw, C, dtype=torch.float32, device=x.device)
+    LIB.call("uh_tile_gather", v.data_ptr(), tiles.data_ptr(), B, H, W, C, cfg.size, cfg.overlap, _stream())
+    return tiles.permute(0, 3, 1, 2)
+
+
+def tile_merge(src: torch.Tensor, cfg, size: Tuple[int, int], views: int = 1, *, sums: bool = False, probs: bool = False) -> TileMerged:
+    """Merges the results of the tiles of tile_gather back onto the image grid `size` = (H, W).  src: the tiles' logits
+    [B*ny*nx,NC,th,tw] (fp32 or bf16, read through their NHWC view; views = 1), or the int32 sums of tta_merge(sums=True) for
+    every tile, [B*ny*nx,th,tw,NC] as TtaMerged.sums holds them, with `views` the number of views they add up.
+    -> TileMerged(classes, sums or None, den or None, probs or None); den comes with sums."""
+    from .utils.tiling import tile_config, tile_grid
+    cfg = tile_config(cfg)
+    if cfg is None:
+        raise ValueError("tile_merge needs a tile config")
+    H, W = int(size[0]), int(size[1])
+    ny, nx, th, tw, _, _ = tile_grid(H, W, cfg)
+    if views not in (1, 2, 4, 8):
+        raise ValueError(f"tile_merge: views is 1, 2, 4 or 8, got {views!r}")
+    _require_gpu(src, "tile results")
+    if src.dim() != 4:
+        raise RuntimeError(f"tile_merge expects 4-d tile results, got {tuple(src.shape)}")
+    if src.dtype == torch.int32:
+        if tuple(src.shape[1:3]) != (th, tw) or src.shape[3] > 256:
+            raise RuntimeError(f"tile_merge expects [N,{th},{tw},NC<=256] int32 sums, got {tuple(src.shape)}")
+        v, kind = src, UH_TILE_SUMS_I32
+    else:
+        if views != 1:
+            raise ValueError("tile_merge: logits are one view (views = 1); pass the sums of tta_merge for more")
+        if tuple(src.shape[2:]) != (th, tw) or src.shape[1] > 256:
+            raise RuntimeError(f"tile_merge expects [N,C<=256,{th},{tw}] logits, got {tuple(src.shape)}")
+        v = src.permute(0, 2, 3, 1)
+        if v.dtype not in (torch.float32, torch.bfloat16):
+            v = v.float()
+        kind = _dt(v)
+    if not v.is_contiguous():
+        v = v.contiguous()
+    N, NC = v.shape[0], v.shape[3]
+    if N == 0 or N % (ny * nx):
+        raise RuntimeError(f"tile_merge: {N} tiles are not whole {H} x {W} images of {ny} x {nx} tiles")
+    B = N // (ny * nx)
+    dev = v.device
+    classes = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    s = torch.empty(B, H, W, NC, dtype=torch.int64, device=dev) if sums else None
+    d = torch.empty(B, H, W, dtype=torch.int32, device=dev) if sums else None
+    p = torch.empty(B, H, W, NC, dtype=torch.float32, device=dev) if probs else None
+    LIB.call("uh_tile_merge", v.data_ptr(), kind, int(views), B, H, W, NC, cfg.size, cfg.overlap, _p(s), _p(d), classes.data_ptr(),
+             _p(p), _stream())
+    return TileMerged(classes, s, d, p)
+
+
 # ----------------------------------------------------------------------------- contour metrics (csrc/contour_metrics.hip)
 CONTOUR_RECORD_DOUBLES = 12         # uh_contour_record: 12 x uint32 (= 6 doubles wide), then 6 x double
 _EDT_WS = {}

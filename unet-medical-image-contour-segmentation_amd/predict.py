@@ -3,7 +3,7 @@
     predict_img(model, full_img, device) -> np.ndarray[H, W] of class indices        predict.py:15-29
     mask_to_image(mask) -> PIL.Image (0 / 128 / 255 grey levels)                      predict.py:52-58
     preprocess_image(pil_img, scale=1.0) -> float32 [C, H, W]                         data_loading.py:65-91 (image branch)
-    BatchPredictor(model, batch=8, postprocess=True, batch_invariant=False, tta=None)(images) -> [uint8 [H, W] grey]
+    BatchPredictor(model, batch=8, postprocess=True, batch_invariant=False, tta=None, tile=None)(images) -> [uint8 [H, W] grey]
                                                                                       predict.py:120-135 for a list of images
     python -m unet_amd.predict -m model.pth -i DIR [-o OUT]                           predict.py:31-152 (predict_cli.py)
 
@@ -15,7 +15,7 @@ batch.  Its result for an image is, pixel for pixel, mask_to_image(postprocess_m
 """
 from __future__ import annotations
 
-from collections import OrderedDict
+from collections import OrderedDict, deque
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -154,12 +154,23 @@ class BatchPredictor:
     DESIGN.md section 3 "Test-time augmentation").  `batch` stays the number of images per forward launch, so a launch group
     holds batch // (views per launch) source images (`tta_group`); the view batches are cut by `launch_lengths` and replay
     captured graphs like any other batch, so every view gets the logits it gets alone and the prediction of a posed image is
-    exactly the posed prediction.  `probabilities(images)` returns the averaged probabilities.  None: nothing of this runs."""
+    exactly the posed prediction.  `probabilities(images)` returns the averaged probabilities.  None: nothing of this runs.
+
+    `tile` (a utils.tiling.TileConfig or its spec string, "512,overlap=128"): sliding-window prediction.  Every image is cut
+    into tiles of one shape, (min(size, H), min(size, W)), on the device (uh_tile_gather, after the prepare of the WHOLE image);
+    the tiles of all images of a call that share a tile shape are pooled, whatever the images' sizes, and forwarded `batch` at
+    a time through the same launch cutting and graph cache as any batch, so every launch but the last of a tile shape is full
+    and device memory holds `batch` tiles of activations plus the logits of the images in flight; uh_tile_merge adds the tiles'
+    quantised probabilities, weighted by a tent over the overlap, as integers and takes the first maximum (DESIGN.md section 3
+    "Tiled prediction").  Post-processing and grey coding run on the whole-image map as ever.  An image that fits in one tile
+    is that tile and gets the bits of the untiled path.  With `tta`, every chunk of `tta_group` tiles goes through the views,
+    the forward and uh_tta_merge, and the tile merge adds the views' integer sums; the tile origins are not mirror-symmetric,
+    so a posed image is NOT promised the posed prediction here.  None: nothing of this runs."""
 
     MAX_GRAPHS = 4
 
     def __init__(self, model: torch.nn.Module, batch: int = 8, postprocess: bool = True, amp: bool = True, device=None,
-                 min_area: int = 15000, morph_kernel_size: int = 3, batch_invariant: bool = False, tta=None):
+                 min_area: int = 15000, morph_kernel_size: int = 3, batch_invariant: bool = False, tta=None, tile=None):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.batch_invariant = bool(batch_invariant)
@@ -167,6 +178,10 @@ class BatchPredictor:
             from .utils.tta import tta_mask
             tta = tta_mask(tta)                                          # ValueError for anything but the four modes
         self.tta = tta
+        if tile is not None:
+            from .utils.tiling import tile_config
+            tile = tile_config(tile)                                     # ValueError for a bad size, overlap or spec
+        self.tile = tile
         if getattr(model, "n_classes", None) == 1:
             # predict.py:27 takes argmax(dim=1) of a one-channel tensor: all zeros.  Not reproduced.
             raise ValueError("BatchPredictor needs a multi-class head: predict.py's argmax over one channel is all zeros. "
@@ -295,6 +310,8 @@ class BatchPredictor:
         """One batch of equally sized uint8 [H,W] images -> uint8 [B,H,W] on the host (grey-coded, or class indices), in as
         few launches as launch_lengths allows."""
         H, W = arrays[0].shape
+        if getattr(self, "tile", None) is not None:
+            return np.stack(self._run_tiled(arrays, grey))
         if getattr(self, "tta", None) is not None:
             g = self.tta_group(H, W)
             out = [self._launch_tta(arrays[s:s + g], grey) for s in range(0, len(arrays), g)]
@@ -356,6 +373,18 @@ class BatchPredictor:
             s += b
         return torch.cat(pieces)
 
+    def _tta_logits(self, x: torch.Tensor, H: int, W: int):
+        """The logits of the views of a prepared batch [B,C,H,W]: (untransposed views, transposed views or None)."""
+        v0, v1 = self._mark("views", ops.tta_views, x, self.tta)
+        if v1 is not None and H == W:                                  # one view shape: one forward
+            l0, l1 = self._mark("forward", self._forward_cut, ops.tta_joint_views(v0, v1), (H, W)), None
+        else:
+            l0 = self._mark("forward", self._forward_cut, v0, (H, W))
+            l1 = self._mark("forward", self._forward_cut, v1, (W, H)) if v1 is not None else None
+        if tuple(l0.shape[-2:]) != (H, W) or (l1 is not None and tuple(l1.shape[-2:]) != (W, H)):
+            raise RuntimeError(f"the network returned {tuple(l0.shape[-2:])} for a {(H, W)} input")
+        return l0, l1
+
     def _launch_tta(self, arrays: List[np.ndarray], grey: bool, probs: bool = False) -> np.ndarray:
         """One launch group under test-time augmentation -> uint8 [B,H,W] as _launch, or (probs) float32 [B,NC,H,W]."""
         H, W = arrays[0].shape
@@ -365,21 +394,110 @@ class BatchPredictor:
             x = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
             flags = self._flags if B <= self._flags.numel() else torch.empty(B, dtype=torch.int32, device=self.device)
             self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
-            v0, v1 = self._mark("views", ops.tta_views, x, self.tta)
-            if v1 is not None and H == W:                              # one view shape: one forward
-                l0, l1 = self._mark("forward", self._forward_cut, ops.tta_joint_views(v0, v1), (H, W)), None
-            else:
-                l0 = self._mark("forward", self._forward_cut, v0, (H, W))
-                l1 = self._mark("forward", self._forward_cut, v1, (W, H)) if v1 is not None else None
-            if tuple(l0.shape[-2:]) != (H, W) or (l1 is not None and tuple(l1.shape[-2:]) != (W, H)):
-                raise RuntimeError(f"the network returned {tuple(l0.shape[-2:])} for a {(H, W)} input")
+            l0, l1 = self._tta_logits(x, H, W)
             merged = self._mark("merge", ops.tta_merge, l0, l1, self.tta, (H, W), probs=probs)
             if probs:
                 return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
             return self._deliver(merged.classes, grey)
 
+    # ---------------------------------------------------------------- tiled prediction
+    def tile_chunk(self, th: int, tw: int) -> int:
+        """Tiles of one shape per forward step: `batch`, or under test-time augmentation what tta_group allows (it counts
+        tiles here: `batch` stays the number of network inputs per forward launch)."""
+        return self.batch if getattr(self, "tta", None) is None else self.tta_group(th, tw)
+
+    def _prepare_tiles(self, arrays: List[np.ndarray]) -> torch.Tensor:
+        """Equally sized images -> their tiles [B*ny*nx,1,th,tw] on the device; the prepare sees the WHOLE images."""
+        H, W = arrays[0].shape
+        B = len(arrays)
+        with torch.cuda.device(self.device):
+            busy = getattr(self, "_upload_done", None)
+            if busy is not None:
+                busy.synchronize()                 # the pinned staging buffer is free once the previous upload has left it
+            img = self._mark("upload", self._upload, arrays, H, W)
+            self._upload_done = torch.cuda.Event()
+            self._upload_done.record()
+            x = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
+            flags = self._flags if B <= self._flags.numel() else torch.empty(B, dtype=torch.int32, device=self.device)
+            self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
+            return self._mark("gather", ops.tile_gather, x, self.tile)
+
+    def _tile_forward(self, tiles: torch.Tensor, shape: Tuple[int, int]) -> torch.Tensor:
+        """One forward step of the tiled flow: the logits [n,NC,th,tw] of the tiles, or under test-time augmentation the
+        int32 sums [n,th,tw,NC] over their views."""
+        th, tw = shape
+        with torch.cuda.device(self.device):
+            if self.tta is None:
+                logits = self._mark("forward", self._forward_cut, tiles, shape)
+                if tuple(logits.shape[-2:]) != (th, tw):
+                    raise RuntimeError(f"the network returned {tuple(logits.shape[-2:])} for a {(th, tw)} input")
+                return logits.clone()                                  # (a replayed graph returns its static buffer)
+            l0, l1 = self._tta_logits(tiles, th, tw)
+            return self._mark("merge", ops.tta_merge, l0, l1, self.tta, shape, sums=True).sums
+
+    def _tile_finish(self, src: torch.Tensor, H: int, W: int, grey: bool, probs: bool) -> np.ndarray:
+        """The results of every tile of a batch of H x W images -> uint8 [B,H,W] as _launch, or (probs) float32 [B,NC,H,W]."""
+        from .utils.tiling import tile_count
+        views = 1
+        if self.tta is not None:
+            from .utils.tta import tta_counts
+            views = sum(tta_counts(self.tta))
+        with torch.cuda.device(self.device):
+            if probs:
+                merged = self._mark("tile_merge", ops.tile_merge, src, self.tile, (H, W), views, probs=True)
+                return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
+            if self.tta is None and tile_count(H, W, self.tile) == 1:
+                cls = self._mark("classes", ops.logits_to_classes_u8, src)     # the tile is the image: the untiled statement
+            else:
+                cls = self._mark("tile_merge", ops.tile_merge, src, self.tile, (H, W), views).classes
+            return self._deliver(cls, grey)
+
+    def _run_tiled(self, arrays: List[np.ndarray], grey: bool, probs: bool = False) -> List[np.ndarray]:
+        """Images of any sizes -> their results in input order.  The tiles of all images that share a tile shape are pooled:
+        same-size images (up to `batch`) share an upload, a prepare, a gather and a merge; the pool forwards `tile_chunk`
+        tiles at a time, so every forward step but the last of a tile shape is full, and an image is merged and delivered
+        as soon as its last tile is through."""
+        from .utils.tiling import tile_shape
+        result: List[Optional[np.ndarray]] = [None] * len(arrays)
+        by_shape: "OrderedDict[Tuple[int, int], List[int]]" = OrderedDict()
+        for i, a in enumerate(arrays):
+            by_shape.setdefault(tile_shape(a.shape[0], a.shape[1], self.tile), []).append(i)
+        for shape, members in by_shape.items():
+            chunk = self.tile_chunk(*shape)
+            waiting: Optional[torch.Tensor] = None                     # tiles not yet forwarded
+            done: List[torch.Tensor] = []                              # results of forwarded tiles, in order
+            n_done = 0
+            records = deque()                                          # (image indices, H, W, tiles) in tile order
+
+            def advance(final: bool):
+                nonlocal waiting, done, n_done
+                while waiting is not None and (waiting.shape[0] >= chunk or final):
+                    part, rest = waiting[:chunk], waiting[chunk:]
+                    waiting = rest if rest.shape[0] else None
+                    done.append(self._tile_forward(part, shape))
+                    n_done += part.shape[0]
+                    while records and records[0][3] <= n_done:
+                        idx, H, W, n = records.popleft()
+                        have = done[0] if len(done) == 1 else torch.cat(done)
+                        done = [have[n:]] if have.shape[0] > n else []
+                        n_done -= n
+                        out = self._tile_finish(have[:n], H, W, grey, probs)
+                        for k, i in enumerate(idx):
+                            result[i] = np.ascontiguousarray(out[k])
+
+            for _, group in plan_batches([arrays[i].shape for i in members], self.batch):
+                idx = [members[k] for k in group]
+                tiles = self._prepare_tiles([arrays[i] for i in idx])
+                records.append((idx, arrays[idx[0]].shape[0], arrays[idx[0]].shape[1], tiles.shape[0]))
+                waiting = tiles if waiting is None else torch.cat([waiting, tiles])
+                advance(False)
+            advance(True)
+        return result
+
     def _run(self, images, grey: bool) -> List[np.ndarray]:
         arrays = [_as_grey_array(im) for im in images]
+        if getattr(self, "tile", None) is not None:
+            return self._run_tiled(arrays, grey)
         result: List[Optional[np.ndarray]] = [None] * len(arrays)
         for _, members in plan_batches([a.shape for a in arrays], self.batch):
             out = self.run_batch([arrays[i] for i in members], grey)
@@ -394,11 +512,14 @@ class BatchPredictor:
         return self._run(images, False)
 
     def probabilities(self, images) -> List[np.ndarray]:
-        """float32 [NC,H,W] per image: the mean over the views of the softmax probabilities (multiples of 2^-24 / V)."""
-        if getattr(self, "tta", None) is None:
-            raise RuntimeError("probabilities() returns the mean over the views of test-time augmentation: build the predictor "
-                               "with tta=...")
+        """float32 [NC,H,W] per image: the mean over the views of the softmax probabilities (multiples of 2^-24 / V); under
+        `tile` the weighted mean over the covering tiles (and their views), (float)(sum / (den V 2^24))."""
+        if getattr(self, "tta", None) is None and getattr(self, "tile", None) is None:
+            raise RuntimeError("probabilities() returns the mean over the views of test-time augmentation (tta=...) or over the "
+                               "covering tiles of tiled prediction (tile=...): build the predictor with one of them")
         arrays = [_as_grey_array(im) for im in images]
+        if getattr(self, "tile", None) is not None:
+            return self._run_tiled(arrays, False, probs=True)
         result: List[Optional[np.ndarray]] = [None] * len(arrays)
         for (H, W), members in plan_batches([a.shape for a in arrays], self.batch):
             g = self.tta_group(H, W)

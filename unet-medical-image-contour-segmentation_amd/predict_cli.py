@@ -2,14 +2,16 @@
 
     python -m unet_amd.predict -m model.pth -i FILE_OR_DIR [-o OUT] [-n] [-v] [--no-postprocess]
                                [--arch UNet] [-c 3] [--bilinear] [--no-amp] [-b 8] [--workers 8] [--no-batch-invariant]
-                               [--tta [hflip|flips|rot4|d4]]
+                               [--tta [hflip|flips|rot4|d4]] [--tile [SIZE[,overlap=N]]]
 
 Every image is predicted at its own size (scale 1).  The images of a folder are decoded by a thread pool, grouped by size,
 run through BatchPredictor in batches (prepare, eval forward, classes, post-processing and grey coding on the device, one
 upload and one download per batch) and encoded to PNG by the same pool while the next batch runs.  The forward is
 batch-invariant (BatchPredictor(batch_invariant=True)): a batch is one launch and every image gets the bits it gets alone;
 --no-batch-invariant cuts the batches instead, to the same files.  --tta averages the prediction over the views of a mode
-(utils/tta.py; a bare --tta means d4): -b stays the number of images per forward launch, views included.
+(utils/tta.py; a bare --tta means d4): -b stays the number of images per forward launch, views included.  --tile predicts
+every image as overlapping tiles of one shape (utils/tiling.py; a bare --tile means 512,overlap=128): the images are grouped
+by tile shape instead of size, the tiles of a group share full forward launches of -b tiles, and the overlap is blended.
 
 Reference behaviour that is kept, awkward parts included:
   - predict.py:33-38  the flags -m, -i (both required), -o, -v, -n, and -p, a store_true whose default is already True;
@@ -70,6 +72,17 @@ def build_parser() -> argparse.ArgumentParser:
     from .utils.tta import DEFAULT_MODE, MODES
     p.add_argument("--tta", nargs="?", const=DEFAULT_MODE, default=None, choices=tuple(MODES),
                    help="Test-time augmentation: average the prediction over these views (a bare --tta: d4; default: off)")
+    from .utils.tiling import DEFAULT_SPEC, parse_tile_spec
+
+    def tile_spec(text):
+        try:
+            return parse_tile_spec(text).spec
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e))
+
+    p.add_argument("--tile", nargs="?", const=DEFAULT_SPEC, default=None, type=tile_spec, metavar="SPEC",
+                   help="Sliding-window prediction: cut every image into tiles of SIZE[,overlap=N] pixels and blend the overlap "
+                        f"(a bare --tile: {DEFAULT_SPEC}; default: off)")
     return p
 
 
@@ -118,13 +131,16 @@ def run(predictor, files: List[str], output: Optional[str], save: bool, workers:
     workers = max(1, int(workers))
     failed: List[str] = []
     planner = BatchPlanner(predictor.batch, window if window is not None else 16 * predictor.batch)
+    tile = getattr(predictor, "tile", None)
+    if tile is not None:
+        from .utils.tiling import tile_shape
     held = {}
     with ThreadPoolExecutor(max_workers=workers, thread_name_prefix="predict-io") as pool:
         writer = OrderedPngWriter(pool=pool)
 
         def finish(members):
             imgs = [held.pop(i) for i in members]
-            out = predictor.run_batch(imgs)
+            out = predictor(imgs) if tile is not None else predictor.run_batch(imgs)     # (tiled: sizes are mixed)
             for k, i in enumerate(members):
                 if save:
                     writer.submit(i, output_path(output, files[i]), out[k])
@@ -150,7 +166,7 @@ def run(predictor, files: List[str], output: Optional[str], save: bool, workers:
                 writer.skip(i)
                 continue
             held[i] = img
-            for _, members in planner.add(i, img.shape):
+            for _, members in planner.add(i, img.shape if tile is None else tile_shape(img.shape[0], img.shape[1], tile)):
                 finish(members)
         for _, members in planner.flush():
             finish(members)
@@ -213,7 +229,7 @@ def main(argv=None) -> int:
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info("Using device %s", device)
     predictor = BatchPredictor(model, batch=args.batch_size, postprocess=args.postprocess, amp=args.amp, device=device,
-                               batch_invariant=args.batch_invariant, tta=args.tta)
+                               batch_invariant=args.batch_invariant, tta=args.tta, tile=args.tile)
     if args.output is not None and not args.no_save:
         os.makedirs(args.output, exist_ok=True)                       # predict.py:48
     show = (lambda path, img, grey: _show(plt, path, img, grey)) if plt is not None else None
