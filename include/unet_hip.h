@@ -757,6 +757,35 @@ int uh_tile_gather(const float* x, float* tiles, int B, int H, int W, int C, int
 int uh_tile_merge(const void* src, int kind, int views, int B, int H, int W, int NC, int size, int overlap,
                   unsigned long long* sums, unsigned int* den, uint8_t* classes, float* probs, uh_stream stream);
 
+/* ---- patch training: seeded foreground-aware crops  (csrc/crop.hip; the reference has none) ---------------------------
+ * One square crop of side `size` (a multiple of 16, >= 16) per item.  The item table is HOST memory, one row per item, and the
+ * items may differ in size (1 <= H, W <= 16384, both >= size): every row is checked before any launch and the rows travel
+ * by value in the kernel arguments, so no call copies, allocates or synchronises with the host.  r[0..3] are the item's four
+ * random words.  With ny = H - size + 1, nx = W - size + 1 and n the number of pixels whose label v has bit v of class_mask
+ * set (labels outside 0..63 never count):
+ *   foreground branch, iff n > 0 and r[0] < fg_threshold (0 .. 2^32):  k = (r[1] n) >> 32, (py, px) the k-th such pixel in
+ *     raster order, jy = (r[2] size) >> 32, jx = (r[3] size) >> 32, oy = clamp(py - jy, 0, ny - 1), ox = clamp(px - jx, 0, nx - 1);
+ *   uniform branch, otherwise:  oy = (r[2] ny) >> 32, ox = (r[3] nx) >> 32.
+ * uh_crop_select: origin DEVICE int32 [B][2] = (oy, ox); count DEVICE uint32 [B] = n, nullable; ws DEVICE, at least
+ *   uh_crop_select_ws_bytes(B) bytes, 4-byte aligned.  Two launches per 32 rows, no atomics; `image` and `ld` are not read.
+ * uh_crop_gather: image_out [B][size][size][ld_out] in dt (UH_F32 / UH_BF16) and labels_out int64 [B][size][size], each nullable
+ *   (one at least; without image_out the rows' `image` may be null): the bits of [oy, oy + size) x [ox, ox + size) of every
+ *   item, C channels (1 .. 4) of a pixel.  The origin is clamped into [0, H - size] x [0, W - size] as it is loaded, so no source
+ *   address leaves its item whatever the table holds.  Sources need the alignment of their element only.
+ * Null or misaligned pointers, a bad size, C, stride, dtype or threshold, a row smaller than `size` or a short workspace:
+ * UH_EINVAL before any launch. */
+typedef struct uh_crop_item {
+    const void* image;                 /* DEVICE NHWC [H][W][ld] in dt, or NULL (labels only) */
+    const int64_t* labels;             /* DEVICE int64 [H][W] */
+    int H, W, ld, reserved;
+    uint32_t r[4];
+} uh_crop_item;
+size_t uh_crop_select_ws_bytes(int B);
+int uh_crop_select(const uh_crop_item* items, int B, int size, uint64_t class_mask, uint64_t fg_threshold, int32_t* origin,
+                   uint32_t* count, void* ws, size_t ws_bytes, uh_stream stream);
+int uh_crop_gather(const uh_crop_item* items, int B, int C, int dt, int size, const int32_t* origin, void* image_out, int ld_out,
+                   int64_t* labels_out, uh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

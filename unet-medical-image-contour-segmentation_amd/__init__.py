@@ -18,6 +18,7 @@ from .utils.augment import AugmentConfig, BatchAugment, ElasticConfig  # noqa: F
 from .utils.post_process import postprocess_mask, remove_internal_regions  # noqa: F401
 from .utils.tta import tta_mask, tta_view_shape, tta_source_position  # noqa: F401
 from .utils.tiling import TileConfig, parse_tile_spec, tile_grid  # noqa: F401
+from .utils.crop import CropConfig, BatchCrop  # noqa: F401
 from .inference import GraphedForward  # noqa: F401
 from .utils.raw2png import read_raw, window_level  # noqa: F401
 from .utils.png_normalize import letterbox, letterbox_geometry, lanczos_coeffs  # noqa: F401

@@ -9,7 +9,7 @@ import contextlib
 import ctypes
 import math
 import os
-from typing import NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch.autograd import Function
@@ -1984,6 +1984,68 @@ def tile_merge(src: torch.Tensor, cfg, size: Tuple[int, int], views: int = 1, *,
     LIB.call("uh_tile_merge", v.data_ptr(), kind, int(views), B, H, W, NC, cfg.size, cfg.overlap, _p(s), _p(d), classes.data_ptr(),
              _p(p), _stream())
     return TileMerged(classes, s, d, p)
+
+
+# ----------------------------------------------------------------------------- patch training (csrc/crop.hip)
+def crop_select(labels: Sequence[torch.Tensor], words, size: int, class_mask: int, threshold: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The crop origins of utils/crop.py for int64 label planes [H,W] of any sizes: words uint32 [B,4] (r0..r3 per plane),
+    class_mask bit v set for every label value v that counts, threshold = rint(fg 2^32).
+    -> (origins int32 [B,2] = (oy, ox), counts int32 [B] = the counted pixels), both on the device."""
+    from .utils.crop import item_table
+    labels = list(labels)
+    if not labels:
+        raise ValueError("crop_select needs at least one label plane")
+    for m in labels:
+        _require_gpu(m, "labels")
+    if not 0 <= int(class_mask) < 1 << 64 or not 0 <= int(threshold) <= 1 << 32:
+        raise ValueError(f"crop_select: class_mask is a 64-bit mask and threshold lies in [0, 2^32], got {class_mask!r}, {threshold!r}")
+    table, keep = item_table(None, labels, words)
+    B, dev = len(labels), labels[0].device
+    with torch.cuda.device(dev):
+        origins = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        counts = torch.empty(B, dtype=torch.int32, device=dev)
+        ws_bytes = LIB.query("uh_crop_select_ws_bytes", B)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+        LIB.call("uh_crop_select", table.ctypes.data, B, int(size), int(class_mask), int(threshold), origins.data_ptr(),
+                 counts.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+    del keep
+    return origins, counts
+
+
+def crop_gather(images: Optional[Sequence[torch.Tensor]], labels: Optional[Sequence[torch.Tensor]], origins: torch.Tensor,
+                size: int, ld_out: Optional[int] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """[oy, oy + size) x [ox, ox + size) of every item: images [C,H,W] (fp32 or bf16, one dtype and C, read through their NHWC
+    views; a pixel stride above C is taken as it is) and / or int64 labels [H,W], origins int32 [B,2] on the device (clamped
+    into the item as they are loaded).  -> (image [B,C,size,size], channels_last memory with pixel stride ld_out (default C),
+    or None; labels int64 [B,size,size] or None).  A pure copy."""
+    from .utils.crop import item_table
+    images = list(images) if images is not None else None
+    labels = list(labels) if labels is not None else None
+    ref = images if images is not None else labels
+    if not ref or (images is not None and labels is not None and len(images) != len(labels)):
+        raise ValueError("crop_gather needs images and / or labels, one of each per item")
+    for t in (images or []) + (labels or []) + [origins]:
+        _require_gpu(t, "crop source")
+    B, dev = len(ref), ref[0].device
+    if origins.dtype != torch.int32 or tuple(origins.shape) != (B, 2) or not origins.is_contiguous():
+        raise RuntimeError(f"crop_gather expects contiguous int32 [{B},2] origins, got {origins.dtype} {tuple(origins.shape)}")
+    C, dt, out, lab = 1, UH_F32, None, None
+    if images is not None:
+        C = images[0].shape[0]
+        if any(x.dtype != images[0].dtype or x.shape[0] != C for x in images):
+            raise RuntimeError("crop_gather: the images of a batch have one dtype and one channel count")
+        dt = _dt(images[0])
+    table, keep = item_table(images, labels)
+    size = int(size)
+    ld_out = C if ld_out is None else int(ld_out)
+    with torch.cuda.device(dev):
+        if images is not None:
+            out = (torch.empty if ld_out == C else torch.zeros)((B, size, size, max(ld_out, 1)), dtype=images[0].dtype, device=dev)
+        if labels is not None:
+            lab = torch.empty((B, size, size), dtype=torch.int64, device=dev)
+        LIB.call("uh_crop_gather", table.ctypes.data, B, C, dt, size, origins.data_ptr(), _p(out), ld_out, _p(lab), _stream())
+    del keep
+    return (out[..., :C].permute(0, 3, 1, 2) if out is not None else None), lab
 
 
 # ----------------------------------------------------------------------------- contour metrics (csrc/contour_metrics.hip)

@@ -4,6 +4,7 @@
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
                              [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--elastic [SPEC]] [--surface-loss [SPEC]]
                              [--loss [SPEC]] [--ema [DECAY[,warmup=N]]] [--save-state] [--resume STATE]
+                             [--crop [SPEC]] [--tile [SPEC]]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -39,6 +40,13 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     rule receives.  checkpoint_epoch{E}.pth and model_epoch{E}.pth keep the live weights; checkpoint_epoch{E}_ema.pth and
     model_epoch{E}_ema.pth are written beside them in the same wire format (predict, evaluate and seg_main load them as
     they are).  BatchNorm running statistics are the live ones in both;
+  - --crop [SIZE[,fg=P][,classes=a+b]] (default: off; bare: "256,fg=0.5") is patch training (utils/crop.py, csrc/crop.hip): every
+    TRAINING item gives one SIZE x SIZE crop per epoch, drawn per (seed, epoch, item) and, with probability P, placed so that
+    it holds a pixel of the given classes (default: the class evaluate scores).  The training images may then differ in
+    size; each must be at least SIZE x SIZE after --scale.  The crop comes before --augment / --elastic.  Validation is
+    untouched: whole images, one size per batch.  A spec that does not fit --classes ends the command with status 2;
+  - --tile [SIZE[,overlap=N]] (default: off; bare: "512,overlap=128") runs every in-loop evaluation as the sliding-window
+    prediction of utils/tiling.py (evaluate(tile=...)): what validates a patch-trained network on images larger than its crops;
   - --save-state writes checkpoint_dir/train_state.pth at the end of every epoch (a temporary file renamed over it): model
     and optimizer state (both RMSprop buffers, the moving average and its update count), epoch, global step, lr, the
     loader's and the augmenter's seeds, and a record of the arguments that determine the run (RECORDED);
@@ -80,11 +88,14 @@ class SurfaceSpec(NamedTuple):
 
 SURFACE_BARE = "0.01,ramp=0.01"
 EMA_BARE = EmaConfig().spec()            # "0.999,warmup=10"
+CROP_BARE = "256,fg=0.5"
+TILE_BARE = "512,overlap=128"
 STATE_FILE = "train_state.pth"
 # the arguments that determine a run, as --save-state records and --resume compares them: (record key, command-line name)
 RECORDED = (("model", "--model"), ("classes", "--classes"), ("bilinear", "--bilinear"), ("batch_size", "--batch-size"),
             ("scale", "--scale"), ("amp", "--amp / --no-amp"), ("lr", "--learning-rate"), ("augment", "--augment"),
-            ("elastic", "--elastic"), ("surface", "--surface-loss"), ("ema", "--ema"), ("loss", "--loss"))
+            ("elastic", "--elastic"), ("surface", "--surface-loss"), ("ema", "--ema"), ("loss", "--loss"),
+            ("crop", "--crop"), ("tile", "--tile"))
 
 
 def parse_surface_spec(text: str) -> SurfaceSpec:
@@ -153,6 +164,22 @@ def _loss_arg(text: str):
         raise argparse.ArgumentTypeError(f"bad --loss {text!r}: {e}") from None
 
 
+def _crop_arg(text: str):
+    from .utils.crop import CropConfig
+    try:
+        return CropConfig.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"bad --crop {text!r}: {e}") from None
+
+
+def _tile_arg(text: str) -> str:
+    from .utils.tiling import parse_tile_spec
+    try:
+        return parse_tile_spec(text).spec
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"bad --tile {text!r}: {e}") from None
+
+
 def run_record(args: argparse.Namespace) -> Dict:
     """The arguments that determine what a run computes (RECORDED), specs in their canonical form, None for an option that is
     off.  ValueError for a spec that does not parse."""
@@ -163,7 +190,9 @@ def run_record(args: argparse.Namespace) -> Dict:
             "elastic": ElasticConfig.parse(args.elastic).spec() if args.elastic is not None else None,
             "surface": surface_spec_text(args.surface_loss),
             "ema": args.ema.spec() if args.ema is not None else None,
-            "loss": args.loss.spec() if getattr(args, "loss", None) is not None else None}
+            "loss": args.loss.spec() if getattr(args, "loss", None) is not None else None,
+            "crop": args.crop.spec() if getattr(args, "crop", None) is not None else None,
+            "tile": getattr(args, "tile", None)}
 
 
 def load_resume_state(args: argparse.Namespace) -> Optional[Dict]:
@@ -232,6 +261,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ema", nargs="?", const=EMA_BARE, default=None, type=_ema_arg, metavar="DECAY[,warmup=N]",
                    help="Keep an exponential moving average of the weights in the optimizer pass; evaluations run on it and "
                         f"*_ema.pth files are written beside the usual ones (bare flag: '{EMA_BARE}'; default: off)")
+    p.add_argument("--crop", nargs="?", const=CROP_BARE, default=None, type=_crop_arg, metavar="SIZE[,fg=P][,classes=a+b]",
+                   help="Patch training: one seeded SIZE x SIZE crop per training item and epoch, cut on the device; with "
+                        "probability P it holds a pixel of the given classes (default: the class evaluate scores).  The training "
+                        f"images may differ in size (bare flag: '{CROP_BARE}'; default: off)")
+    p.add_argument("--tile", nargs="?", const=TILE_BARE, default=None, type=_tile_arg, metavar="SIZE[,overlap=N]",
+                   help="Run the in-loop evaluations as the sliding-window prediction: tiles of SIZE pixels, overlap blended "
+                        f"(bare flag: '{TILE_BARE}'; default: off)")
     p.add_argument("--save-state", dest="save_state", action="store_true", default=False,
                    help=f"Write checkpoint_dir/{STATE_FILE} after every epoch: everything --resume needs (default: off)")
     p.add_argument("--resume", default=None, metavar="STATE",
@@ -275,7 +311,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
                  train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
                  augment=None, surface: Optional[SurfaceSpec] = None, elastic=None, ema=None, save_state: bool = False,
-                 resume: Optional[Dict] = None, record: Optional[Dict] = None, loss=None) -> List[Dict]:
+                 resume: Optional[Dict] = None, record: Optional[Dict] = None, loss=None, crop=None, tile=None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
@@ -289,6 +325,9 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     record returned carries the averaged model as "ema_state_dict" (TrainStepper.ema_state_dict(), on the CPU).
     `loss`: a LossConfig or a spec string; every step runs the focal + Tversky node in place of the CE + Dice pair, and the record
     gains the summed "focal" and "tversky" terms.
+    `crop`: a CropConfig, a spec string or a BatchCrop for the TRAIN loader (a config is seeded with the loader's seed, which
+    is the saved one on resume: the state file needs no key for it); the validation loader never gets one.
+    `tile`: a TileConfig or a spec string, passed to every evaluation of the loop.
     `save_state`: write checkpoint_dir/train_state.pth after every epoch, holding `record` (run_record) as its "args".
     `resume`: such a state (load_resume_state); the model must already hold its weights.  Optimizer state, lr, counters
     and the seeds are restored and the loop continues with the epoch after the saved one: only those epochs are returned."""
@@ -302,6 +341,13 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                                          seed=seed if resume is None else resume["loader_seed"], workers=workers, device=device)
     elif resume is not None:
         train_loader.seed = int(resume["loader_seed"])
+    if crop is not None:
+        from .utils.crop import BatchCrop
+        if not isinstance(crop, BatchCrop):
+            crop = BatchCrop(crop, train_loader.seed, model.n_classes)
+        train_loader.crop = crop
+        if log:
+            log(f"Training crops (seed {crop.seed}): {crop.config.spec()}")
     if augment is not None or elastic is not None:
         from .utils.augment import AugmentConfig, BatchAugment
         if isinstance(augment, BatchAugment):
@@ -330,6 +376,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
         if log:
             log(f"Resumed after epoch {resume['epoch']} (global step {global_step}, lr {lr:.6g})")
     tag = " (EMA)" if stepper.ema is not None else ""
+    tile_kw = {"tile": tile} if tile is not None else {}
     mask_values = train_set.mask_values + val_set.mask_values
     history = []
     for epoch in range(first_epoch, epochs + 1):
@@ -364,7 +411,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                     from .utils.contour_metrics import ContourMetrics, format_line
                     acc = ContourMetrics()
                 with (stepper.averaged() if stepper.ema is not None else contextlib.nullcontext()):
-                    val_score, val_post, val_min = evaluate(model, val_loader, device, amp, epoch_pred_dir, metrics=acc)  # postprocess=True
+                    val_score, val_post, val_min = evaluate(model, val_loader, device, amp, epoch_pred_dir, metrics=acc, **tile_kw)  # postprocess=True
                 lr = cosine_warm_restarts_lr(learning_rate, float(val_score))                    # scheduler.step(val_score)
                 stepper.optimizer.param_groups[0]["lr"] = lr
                 dice = (float(val_score), float(val_post), float(val_min))
@@ -435,6 +482,11 @@ def main(argv=None) -> int:
                 args.loss.for_head(args.classes)                              # against the head, before anything is loaded
             except ValueError as e:
                 raise ValueError(f"--loss: {e}") from None
+        if args.crop is not None:
+            try:
+                args.crop.for_head(args.classes)                              # likewise
+            except ValueError as e:
+                raise ValueError(f"--crop: {e}") from None
         resume = load_resume_state(args)                                      # a refused --resume needs no GPU to say so
         record = run_record(args) if (args.save_state or resume is not None) else None
     except ValueError as e:
@@ -486,7 +538,8 @@ def main(argv=None) -> int:
                            learning_rate=args.lr, amp=args.amp, checkpoint_dir=args.checkpoint_dir, seed=args.seed,
                            workers=args.workers, log=logging.info, pred_dir=args.pred_dir, metrics=args.metrics,
                            augment=augment, surface=args.surface_loss, elastic=elastic, ema=args.ema,
-                           save_state=args.save_state, resume=resume, record=record, loss=args.loss)
+                           save_state=args.save_state, resume=resume, record=record, loss=args.loss,
+                           crop=args.crop, tile=args.tile)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")

@@ -230,10 +230,14 @@ class DeviceBatchLoader:
     A dataset that does not decode to 8-bit (raw_item raises TypeError: .npy / float images) is served through ds[i] and
     the host tensors are moved to the device; that is logged once.
     `augment`: a utils.augment.BatchAugment; every batch (the host-item fallback too) is passed through it on the device
-    with the 0-based epoch number and the batch's dataset indices.  None (the default) changes nothing."""
+    with the 0-based epoch number and the batch's dataset indices.  None (the default) changes nothing.
+    `crop`: a utils.crop.BatchCrop (patch training).  A batch's raw items are then collated and prepared one decoded shape
+    (and turn parity, and scale) at a time instead of as one stack, so the items of a batch may differ in size; every prepared
+    item is cropped on the device (the host-item fallback too) and the crop batch is what `augment` receives.  None (the
+    default) changes nothing."""
 
     def __init__(self, ds, batch_size: int = 1, shuffle: bool = False, drop_last: bool = False, seed=None, workers: int = 8,
-                 device=None, prefetch: int = 2, host_rescale: bool = False, augment=None):
+                 device=None, prefetch: int = 2, host_rescale: bool = False, augment=None, crop=None):
         if batch_size < 1 or workers < 1 or prefetch < 1:
             raise ValueError("DeviceBatchLoader: batch_size, workers and prefetch must be positive")
         self.ds, self.batch_size, self.shuffle, self.drop_last = ds, int(batch_size), bool(shuffle), bool(drop_last)
@@ -245,6 +249,7 @@ class DeviceBatchLoader:
         self._switch = threading.Lock()
         self.host_rescale = bool(host_rescale)     # True: Pillow rescales in the decode threads (the earlier path; benchmarks)
         self.augment = augment
+        self.crop = crop
 
     def epoch_order(self, epoch: int) -> List[int]:
         n = len(self.ds)
@@ -283,6 +288,33 @@ class DeviceBatchLoader:
         host = [it if "image" in it else self.ds[i] for i, it in zip(idx, items)]
         return {"image": torch.stack([h["image"] for h in host]), "mask": torch.stack([h["mask"] for h in host])}
 
+    def _collate_groups(self, idx, futures):
+        """`_collate` under `crop`: the raw items of a batch grouped by what collate_raw needs equal -- decoded shape, scale
+        and, unless the images are square, turn parity -- as {'groups': [(positions in the batch, collated group)]}, or the
+        host items {'host': [ds[i]]} once the dataset has refused raw_item."""
+        items = [f.result() for f in futures]
+        if not all("image_u8" in it for it in items):
+            return {"host": [it if "image" in it else self.ds[i] for i, it in zip(idx, items)]}
+        groups = {}
+        for pos, it in enumerate(items):
+            shape = tuple(it["image_u8"].shape)
+            parity = (int(it["turns"]) & 1) if shape[0] != shape[1] else 0
+            groups.setdefault((shape, parity, float(it.get("scale", 1.0))), []).append(pos)
+        return {"groups": [(pos, collate_raw([items[p] for p in pos])) for pos in groups.values()]}
+
+    def _prepared_items(self, batch, dev):
+        """The prepared device items {'image' [C,H,W], 'mask' [H,W]} of a `_collate_groups` batch, in batch order."""
+        if "host" in batch:
+            return [{"image": h["image"].to(dev, non_blocking=True), "mask": h["mask"].to(dev, non_blocking=True)}
+                    for h in batch["host"]]
+        n = sum(len(pos) for pos, _ in batch["groups"])
+        out = [None] * n
+        for pos, raw in batch["groups"]:
+            prepared = prepare_batch_device(raw["image_u8"], raw["mask_u8"], raw["turns"], device=dev, scale=raw["scale"])
+            for j, p in enumerate(pos):
+                out[p] = {"image": prepared["image"][j], "mask": prepared["mask"][j]}
+        return out
+
     def __iter__(self):
         from concurrent.futures import ThreadPoolExecutor
         epoch = self.epoch
@@ -293,6 +325,8 @@ class DeviceBatchLoader:
         dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
         with ThreadPoolExecutor(self.workers) as items_pool, ThreadPoolExecutor(self.prefetch) as batch_pool:
             def submit(idx):
+                if self.crop is not None:
+                    return batch_pool.submit(self._collate_groups, idx, [items_pool.submit(self._raw, i) for i in idx])
                 return batch_pool.submit(self._collate, idx, [items_pool.submit(self._raw, i) for i in idx])
 
             pending = [submit(idx) for idx in batches[:self.prefetch + 1]]
@@ -305,6 +339,10 @@ class DeviceBatchLoader:
                 if nxt < len(batches):
                     pending.append(submit(batches[nxt]))
                     nxt += 1
+                if self.crop is not None:
+                    out = self.crop(self._prepared_items(batch, dev), epoch, idx)
+                    yield out if self.augment is None else self.augment(out, epoch, idx)
+                    continue
                 if "image_u8" in batch:
                     out = prepare_batch_device(batch["image_u8"], batch["mask_u8"], batch["turns"], device=dev,
                                                scale=batch["scale"])
