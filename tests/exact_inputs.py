@@ -4,6 +4,9 @@ The conv / transposed-conv / 1x1 kernels accumulate in fp32.  Where every produc
 integer times one fixed power of two) below 2^24, fp32 addition is exact in ANY order, so the result equals the float64 reference
 bit for bit: no tolerance, and a missing, doubled or misplaced term, or an intermediate kept in fewer bits, changes the output.
 
+The pixel passes (BatchNorm + ReLU, the pool and head tails, max-pool) and the recomputed stem have their own "dyadic" family and
+case classes in the second half of this file.
+
 Families (all values are exact in bf16, so one set of inputs serves the fp32 and the bf16 kernels):
   ternary  {-1, 0, +1}; for a contraction of length K the densities obey p_a * p_b <= 1100 / K, which keeps the outputs (integers)
            within +-256: bf16 stores them exactly.  `require_bf16_exact` asserts that on the reference -- a condition on the inputs.
@@ -321,3 +324,341 @@ class OutConvCase:
 @functools.lru_cache(maxsize=2)
 def outconv_case(shape, ncls, family, ref_dtype=torch.float64):
     return OutConvCase(shape, ncls, family, ref_dtype)
+
+
+# ------------------------------------------------------------------------------------------------ the dyadic family (pixel passes)
+# BatchNorm + ReLU apply / backward, the pool and head tails, max-pool and the recomputed stem are per-channel affine maps, masks,
+# 2x2 maxima and sums.  Tensors hold small integers, the per-channel coefficients are dyadic (a few bits times a power of two), so
+# every product is exact in fp32 and every term of a sum is a multiple of ONE power-of-two quantum q: while sum |terms| / q stays
+# below 2^24 (`require_exact_sum`, asserted on the float64 terms of the very case) every partial sum, in any order and through any
+# fused multiply-add, is exact -- the kernel's result has one right value.  Element-wise bf16 outputs are one rounding of it.
+SCALE_MAGS = (0.25, 0.5, 1.0, 2.0, 4.0)
+RSTDS = (0.5, 1.0, 2.0)
+HALVES = 17                    # shift and mean: k / 2 for k in -8 .. 8
+N_TOTAL = 1024                 # the SyncBN form's pixel count: a power of two that is no case's own pixel count
+
+
+def require_exact_sum(terms, q, dim, what=""):
+    """terms: the float64 terms of a reduction over `dim` (for an element-wise result: every term a kernel may form for one element,
+    stacked along `dim`).  All are multiples of the power-of-two quantum q, and per output element sum |terms| / q < 2^24: every
+    partial sum, in any order and through any fused multiply-add, is then a multiple of q below 2^24 q -- exact in fp32."""
+    t = terms / q
+    assert torch.equal(t, t.round()), f"{what}: a term is no multiple of {q}"
+    m = float(t.abs().sum(dim=dim).max())
+    assert m < F32_INT, f"{what}: sum |terms| / q = {m} reaches 2^24"
+    return m
+
+
+def dyadic_coeffs(C, g, narrow=False):
+    """-> scale, shift, mean, rstd (float64 [C]), the tuple distinct for every channel (drawn without replacement from the whole
+    set, asserted): a kernel that computes a channel with another channel's coefficients changes the output.
+    scale in +-{1/4, 1/2, 1, 2, 4}, shift and mean multiples of 1/2 in [-4, 4], rstd in {1/2, 1, 2};
+    narrow: scale in +-{1, 2}, rstd in {1, 2}, mean an integer (coarser quanta for the long sums of the stem)."""
+    mags = (1.0, 2.0) if narrow else SCALE_MAGS
+    rstds = (1.0, 2.0) if narrow else RSTDS
+    nmean = 9 if narrow else HALVES
+    radix = (len(mags), 2, HALVES, nmean, len(rstds))
+    total = 1
+    for r in radix:
+        total *= r
+    assert C <= total
+    idx = torch.randperm(total, generator=g)[:C]
+    digits = []
+    for r in radix:
+        digits.append(idx % r)
+        idx = idx // r
+    scale = torch.tensor(mags, dtype=torch.float64)[digits[0]] * (digits[1].double() * 2 - 1)
+    shift = (digits[2].double() - 8) / 2
+    mean = (digits[3].double() - 4) if narrow else (digits[3].double() - 8) / 2
+    rstd = torch.tensor(rstds, dtype=torch.float64)[digits[4]]
+    tup = torch.stack([scale, shift, mean, rstd], 1)
+    assert len(torch.unique(tup, dim=0)) == C, "the coefficient tuples must be distinct per channel"
+    assert bool((scale < 0).any()) or C < 4
+    return scale, shift, mean, rstd
+
+
+def _cv(v):
+    """[C] -> [1, C, 1, 1]"""
+    return v.view(1, -1, 1, 1)
+
+
+def relu_and_mask(y, scale, shift, dz):
+    """z = relu(y * scale + shift) and m = the gradient torch's ReLU passes for dz (0 where z == 0), float64 NCHW."""
+    t = (y * _cv(scale) + _cv(shift)).requires_grad_(True)
+    z = torch.relu(t)
+    (m,) = torch.autograd.grad(z, [t], dz)
+    return z.detach(), m
+
+
+def bn_sums(m, y, mean, rstd, what):
+    """-> xhat, sum m, sum m xhat (float64), the two sums exact in fp32 in any order (asserted)."""
+    xhat = (y - _cv(mean)) * _cv(rstd)
+    require_exact_sum(m, 1.0, (0, 2, 3), what + ": sum m")
+    require_exact_sum(m * xhat, 0.25, (0, 2, 3), what + ": sum m xhat")       # (y - mean) in halves, rstd >= 1/2
+    return xhat, m.sum((0, 2, 3)), (m * xhat).sum((0, 2, 3))
+
+
+def bn_dy(m, y, scale, mean, rstd, dgamma, dbeta, n, q_sums, what):
+    """dy = scale (m - dbeta / n - xhat dgamma / n) in float64.  q_sums: the quantum of dgamma and dbeta.  Every term a kernel may
+    form on the way -- scale m, scale dbeta / n, scale rstd dgamma / n times y and times mean -- is a multiple of
+    q = q_sums / (16 n) (scale >= 1/4, rstd >= 1/2, mean in halves), and their absolute sum stays below 2^24 q (asserted): whatever the
+    grouping (the kernels use a m + (b y + k), k = -scale dbeta / n - b mean), fp32 holds every intermediate exactly."""
+    q = q_sums / (16.0 * n)
+    b = _cv(scale * rstd * dgamma / n)
+    terms = torch.stack([(_cv(scale) * m).abs(), (_cv(scale * dbeta / n)).abs().expand_as(m), (b * y).abs(), (b * _cv(mean)).abs().expand_as(m)])
+    require_exact_sum(terms, q, 0, what + ": dy")
+    xhat = (y - _cv(mean)) * _cv(rstd)
+    return _cv(scale) * (m - _cv(dbeta) / n - xhat * _cv(dgamma) / n)
+
+
+def given_sums(C, g, unit=1.0):
+    """dgamma, dbeta of the SyncBN form: integers (times `unit`) in [-3, 3]."""
+    return (torch.randint(-3, 4, (C,), generator=g).double() * unit, torch.randint(-3, 4, (C,), generator=g).double() * unit)
+
+
+def is_pow2(n):
+    return n > 0 and n & (n - 1) == 0
+
+
+class BnCase:
+    """BatchNorm + ReLU on [B,C,H,W] (NCHW float64 references; the inputs are exact in bf16):
+        z = relu(y scale + shift);  m = dz [z > 0] (torch's ReLU gradient: 0 at z == 0, and many z are exactly 0 here);
+        sum1 = sum m, sum2 = sum m xhat, xhat = (y - mean) rstd;
+        dy = scale (m - dbeta / n - xhat dgamma / n) with GIVEN integer dgamma, dbeta and n = N_TOTAL (the SyncBN form), and --
+        `own_dy`, where the pixel count is a power of two -- with dgamma = sum2, dbeta = sum1, n = the pixel count.
+    dz: "wide" integers, or "ternary" of density p_dz where the sums of a large extent need it."""
+
+    def __init__(self, B, H, W, C, dz_family="wide", p_dz=1.0):
+        g = torch.Generator().manual_seed(_seed(B, H, W, C, 53, dz_family == "wide"))
+        self.shape, self.npix = (B, H, W, C), B * H * W
+        self.y = wide((B, C, H, W), g)
+        self.dz = wide((B, C, H, W), g) if dz_family == "wide" else ternary((B, C, H, W), p_dz, g)
+        self.scale, self.shift, self.mean, self.rstd = dyadic_coeffs(C, g)
+        self.dgamma, self.dbeta = given_sums(C, g)
+        y, dz = self.y.double(), self.dz.double()
+        self.z, self.m = relu_and_mask(y, self.scale, self.shift, dz)
+        assert bool((self.z == 0).any()) and bool((self.z > 0).any())
+        _, self.sum1, self.sum2 = bn_sums(self.m, y, self.mean, self.rstd, "BnCase")
+        self.dy = bn_dy(self.m, y, self.scale, self.mean, self.rstd, self.dgamma, self.dbeta, N_TOTAL, 1.0, "BnCase, given sums")
+        self.own_dy = None
+        if is_pow2(self.npix):
+            self.own_dy = bn_dy(self.m, y, self.scale, self.mean, self.rstd, self.sum2, self.sum1, self.npix, 0.25, "BnCase, own sums")
+
+    def coeffs(self):
+        return self.scale, self.shift, self.mean, self.rstd
+
+
+@functools.lru_cache(maxsize=4)
+def bn_case(B, H, W, C, dz_family="wide", p_dz=1.0):
+    return BnCase(B, H, W, C, dz_family, p_dz)
+
+
+def first_max_route(zq, dpool):
+    """pooled = MaxPool2d(2) of zq and the gradient of zq under dpool: torch routes it to the FIRST maximum of a window in
+    (0,0), (0,1), (1,0), (1,1) order; rows / columns past 2 floor(H / 2) get nothing."""
+    zl = zq.clone().requires_grad_(True)
+    pooled = F.max_pool2d(zl, 2)
+    (route,) = torch.autograd.grad(pooled, [zl], dpool)
+    return pooled.detach(), route
+
+
+class PoolTailCase:
+    """BnCase with z also max-pooled 2x2.  Backward takes dskip (optional) plus dpool routed to the first maximum of the window:
+    dz = dskip + route(dpool), never stored by the fused kernels.  z holds quarters in [0, 64]: ties are common, all-zero windows
+    included (asserted).  The STORED z decides the maximum, so the references round it to the tensor dtype first (quarters up to 64
+    are exact in bf16: the rounding of z itself is exercised by the stem's wide family): `refs(dtype, skip)`.  Also serves uh_maxpool2_fwd / _bwd on their own (x = the stored z; H and W
+    may then be odd).  sums=False: element-wise outputs only (an extent whose sums would need narrower inputs than its dy)."""
+
+    def __init__(self, B, H, W, C, dz_family="wide", p_dz=1.0, sums=True):
+        g = torch.Generator().manual_seed(_seed(B, H, W, C, 59, dz_family == "wide"))
+        self.shape, self.npix, self.sums = (B, H, W, C), B * H * W, sums
+        draw = (lambda shp: wide(shp, g)) if dz_family == "wide" else (lambda shp: ternary(shp, p_dz, g))
+        self.y = wide((B, C, H, W), g)
+        self.dskip, self.dpool = draw((B, C, H, W)), draw((B, C, H // 2, W // 2))
+        self.scale, self.shift, self.mean, self.rstd = dyadic_coeffs(C, g)
+        if self.npix < 200 and not is_pow2(self.npix) and C >= 2:
+            # two means that are halves but NO bf16 numbers (nine bits): the bf16 reduce kernel sums m (y - pivot) around pivot =
+            # mean rounded to bf16 and corrects by (mean - pivot) sum m afterwards -- with every mean a bf16 number that term is 0.
+            # (small extents only, and none whose own sums feed an exact dy: |xhat| grows tenfold, and with it the sums; the conditions
+            # are asserted as everywhere)
+            self.mean[0], self.mean[1] = 128.5, -200.5
+            assert not torch.equal(self.mean.float().bfloat16().double(), self.mean)
+        self.dgamma, self.dbeta = given_sums(C, g)
+        self.z, _ = relu_and_mask(self.y.double(), self.scale, self.shift, torch.zeros(B, C, H, W, dtype=torch.float64))
+        self._refs = {}
+
+    def coeffs(self):
+        return self.scale, self.shift, self.mean, self.rstd
+
+    def refs(self, dtype, skip=True):
+        """-> dict(zq, pooled, route, dz, m, sum1, sum2, dy[, own_dy]) in float64; zq = z as stored in `dtype`."""
+        key = (dtype, skip)
+        if key in self._refs:
+            return self._refs[key]
+        y = self.y.double()
+        zq = expected(self.z, dtype).double()
+        pooled, route = first_max_route(zq, self.dpool.double())
+        win = F.unfold(zq, 2, stride=2)                                       # [B, C * 4, windows]
+        win = win.view(zq.shape[0], zq.shape[1], 4, -1)
+        ties = (win == win.max(2, keepdim=True).values).sum(2)
+        if win.numel() >= 400:                                                # (the few windows of a tiny extent need not hold one)
+            assert bool((ties > 1).any()) and bool((win.max(2).values == 0).any()), "the case must hold ties and all-zero windows"
+        dz = route + (self.dskip.double() if skip else 0.0)
+        assert float(dz.abs().max()) <= BF16_INT                              # dz = round_T(dskip + dpool): nothing to round
+        _, m = relu_and_mask(y, self.scale, self.shift, dz)
+        r = dict(zq=zq, pooled=pooled, route=route, dz=dz, m=m)
+        if self.sums:
+            _, r["sum1"], r["sum2"] = bn_sums(m, y, self.mean, self.rstd, "PoolTailCase")
+        r["dy"] = bn_dy(m, y, self.scale, self.mean, self.rstd, self.dgamma, self.dbeta, N_TOTAL, 1.0, "PoolTailCase, given sums")
+        if self.sums and is_pow2(self.npix):
+            r["own_dy"] = bn_dy(m, y, self.scale, self.mean, self.rstd, r["sum2"], r["sum1"], self.npix, 0.25, "PoolTailCase, own sums")
+        self._refs[key] = r
+        return r
+
+
+@functools.lru_cache(maxsize=4)
+def pool_tail_case(B, H, W, C, dz_family="wide", p_dz=1.0, sums=True):
+    return PoolTailCase(B, H, W, C, dz_family, p_dz, sums)
+
+
+class HeadTailCase:
+    """BnCase followed by the 1x1 head: logits = head_w . zq + bias (fp32) with zq = z as it would have been stored in the tensor
+    dtype, never written.  Backward takes dlogits: dz = dlogits . head_w, and yields dhead_w = sum dlogits (x) zq, dhead_b = sum dlogits
+    beside the BatchNorm sums and dy.  head_w, bias: wide integers; dlogits: dense +-1, so |dz| <= 15 ncls is exact in bf16 (the
+    kernels round dz to the tensor dtype as the unfused path stores it: nothing to round here, asserted).  w_family "ternary": a
+    head_w in {-1, 0, 1}, where the sums are to be used as dgamma / dbeta of an exact dy (the in-kernel finalize)."""
+
+    def __init__(self, B, H, W, C, ncls, w_family="wide"):
+        g = torch.Generator().manual_seed(_seed(B, H, W, C, ncls, 61, w_family == "wide"))
+        self.shape, self.ncls, self.npix = (B, H, W, C), ncls, B * H * W
+        self.y = wide((B, C, H, W), g)
+        self.head_w = wide((ncls, C, 1, 1), g) if w_family == "wide" else ternary((ncls, C, 1, 1), 0.5, g)
+        self.head_b = wide((ncls,), g)
+        self.dlogits = ternary((B, ncls, H, W), 1.0, g)
+        self.scale, self.shift, self.mean, self.rstd = dyadic_coeffs(C, g)
+        self.dgamma, self.dbeta = given_sums(C, g)
+        self.z, _ = relu_and_mask(self.y.double(), self.scale, self.shift, torch.zeros(B, C, H, W, dtype=torch.float64))
+        self._refs = {}
+
+    def coeffs(self):
+        return self.scale, self.shift, self.mean, self.rstd
+
+    def refs(self, dtype):
+        if dtype in self._refs:
+            return self._refs[dtype]
+        y, w, b, dl = self.y.double(), self.head_w.double(), self.head_b.double(), self.dlogits.double()
+        zq = expected(self.z, dtype).double().requires_grad_(True)
+        wl, bl = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        logits = F.conv2d(zq, wl, bl)
+        dz, dhw, dhb = torch.autograd.grad(logits, [zq, wl, bl], dl)
+        zq = zq.detach()
+        # logits: C products zq w and the bias, in quarters; dhead_w: one product per pixel, in quarters; dhead_b: +-1 per pixel
+        require_exact_sum(torch.cat([zq.unsqueeze(1) * w.view(1, -1, zq.shape[1], 1, 1), b.view(1, -1, 1, 1, 1).expand(zq.shape[0], -1, 1, *zq.shape[2:])], 2),
+                          0.25, 2, "HeadTailCase: logits")
+        require_exact_sum(dl.unsqueeze(2) * zq.unsqueeze(1), 0.25, (0, 3, 4), "HeadTailCase: dhead_w")
+        assert self.npix < F32_INT and float(dz.abs().max()) <= BF16_INT
+        _, m = relu_and_mask(y, self.scale, self.shift, dz)
+        _, sum1, sum2 = bn_sums(m, y, self.mean, self.rstd, "HeadTailCase")
+        r = dict(zq=zq, logits=logits.detach(), dz=dz, m=m, dhead_w=dhw.view(self.ncls, -1), dhead_b=dhb, sum1=sum1, sum2=sum2)
+        r["dy"] = bn_dy(m, y, self.scale, self.mean, self.rstd, self.dgamma, self.dbeta, N_TOTAL, 1.0, "HeadTailCase, given sums")
+        if is_pow2(self.npix):
+            r["own_dy"] = bn_dy(m, y, self.scale, self.mean, self.rstd, sum2, sum1, self.npix, 0.25, "HeadTailCase, own sums")
+        self._refs[dtype] = r
+        return r
+
+
+@functools.lru_cache(maxsize=4)
+def head_tail_case(B, H, W, C, ncls, w_family="wide"):
+    return HeadTailCase(B, H, W, C, ncls, w_family)
+
+
+STEM_C = 64
+STEM_UNIT = 256.0              # dgamma, dbeta of the stem: integers that are multiples of N_TOTAL / 4, so dgamma / n is in quarters
+
+
+def stem_dy(m, yq, scale, mean, rstd, dgamma, dbeta, n):
+    """The stem's dy = scale (m - dbeta / n - xhat dgamma / n), float64, BEFORE its rounding to bf16; the terms checked as in bn_dy
+    with the narrow coefficients' quanta: scale, rstd >= 1, mean an integer, dgamma / n and dbeta / n in quarters -> q = 1/4."""
+    b = _cv(scale * rstd * dgamma / n)
+    terms = torch.stack([(_cv(scale) * m).abs(), (_cv(scale * dbeta / n)).abs().expand_as(m), (b * yq).abs(), (b * _cv(mean)).abs().expand_as(m)])
+    require_exact_sum(terms, 0.25, 0, "StemCase: dy")
+    xhat = (yq - _cv(mean)) * _cv(rstd)
+    return _cv(scale) * (m - _cv(dbeta) / n - xhat * _cv(dgamma) / n)
+
+
+def stem_dw(dyq, x):
+    """dw [64, 1, 3, 3] = sum over pixels of dyq (x) x (the filter gradient of a padded 3x3 conv), float64."""
+    w0 = torch.zeros(STEM_C, 1, 3, 3, dtype=torch.float64, requires_grad=True)
+    (dw,) = torch.autograd.grad(F.conv2d(x, w0, padding=1), [w0], dyq)
+    return dw
+
+
+class StemCase:
+    """The recomputed stem: x [B,1,H,W] and w [64,1,3,3] hold integers, y = conv(x, w) is exact in fp32 and the kernel rounds it to
+    bf16 BY DESIGN (as the stored path stores it): yq = to_bf16(y), the reference rounds in the same place.  Then as BnCase on yq;
+    dy is rounded to bf16 before dw = sum dy (x) x, again by design and again in the reference.
+      "ternary"  x, w in {-1, 0, 1}: |y| <= 9, no rounding occurs; dz wide, the full coefficient set for z and the sums.
+      "wide"     x, w in [-15, 15]: |y| up to 2025, the rounding of y is exercised; dz ternary.
+    The sums run over every pixel of the image, so the inputs are narrowed with the pixel count until the conditions hold
+    (asserted, never assumed): dz gets sparser, and the backward-weights half uses the narrow coefficient set (dyadic_coeffs) with
+    dgamma, dbeta multiples of STEM_UNIT = N_TOTAL / 4 -- dy is then in quarters, and sum |dyq x| * 4 < 2^24 per filter element.
+    Where even that fails dgamma, dbeta shrink to one unit, then (the wide family on a large image: |xhat| ~ 500 on every pixel) to 0:
+    dy = scale m is then as sparse as dz; the small shapes keep the xhat term."""
+
+    def __init__(self, B, H, W, family):
+        g = torch.Generator().manual_seed(_seed(B, H, W, 67, family == "wide"))
+        self.shape, self.family, self.npix = (B, H, W), family, B * H * W
+        n = self.npix
+        if family == "ternary":
+            self.x, self.w = ternary((B, 1, H, W), 0.75, g), ternary((STEM_C, 1, 3, 3), 0.75, g)
+            self.dz = wide((B, STEM_C, H, W), g) if n <= 4096 else ternary((B, STEM_C, H, W), min(1.0, 65536.0 / n), g)
+        elif family == "wide":
+            self.x, self.w = wide((B, 1, H, W), g), wide((STEM_C, 1, 3, 3), g)
+            self.dz = ternary((B, STEM_C, H, W), min(1.0, 1024.0 / n), g)
+        else:
+            raise ValueError(family)
+        x, w, dz = self.x.double(), self.w.double(), self.dz.double()
+        self.y = F.conv2d(x, w, padding=1)
+        assert float(self.y.abs().max()) < F32_INT
+        self.yq = to_bf16(self.y).double()
+        if family == "ternary":
+            assert torch.equal(self.yq, self.y)
+        else:
+            # |y| has a standard deviation of 3 * 80: about a third lies past 256, where every second integer or more is rounded
+            assert float((self.yq != self.y).double().mean()) > 0.1, "the wide family must exercise the rounding of y"
+        # forward and the BatchNorm sums: the full coefficient set
+        self.scale, self.shift, self.mean, self.rstd = dyadic_coeffs(STEM_C, g)
+        self.z, self.m = relu_and_mask(self.yq, self.scale, self.shift, dz)
+        assert bool((self.z > 0).any()) and (family == "wide" or bool((self.z == 0).any()))
+        _, self.sum1, self.sum2 = bn_sums(self.m, self.yq, self.mean, self.rstd, "StemCase")
+        # backward-weights: the narrow set
+        self.wg_scale, self.wg_shift, self.wg_mean, self.wg_rstd = dyadic_coeffs(STEM_C, g, narrow=True)
+        self.dgamma, self.dbeta = given_sums(STEM_C, g, STEM_UNIT)
+        _, mw = relu_and_mask(self.yq, self.wg_scale, self.wg_shift, dz)
+        for attempt in (0, 1, 2):
+            self.dy = stem_dy(mw, self.yq, self.wg_scale, self.wg_mean, self.wg_rstd, self.dgamma, self.dbeta, N_TOTAL)
+            self.dyq = to_bf16(self.dy).double()
+            xw = F.unfold(x, 3, padding=1).view(B, 1, 9, H, W)                # the nine shifted images
+            budget = float(torch.einsum("bchw,bkhw->ck", self.dyq.abs() * 4, xw[:, 0].abs()).max())
+            if budget < F32_INT:
+                break
+            assert attempt < 2, f"StemCase: sum |dyq x| * 4 = {budget} reaches 2^24 even with dy = scale m"
+            if attempt == 0:                                                  # one unit at the most, then none
+                self.dgamma, self.dbeta = self.dgamma.sign() * STEM_UNIT, self.dbeta.sign() * STEM_UNIT
+            else:
+                self.dgamma, self.dbeta = torch.zeros(STEM_C, dtype=torch.float64), torch.zeros(STEM_C, dtype=torch.float64)
+        t = self.dyq * 4
+        assert torch.equal(t, t.round())
+        self.dw = stem_dw(self.dyq, x)
+        assert bool((self.dw != 0).any())
+
+    def coeffs(self):
+        return self.scale, self.shift, self.mean, self.rstd
+
+    def wg_coeffs(self):
+        return self.wg_scale, self.wg_shift, self.wg_mean, self.wg_rstd
+
+
+@functools.lru_cache(maxsize=4)
+def stem_case(B, H, W, family):
+    return StemCase(B, H, W, family)

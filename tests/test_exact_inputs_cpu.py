@@ -177,3 +177,229 @@ def test_the_comparator_counts_a_nan_and_refuses_another_dtype():
     assert "(0, 1, 0, 2)" in E.mismatches(b, a)
     with pytest.raises(AssertionError):
         E.mismatches(a.bfloat16(), a)
+
+
+# ================================================================================================ the dyadic family (pixel passes)
+# tests/test_gpu_exact_pixel.py: (a) every case class meets its conditions at every shape that file runs (the builders assert them on
+# the float64 terms; here they are built, and the inputs are shown to be exact in bf16); (b) float32 sums in two orders give the
+# float64 sums; (c) each mutation of the reference a subtly wrong kernel would amount to changes a compared value.
+import test_gpu_exact_pixel as P  # noqa: E402
+
+PIXEL_SHAPES = sorted({k[:4] for k in P.FORMS})
+SMALL = (2, 6, 10, 24)
+
+
+def _ids(v):
+    return "x".join(map(str, v)) if isinstance(v, tuple) else None
+
+
+def _dy(m, y, scale, mean, rstd, dgamma, dbeta, n):
+    v = E._cv
+    return v(scale) * (m - v(dbeta) / n - (y - v(mean)) * v(rstd) * v(dgamma) / n)
+
+
+def _differs(a, b):
+    return E.mismatches(a, b) is not None
+
+
+@pytest.mark.parametrize("shape", [s for s in PIXEL_SHAPES if s not in P.ELEMENTWISE_ONLY], ids=_ids)
+def test_bn_cases_meet_their_conditions(shape):
+    c = E.bn_case(*P._case_args(shape))              # asserts: distinct coefficient tuples, order-free sums, every term of dy exact
+    assert _bf16_holds(c.y, c.dz, *(v.float() for v in c.coeffs()), c.dgamma.float(), c.dbeta.float())
+    assert (c.own_dy is not None) == E.is_pow2(c.npix)
+    assert E.N_TOTAL != c.npix and E.is_pow2(E.N_TOTAL)
+    for v in (c.z, c.dy, c.sum1, c.sum2):
+        assert torch.equal(v.float().double(), v)    # fp32 holds the exact value: bf16 is ONE rounding of it
+
+
+@pytest.mark.parametrize("shape", PIXEL_SHAPES, ids=_ids)
+def test_pool_tail_cases_meet_their_conditions(shape):
+    c = P._pool_case(shape)
+    assert c.sums == (shape not in P.ELEMENTWISE_ONLY)
+    assert _bf16_holds(c.y, c.dskip, c.dpool)
+    dtypes = [dt for dt in (F32, BF16) if (*shape, dt) in P.FORMS]
+    for dt in dtypes:
+        for skip in ((True, False) if c.sums else (True,)):
+            r = c.refs(dt, skip)                     # asserts: ties and all-zero windows, |dz| exact in bf16, sums, dy
+            assert torch.equal(E.expected(r["dz"], dt).double(), r["dz"])
+            assert ("own_dy" in r) == (c.sums and E.is_pow2(c.npix))
+            assert torch.equal(r["zq"], c.z)         # z <= 4 * 15 + 4 in quarters: bf16 stores it exactly, the maxima are the same
+
+
+@pytest.mark.parametrize("shape,ncls,dtype,w_family", P.HEAD_CASES + P.PITCH_HEAD_CASES[-1:], ids=lambda v: _ids(v) if isinstance(v, tuple) else str(v).replace("torch.", ""))
+def test_head_tail_cases_meet_their_conditions(shape, ncls, dtype, w_family):
+    c = E.head_tail_case(*shape, ncls, w_family)
+    assert _bf16_holds(c.y, c.head_w, c.head_b, c.dlogits)
+    r = c.refs(dtype)                                # asserts: logits, dhead_w, the sums and dy exact; |dz| exact in bf16
+    assert ("own_dy" in r) == E.is_pow2(c.npix)
+    assert bool((r["logits"] != 0).any()) and bool((r["dhead_w"] != 0).any())
+    assert torch.equal(r["zq"], c.z)                 # (quarters up to 64: the stored activation is exact in bf16 too)
+
+
+@pytest.mark.parametrize("shape", P.STEM_SHAPES, ids=_ids)
+@pytest.mark.parametrize("family", ["ternary", "wide"])
+def test_stem_cases_meet_their_conditions(family, shape):
+    c = E.stem_case(*shape, family)                  # asserts: y exact, the rounding of y exercised (wide), sums, dy terms, dw budget
+    assert _bf16_holds(c.x, c.w, c.dz)
+    assert float(c.y.abs().max()) <= (9 if family == "ternary" else 2025)
+    assert E.is_pow2(E.N_TOTAL) and torch.equal(c.dgamma, c.dgamma.round()) and torch.equal(c.dbeta, c.dbeta.round())
+    if c.npix < 4096:
+        assert bool((c.dgamma != 0).any()) and bool((c.dbeta != 0).any())      # the small shapes keep the xhat term of dy
+    if family == "wide" and bool((c.dgamma != 0).any()):
+        assert _differs(c.dyq, c.dy)                 # ... and the rounding of dy
+    assert torch.equal(c.dw.float().double(), c.dw)
+    if shape == (1, 513, 513):
+        assert P._tiles(*shape) == 1089
+
+
+def test_float32_sums_in_any_order_equal_the_float64_sums():
+    c = E.bn_case(*P._case_args(SMALL))
+    xhat = (c.y.double() - E._cv(c.mean)) * E._cv(c.rstd)
+    for terms, want in ((c.m, c.sum1), (c.m * xhat, c.sum2)):
+        t = terms.float().permute(1, 0, 2, 3).reshape(terms.shape[1], -1)
+        fwd, rev = torch.zeros(t.shape[0]), torch.zeros(t.shape[0])
+        for i in range(t.shape[1]):                  # serial float32 accumulation, first to last and last to first
+            fwd += t[:, i]
+            rev += t[:, t.shape[1] - 1 - i]
+        assert torch.equal(fwd.double(), want) and torch.equal(rev.double(), want) and torch.equal(t.sum(1).double(), want)
+
+
+def _mutations(y, dz, coeffs, dgamma, dbeta, n, dtypes):
+    """Shared by the four case classes: y, dz float64 NCHW.  Each wrong reference changes a compared value."""
+    scale, shift, mean, rstd = coeffs
+    z, m = E.relu_and_mask(y, scale, shift, dz)
+    xhat = (y - E._cv(mean)) * E._cv(rstd)
+    sum1, sum2 = m.sum((0, 2, 3)), (m * xhat).sum((0, 2, 3))
+    dy = _dy(m, y, scale, mean, rstd, dgamma, dbeta, n)
+    # one pixel dropped from a sum
+    at = tuple((m * xhat != 0).nonzero()[0].tolist())
+    drop1, drop2 = sum1.clone(), sum2.clone()
+    drop1[at[1]] -= m[at]
+    drop2[at[1]] -= (m * xhat)[at]
+    assert _differs(drop1, sum1) and _differs(drop2, sum2)
+    assert _differs(drop1.float(), sum1.float()) and _differs(drop2.float(), sum2.float())          # ... and in the finalized fp32 values
+    # >= in place of > in the mask: torch's ReLU passes nothing at z == 0
+    t = y * E._cv(scale) + E._cv(shift)
+    m_ge = dz * (t >= 0)
+    assert bool(((t == 0) & (dz != 0)).any()) and _differs(m_ge, m)
+    assert _differs(m_ge.sum((0, 2, 3)), sum1)
+    for dt in dtypes:
+        assert _differs(E.expected(_dy(m_ge, y, scale, mean, rstd, dgamma, dbeta, n), dt), E.expected(dy, dt))
+    # channel c computed with channel c + 8's coefficients (a hoisted coefficient group that is not the thread's own)
+    C = y.shape[1]
+    roll = (torch.arange(C) + 8) % C
+    z_w = torch.relu(y * E._cv(scale[roll]) + E._cv(shift[roll]))
+    m_w = E.relu_and_mask(y, scale[roll], shift[roll], dz)[1]
+    for dt in dtypes:
+        assert _differs(E.expected(z_w, dt), E.expected(z, dt))
+        assert _differs(E.expected(_dy(m, y, scale[roll], mean[roll], rstd[roll], dgamma, dbeta, n), dt), E.expected(dy, dt))
+    assert _differs(m_w.sum((0, 2, 3)), sum1)
+    assert _differs((m * (y - E._cv(mean[roll])) * E._cv(rstd[roll])).sum((0, 2, 3)), sum2)
+    # an element-wise result passed through fp16 (11 bits): dy holds 1 / (16 n) steps
+    if F32 in dtypes:
+        assert _differs(dy.float().half().float(), dy.float())
+    return z, m, dy
+
+
+def test_bn_case_mutations_fail():
+    c = E.bn_case(*P._case_args(SMALL))
+    z, m, dy = _mutations(c.y.double(), c.dz.double(), c.coeffs(), c.dgamma, c.dbeta, E.N_TOTAL, (F32, BF16))
+    assert torch.equal(z, c.z) and torch.equal(m, c.m) and torch.equal(dy, c.dy)
+    # the SyncBN form must use n_total, not the pixel count
+    assert _differs(E.expected(_dy(m, c.y.double(), c.scale, c.mean, c.rstd, c.dgamma, c.dbeta, c.npix), F32), E.expected(c.dy, F32))
+
+
+def _one_hot_route(zq, dpool, last):
+    """route(dpool) to the first (torch's rule) or to the LAST maximum of each 2x2 window, without autograd."""
+    B, C, H, W = zq.shape
+    win = F.unfold(zq, 2, stride=2).view(B, C, 4, -1)
+    eq = win == win.max(2, keepdim=True).values
+    if last:
+        eq = eq.flip(2)
+    hot = eq & (eq.double().cumsum(2) == 1)
+    if last:
+        hot = hot.flip(2)
+    g = hot.double() * dpool.reshape(B, C, 1, -1)
+    out = torch.zeros_like(zq)
+    out[:, :, :H // 2 * 2, :W // 2 * 2] = F.fold(g.view(B, C * 4, -1), (H // 2 * 2, W // 2 * 2), 2, stride=2)
+    return out
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=G._name)
+def test_pool_tail_case_mutations_fail(dtype):
+    c = P._pool_case(SMALL)
+    r = c.refs(dtype, True)
+    z, m, dy = _mutations(c.y.double(), r["dz"], c.coeffs(), c.dgamma, c.dbeta, E.N_TOTAL, (dtype,))
+    assert torch.equal(m, r["m"]) and torch.equal(dy, r["dy"])
+    # the last maximum in place of the first: torch's own routing is the first
+    dpool = c.dpool.double()
+    assert torch.equal(_one_hot_route(r["zq"], dpool, False), r["route"])
+    last = _one_hot_route(r["zq"], dpool, True)
+    assert _differs(last, r["route"])
+    dz_last = last + c.dskip.double()
+    assert _differs(E.expected(dz_last, dtype), E.expected(r["dz"], dtype))                         # uh_maxpool2_bwd's dx
+    m_last = E.relu_and_mask(c.y.double(), c.scale, c.shift, dz_last)[1]
+    # (tied positive maxima share y, hence the mask and xhat: the per-channel SUMS cannot see which one was taken -- dx and dy do)
+    assert not _differs(m_last.sum((0, 2, 3)), r["sum1"])
+    assert _differs(E.expected(_dy(m_last, c.y.double(), c.scale, c.mean, c.rstd, c.dgamma, c.dbeta, E.N_TOTAL), dtype), E.expected(r["dy"], dtype))
+    # the odd extent of the stand-alone max-pool: the last row and column get the skip gradient only
+    odd = P._pool_case((1, 5, 5, 3)).refs(dtype, False)
+    assert bool((odd["dz"][:, :, 4] == 0).all()) and bool((odd["dz"][:, :, :, 4] == 0).all()) and bool((odd["dz"] != 0).any())
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=G._name)
+def test_head_tail_case_mutations_fail(dtype):
+    C = 8 * P._vec(dtype)
+    c = E.head_tail_case(2, 6, 10, C, 3, "wide")
+    r = c.refs(dtype)
+    z, m, dy = _mutations(c.y.double(), r["dz"], c.coeffs(), c.dgamma, c.dbeta, E.N_TOTAL, (dtype,))
+    assert torch.equal(m, r["m"]) and torch.equal(dy, r["dy"])
+    w, dl = c.head_w.double(), c.dlogits.double()
+    # one pixel dropped from the head's sums
+    at = tuple((r["zq"] != 0).nonzero()[0].tolist())
+    dhw = r["dhead_w"].clone()
+    dhw[:, at[1]] -= dl[at[0], :, at[2], at[3]] * r["zq"][at]
+    assert _differs(dhw.float(), r["dhead_w"].float())
+    dhb = r["dhead_b"] - dl[0, :, 0, 0]
+    assert _differs(dhb.float(), r["dhead_b"].float())
+    # channel c with channel c + 8's coefficients, seen through the logits
+    roll = (torch.arange(C) + 8) % C
+    z_w = E.expected(torch.relu(c.y.double() * E._cv(c.scale[roll]) + E._cv(c.shift[roll])), dtype).double()
+    assert _differs(F.conv2d(z_w, w, c.head_b.double()).float(), r["logits"].float())
+    # one product dropped from one logit
+    lg = r["logits"].clone()
+    lg[at[0], :, at[2], at[3]] -= w[:, at[1], 0, 0] * r["zq"][at]
+    assert bool((w[:, at[1], 0, 0] != 0).any()) and _differs(lg.float(), r["logits"].float())
+
+
+@pytest.mark.parametrize("family", ["ternary", "wide"])
+def test_stem_case_mutations_fail(family):
+    shape = (2, 7, 40)
+    c = E.stem_case(*shape, family)
+    assert bool((c.dgamma != 0).any())
+    z, m, dy = _mutations(c.yq, c.dz.double(), c.coeffs(), c.dgamma, c.dbeta, E.N_TOTAL, (BF16,))
+    assert torch.equal(z, c.z) and torch.equal(m, c.m)
+    x = c.x.double()
+    # one pixel dropped from the filter gradient
+    at = tuple((c.dyq != 0).nonzero()[0].tolist())
+    hole = c.dyq.clone()
+    hole[at] = 0
+    assert _differs(E.stem_dw(hole, x).float(), c.dw.float())
+    # >= in the mask and channel c + 8's coefficients, seen through dw
+    ws, wsh, wm, wr = c.wg_coeffs()
+    t = c.yq * E._cv(ws) + E._cv(wsh)
+    m_ge = c.dz.double() * (t >= 0)
+    roll = (torch.arange(E.STEM_C) + 8) % E.STEM_C
+    mw = E.relu_and_mask(c.yq, ws, wsh, c.dz.double())[1]
+    for wrong in (_dy(m_ge, c.yq, ws, wm, wr, c.dgamma, c.dbeta, E.N_TOTAL), _dy(mw, c.yq, ws[roll], wm[roll], wr[roll], c.dgamma, c.dbeta, E.N_TOTAL)):
+        assert _differs(E.stem_dw(E.to_bf16(wrong).double(), x).float(), c.dw.float())
+    if family == "wide":
+        # y not rounded to bf16 before BatchNorm
+        z_raw = torch.relu(c.y * E._cv(c.scale) + E._cv(c.shift))
+        assert _differs(E.to_bf16(z_raw), E.to_bf16(c.z))
+        m_raw = E.relu_and_mask(c.y, c.scale, c.shift, c.dz.double())[1]
+        assert _differs((m_raw * (c.y - E._cv(c.mean)) * E._cv(c.rstd)).sum((0, 2, 3)), c.sum2)
+        # dy not rounded to bf16 before the contraction
+        assert _differs(E.stem_dw(c.dy, x).float(), c.dw.float())
+        # dy passed through fp16 on its way to bf16 (a double rounding)
+        assert _differs(E.stem_dw(c.dy.float().half().float().bfloat16().double(), x).float(), c.dw.float())

@@ -14,8 +14,12 @@ Where a kernel rounds by design the inputs are narrowed, never the comparison:
     power-of-two scale per workgroup block): integers survive while every partial is below 2048, so those plans get a dense +-1 x
     and a ternary dy with fewer than 2048 non-zeros per output channel (asserted), which bounds every subset sum;
   * bf16x3 drops the low x low product: one operand of each product is ternary, so that term is zero.
-Not covered here: the BatchNorm statistics of the conv epilogue (divisions; test_gpu_ops.py, test_gpu_bnsum.py), the narrow entry
-points (held bit for bit to the padded form there), tensors past 2 GiB (forward code 5, test_gpu_large.py), loss and optimizer."""
+The pixel passes (BatchNorm + ReLU apply / backward, the pool and head tails, max-pool) and the recomputed stem (uh_stem_*) are
+held to float64 in the same way, on the dyadic family, by test_gpu_exact_pixel.py, which also calls them with pixel pitches.
+Not covered here or there: the BatchNorm statistics of the conv epilogue (divisions; test_gpu_ops.py, test_gpu_bnsum.py; the
+stem's statistics rows have a derived bound in test_gpu_exact_pixel.py), the bilinear pair (weights that are no dyadic numbers:
+test_gpu_ops.py, and pitched against dense calls in test_gpu_exact_pixel.py), the narrow entry points (held bit for bit to the
+padded form there), tensors past 2 GiB (forward code 5, test_gpu_large.py), loss and optimizer."""
 import ctypes
 
 import pytest

@@ -2,6 +2,9 @@
 at (9bd533e, before their entry points shared one launch plan), in every launch form: scalar, 16-byte channel groups with and
 without hoisted coefficients, grids below and at the cap, every rung of the class / lanes-per-pixel ladder.  The cases and the
 record's format are those of tests/golden/make_pixel_pass_forms.py, which this file replays.
+Eight digests of the record are newer: `up`, `up_dx` and `up_dx_ptr` of flat.fp32.c3 and flat.bf16.c64.unaligned and `up_dx`, `up_dx_ptr`
+of flat.bf16.c12 -- the one-channel forms of the bilinear pair, which were given the arithmetic of the 16-byte forms (they differed from
+them by a bf16 ulp now and then: tests/test_gpu_exact_pixel.py) and were recorded again, twice, with every other digest unchanged.
 
 Beside the replay, every case asks uh_pixel_pass_plan for the form its calls take and requires the one it was chosen for, so
 that a shape which falls off its branch fails instead of passing trivially (host only: that part needs no GPU)."""

@@ -2,7 +2,8 @@
 recomputation on the matrix pipe: csrc/stem_mfma.hip).  Same roundings as the stored-output path (y rounded to bf16 before
 BatchNorm, dy before the contraction); the MFMA adds the nine products of a conv output in its own order, so y may differ in
 the last fp32 bit = one bf16 ulp on about one element in 10^4, and the sums are formed in another order: everything agrees
-with the stored path to bf16 / fp32 round-off, nothing more is claimed."""
+with the stored path to bf16 / fp32 round-off, nothing more is claimed here.  The four uh_stem_* entry points are held to float64 bit
+for bit -- more than 1024 tiles, pixel pitches and a first tile too small for the (8, 8) pivot included -- by test_gpu_exact_pixel.py."""
 import pytest
 import torch
 

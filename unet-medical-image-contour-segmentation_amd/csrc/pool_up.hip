@@ -122,6 +122,36 @@ __device__ __forceinline__ UpCoord up_coord(int dst, float scale, int in) {
     return u;
 }
 
+// up_coord leaves the rounding of l1 = scale * dst - i0 to the compiler's contraction, and the two forward kernels came out
+// differently: upsample2x_fwd_rows_kernel (the 16-byte form, every instantiation) subtracts i0 from the ROUNDED product for its
+// vertical weights and fuses product and subtraction for its horizontal ones; the one-channel form fused both.  A weight then
+// differed in its last bit, and a channel slice off the 16-byte grid did not get the bits of the dense call.  The one-channel form
+// now spells out the rows kernel's two roundings (the rows kernel itself, the hot one, keeps its code as compiled);
+// tests/test_gpu_exact_pixel.py holds the two forms to each other bit for bit.
+__device__ __forceinline__ UpCoord up_coord_plain(int dst, float scale, int in) {
+    float src = __fmul_rn(scale, (float)dst);
+    asm volatile("" : "+v"(src));               // the rounded product, for good: * and - are fused by the backend whatever the source says
+    int i0 = (int)src;
+    if (i0 > in - 1) i0 = in - 1;
+    UpCoord u;
+    u.i0 = i0;
+    u.i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+    u.l1 = __fsub_rn(src, (float)i0);
+    u.l0 = __fsub_rn(1.f, u.l1);
+    return u;
+}
+__device__ __forceinline__ UpCoord up_coord_fused(int dst, float scale, int in) {
+    const float src = __fmul_rn(scale, (float)dst);
+    int i0 = (int)src;
+    if (i0 > in - 1) i0 = in - 1;
+    UpCoord u;
+    u.i0 = i0;
+    u.i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+    u.l1 = fmaf(scale, (float)dst, -(float)i0);
+    u.l0 = __fsub_rn(1.f, u.l1);
+    return u;
+}
+
 template <typename T, int V>
 __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
                                                              int B, int h, int w, int C, int Ho, int Wo, int pt, int pl,
@@ -139,7 +169,7 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const T* __restrict
         for (int i = 0; i < V; ++i) o[i] = 0.f;
         int uy = oy - pt, ux = ox - pl;
         if (uy >= 0 && uy < 2 * h && ux >= 0 && ux < 2 * w) {
-            UpCoord cy = up_coord(uy, sy, h), cx = up_coord(ux, sx, w);
+            UpCoord cy = up_coord_plain(uy, sy, h), cx = up_coord_fused(ux, sx, w);
             const T* r0 = x + ((int64_t)(b * h + cy.i0) * w) * ldx + c;
             const T* r1 = x + ((int64_t)(b * h + cy.i1) * w) * ldx + c;
             float v00[V], v01[V], v10[V], v11[V];
@@ -147,9 +177,13 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const T* __restrict
             uh_load<T, V>(r0 + (int64_t)cx.i1 * ldx, v01);
             uh_load<T, V>(r1 + (int64_t)cx.i0 * ldx, v10);
             uh_load<T, V>(r1 + (int64_t)cx.i1 * ldx, v11);
+            // (the two stages spelled out as upsample2x_fwd_rows_kernel spells them)
 #pragma unroll
-            for (int i = 0; i < V; ++i)
-                o[i] = cy.l0 * (cx.l0 * v00[i] + cx.l1 * v01[i]) + cy.l1 * (cx.l0 * v10[i] + cx.l1 * v11[i]);
+            for (int i = 0; i < V; ++i) {
+                const float h0 = fmaf(cx.l0, v00[i], __fmul_rn(cx.l1, v01[i]));
+                const float h1 = fmaf(cx.l0, v10[i], __fmul_rn(cx.l1, v11[i]));
+                o[i] = fmaf(cy.l0, h0, __fmul_rn(cy.l1, h1));
+            }
         }
         uh_store<T, V>(y + p * ldy + c, o);
     }
@@ -549,8 +583,17 @@ extern "C" int uh_upsample2x_bwd(const void* dy, int lddy, void* dx, int lddx, i
             else
                 hipLaunchKernelGGL((upsample2x_bwd_strip_kernel<T, VEC>), grid, dim3(256), 0, st, (const T*)dy,
                                    lddy, (T*)dx, lddx, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx, ty);
+        } else if (h >= 2 && w >= 2) {
+            // no 16-byte pieces (channel count, pointer or pitch): the strip kernel one channel per thread, in its pointer form --
+            // the arithmetic and the order of the sums of the 16-byte form, so a channel slice off the 16-byte grid gets the
+            // bits of the dense call (the gather kernel below folds wy * wx into one weight and rounds differently)
+            int ty = 16;
+            while (ty > 2 && (int64_t)B * ((h + ty - 1) / ty) * w * C < 256 * 1024) ty >>= 1;
+            const int64_t nthr = (int64_t)B * ((h + ty - 1) / ty) * w * C;
+            hipLaunchKernelGGL((upsample2x_bwd_strip_kernel<T, 1>), dim3(uh_flat_grid(nthr, UH_GRID_CAP)), dim3(256), 0, st,
+                               (const T*)dy, lddy, (T*)dx, lddx, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx, ty);
         } else
-            uh_pixel_launch<VEC>(p, [&](auto v, auto) {
+            uh_pixel_launch<VEC>(p, [&](auto v, auto) {      // one-row / one-column maps: the gather form
                 hipLaunchKernelGGL((upsample2x_bwd_kernel<T, decltype(v)::value>), dim3(p.grid), dim3(256), 0, st, (const T*)dy, lddy,
                                    (T*)dx, lddx, B, h, w, C, Ho, Wo, pad_top, pad_left, sy, sx);
             });
