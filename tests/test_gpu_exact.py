@@ -19,7 +19,9 @@ held to float64 in the same way, on the dyadic family, by test_gpu_exact_pixel.p
 Not covered here or there: the BatchNorm statistics of the conv epilogue (divisions; test_gpu_ops.py, test_gpu_bnsum.py; the
 stem's statistics rows have a derived bound in test_gpu_exact_pixel.py), the bilinear pair (weights that are no dyadic numbers:
 test_gpu_ops.py, and pitched against dense calls in test_gpu_exact_pixel.py), the narrow entry points (held bit for bit to the
-padded form there), tensors past 2 GiB (forward code 5, test_gpu_large.py), loss and optimizer."""
+padded form there), tensors past 2 GiB (forward code 5, test_gpu_large.py), the optimizer (held to float64, one step and twenty
+chained, by test_gpu_ema.py).  The default loss (csrc/loss.hip) is held to float64 op by op, with derived bounds, by
+test_gpu_loss_ops.py."""
 import ctypes
 
 import pytest
