@@ -100,8 +100,8 @@ def run_model(name, reps, per_size):
                "ratio_c_over_b": c["images_per_s"] / b["images_per_s"], "outputs_equal": same, "outputs_equal_invariant": same_c,
                "foreground_share": float(np.mean([(g == 255).mean() for g in got])), "graph_replays": predictor.graph_replays,
                "graph_replays_invariant": invariant.graph_replays,
-               "launch_lengths": {f"{h}x{w}": v for (h, w), v in predictor._lengths.items()},
-               "launch_lengths_invariant": {f"{h}x{w}": v for (h, w), v in invariant._lengths.items()}}
+               "launch_lengths": {f"{h}x{w}": v for (h, w), v in predictor.planner.lengths.items()},
+               "launch_lengths_invariant": {f"{h}x{w}": v for (h, w), v in invariant.planner.lengths.items()}}
         if label == "8x512x512":
             for key, pr in (("stage_ms_per_8_images", predictor), ("stage_ms_per_8_images_invariant", invariant)):
                 pr.events = []

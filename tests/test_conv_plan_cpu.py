@@ -178,8 +178,7 @@ def test_wgrad_plan_query_refuses_bad_arguments(lib):
 def test_launch_lengths_at_batch_8(lib, ctor, args, want):
     """profiles/predict_bench_line.json's sizes (H x W); the longest launch of each, bf16, batch 8."""
     import unet_amd
-    from unet_amd.predict import BatchPredictor
-    p = object.__new__(BatchPredictor)          # no device: launch_lengths only asks the library
-    p.model, p.batch, p.amp, p._lengths, p._layer_levels = getattr(unet_amd, ctor)(*args), 8, True, {}, None
+    from unet_amd.predict import LaunchPlanner
+    p = LaunchPlanner(getattr(unet_amd, ctor)(*args), 8, True)          # no device: launch_lengths only asks the library
     got = [p.launch_lengths(H, W) for H, W in ((512, 512), (384, 512), (999, 1000), (700, 300))]
     assert got == [list(range(1, n + 1)) for n in want]

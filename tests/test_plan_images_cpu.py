@@ -105,14 +105,10 @@ def test_plan_images_switch():
 SIZES = ((512, 512), (384, 512), (999, 1000), (700, 300))
 
 
-def _predictor(ctor, args, **attrs):
+def _predictor(ctor, args, **kw):
     import unet_amd
-    from unet_amd.predict import BatchPredictor
-    p = object.__new__(BatchPredictor)          # no device: launch_lengths only asks the library
-    p.model, p.batch, p.amp, p._lengths, p._layer_levels = getattr(unet_amd, ctor)(*args), 8, True, {}, None
-    for k, v in attrs.items():
-        setattr(p, k, v)
-    return p
+    from unet_amd.predict import LaunchPlanner
+    return LaunchPlanner(getattr(unet_amd, ctor)(*args), 8, True, **kw)          # no device: launch_lengths only asks the library
 
 
 @pytest.mark.parametrize("ctor,args,off", [
@@ -124,7 +120,7 @@ def _predictor(ctor, args, **attrs):
 def test_launch_lengths_batch_invariant(lib, ctor, args, off):
     p = _predictor(ctor, args, batch_invariant=True)
     assert [p.launch_lengths(H, W) for H, W in SIZES] == [list(range(1, 9))] * 4
-    # off, and on an object that has no such attribute: the lengths tests/test_conv_plan_cpu.py pins
+    # off, and constructed with the default: the lengths tests/test_conv_plan_cpu.py pins
     for attrs in ({"batch_invariant": False}, {}):
         p = _predictor(ctor, args, **attrs)
         assert [p.launch_lengths(H, W) for H, W in SIZES] == [list(range(1, n + 1)) for n in off]
@@ -161,3 +157,19 @@ def test_constructors_take_the_keyword():
     assert inspect.signature(BatchPredictor.__init__).parameters["batch_invariant"].default is False
     assert inspect.signature(ContourPipeline.__init__).parameters["batch_invariant"].default is False
     assert inspect.signature(GraphedForward.__init__).parameters["plan_images"].default == 0
+
+
+@pytest.mark.parametrize("lengths", [[1], [1, 2, 7], [1, 3], [1, 3, 5, 7], [1, 2, 3, 5, 6, 7], list(range(1, 9))])
+def test_cut_is_the_greedy_split(lengths):
+    """LaunchPlanner.cut: every piece an allowed length, the pieces sum to n, each the largest length that fits what is left."""
+    from unet_amd.predict import LaunchPlanner
+    p = LaunchPlanner(None, 8, True)
+    p.lengths[(48, 64)] = lengths                  # the public cache: no model and no library are asked
+    for n in range(1, 21):
+        pieces = p.cut(n, 48, 64)
+        assert sum(pieces) == n and all(b in lengths for b in pieces)
+        left = n
+        for b in pieces:
+            assert b == max(v for v in lengths if v <= left)
+            left -= b
+    assert p.cut(0, 48, 64) == []

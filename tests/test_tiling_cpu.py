@@ -123,10 +123,9 @@ def test_constructors_take_the_keyword():
     p.tta = p.tile = None
     with pytest.raises(RuntimeError, match="tile"):
         p.probabilities([])
-    p.batch, p.tta = 8, unet_amd.tta_mask("flips")
-    assert p.tile_chunk(32, 32) == 2                                                # under tta the group counts tiles
-    p.tta = None
-    assert p.tile_chunk(32, 32) == 8
+    from unet_amd.predict import LaunchPlanner
+    assert LaunchPlanner(None, 8, True, tta=unet_amd.tta_mask("flips")).tile_chunk(32, 32) == 2      # under tta the group counts tiles
+    assert LaunchPlanner(None, 8, True).tile_chunk(32, 32) == 8
 
 
 def test_command_lines_parse_the_flag(capsys):

@@ -120,10 +120,8 @@ def test_merge_ref_is_equivariant_and_normalised():
 
 def _predictor(batch, tta):
     import unet_amd
-    from unet_amd.predict import BatchPredictor
-    p = object.__new__(BatchPredictor)                                  # no device: the grouping is arithmetic
-    p.batch, p.tta = batch, unet_amd.tta_mask(tta)
-    return p
+    from unet_amd.predict import LaunchPlanner
+    return LaunchPlanner(None, batch, True, tta=unet_amd.tta_mask(tta))          # no device, no model: the grouping is arithmetic
 
 
 def test_grouping_arithmetic_under_tta():
@@ -148,7 +146,7 @@ def test_constructors_take_the_keyword():
     assert inspect.signature(BatchPredictor.__init__).parameters["tta"].default is None
     assert inspect.signature(unet_amd.evaluate).parameters["tta"].default is None
     p = object.__new__(BatchPredictor)
-    p.tta = None
+    p.tta = p.tile = None
     with pytest.raises(RuntimeError, match="tta"):
         p.probabilities([])
 

@@ -21,6 +21,7 @@ import torch
 from . import ops
 from .utils.dice_score import dice_coeff
 from .utils.post_process import postprocess_mask
+from .utils.tta import tta_counts, tta_mask
 
 
 class _PredDump:
@@ -54,42 +55,35 @@ class _PredDump:
         self.writer.close()
 
 
-def _tta_classes(net, image, tta):
-    """uint8 [B,H,W]: the classes of the probabilities averaged over the views of `tta` (inside evaluate's autocast).  Each
-    view of the batch is a launch of its own, of the batch's length, under the pinned plan of one image."""
-    from .utils.tta import tta_counts
-    B, _, H, W = image.shape
+def _tta_merged(net, x, tta, sums=False):
+    """ops.tta_merge of the views of a prepared batch [n,C,H,W] under `tta` (inside evaluate's autocast).  Each view of the
+    batch is a launch of its own, of the batch's length, under the pinned plan of one image."""
+    n, _, H, W = x.shape
     k0, k1 = tta_counts(tta)
-    views0, views1 = ops.tta_views(image, tta)
+    views0, views1 = ops.tta_views(x, tta)
     with ops.plan_images(1):
-        logits0 = torch.cat([net(views0[k * B:(k + 1) * B]) for k in range(k0)])
-        logits1 = torch.cat([net(views1[k * B:(k + 1) * B]) for k in range(k1)]) if k1 else None
-    return ops.tta_merge(logits0, logits1, tta, (H, W)).classes
+        logits0 = torch.cat([net(views0[k * n:(k + 1) * n]) for k in range(k0)])
+        logits1 = torch.cat([net(views1[k * n:(k + 1) * n]) for k in range(k1)]) if k1 else None
+    return ops.tta_merge(logits0, logits1, tta, (H, W), sums=sums)
+
+
+def _tta_classes(net, image, tta):
+    """uint8 [B,H,W]: the classes of the probabilities averaged over the views of `tta`."""
+    return _tta_merged(net, image, tta).classes
 
 
 def _tile_classes(net, image, tile, tta):
     """uint8 [B,H,W]: the classes of the tiled prediction of a batch (inside evaluate's autocast).  The tiles go through the
     network len(image) at a time under the pinned plan of one image; with `tta` every such launch group goes through
-    _tta_classes' route and the tile merge adds the views' integer sums."""
+    _tta_merged and the tile merge adds the views' integer sums."""
     B, _, H, W = image.shape
     tiles = ops.tile_gather(image, tile)
-    th, tw = tiles.shape[-2:]
     if tta is None:
         with ops.plan_images(1):
             src = torch.cat([net(tiles[s:s + B]) for s in range(0, tiles.shape[0], B)])
         return ops.tile_merge(src, tile, (H, W)).classes
-    from .utils.tta import tta_counts
-    k0, k1 = tta_counts(tta)
-    sums = []
-    for s in range(0, tiles.shape[0], B):
-        part = tiles[s:s + B]
-        n = part.shape[0]
-        views0, views1 = ops.tta_views(part, tta)
-        with ops.plan_images(1):
-            logits0 = torch.cat([net(views0[k * n:(k + 1) * n]) for k in range(k0)])
-            logits1 = torch.cat([net(views1[k * n:(k + 1) * n]) for k in range(k1)]) if k1 else None
-        sums.append(ops.tta_merge(logits0, logits1, tta, (th, tw), sums=True).sums)
-    return ops.tile_merge(torch.cat(sums), tile, (H, W), k0 + k1).classes
+    sums = torch.cat([_tta_merged(net, tiles[s:s + B], tta, sums=True).sums for s in range(0, tiles.shape[0], B)])
+    return ops.tile_merge(sums, tile, (H, W), sum(tta_counts(tta))).classes
 
 
 @torch.inference_mode()
@@ -106,7 +100,6 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
     `tile`: a TileConfig or a spec like "512,overlap=128" -- images larger than one tile are predicted tile by tile and merged
     with the overlap blended (None: whole images)."""
     if tta is not None:
-        from .utils.tta import tta_mask
         tta = tta_mask(tta)
     if tile is not None:
         from .utils.tiling import tile_config, tile_count

@@ -5,6 +5,30 @@ from __future__ import annotations
 
 import torch
 
+from . import ops
+
+
+def eval_forward(model: torch.nn.Module, x: torch.Tensor, amp: bool, plan_images: int = 0) -> torch.Tensor:
+    """`model(x)` without autograd, under bf16 autocast when `amp`, and under ops.plan_images(plan_images) when that is > 0
+    (0 leaves a plan that is already active in force)."""
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+        if plan_images:
+            with ops.plan_images(plan_images):
+                return model(x)
+        return model(x)
+
+
+def timed_stage(events, name, fn, *a, **kw):
+    """`fn(*a, **kw)`; when `events` is a list, (name, start event, end event) on the current stream is appended to it."""
+    if events is None:
+        return fn(*a, **kw)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    r = fn(*a, **kw)
+    e1.record()
+    events.append((name, e0, e1))
+    return r
+
 
 class GraphedForward:
     """`g = GraphedForward(model, example_images); logits = g(images)` -- same result as `model.eval()(images)`.
@@ -24,20 +48,12 @@ class GraphedForward:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up off the default stream: filter packs, allocator pools
             for _ in range(max(1, warmup)):
-                self._forward(self.static_in)
+                eval_forward(self.model, self.static_in, self.amp, self.plan_images)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.static_out = self._forward(self.static_in)
-
-    def _forward(self, x):
-        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.amp):
-            if self.plan_images:
-                from . import ops
-                with ops.plan_images(self.plan_images):
-                    return self.model(x)
-            return self.model(x)
+            self.static_out = eval_forward(self.model, self.static_in, self.amp, self.plan_images)
 
     def __call__(self, images: torch.Tensor) -> torch.Tensor:
         if images.shape != self.static_in.shape:

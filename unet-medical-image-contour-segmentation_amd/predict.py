@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .inference import GraphedForward, eval_forward, timed_stage
 
 
 def _table(pairs) -> np.ndarray:
@@ -124,12 +125,9 @@ def _as_grey_array(img) -> np.ndarray:
     return a
 
 
-class BatchPredictor:
-    """`predictor(images)` -> one uint8 [H,W] grey-coded mask per image, in input order: what
-    mask_to_image(postprocess_mask(predict_img(model, image, device))) returns for that image (mask_to_image(predict_img(...))
-    with postprocess=False).  `predictor.classes(images)` returns the class maps instead.  Images may have mixed sizes; they
-    are grouped by (H, W) and run up to `batch` at a time.  A full batch of a size that has been seen before replays a
-    captured graph (at most MAX_GRAPHS are kept, least recently used first out); everything else runs un-graphed.
+class LaunchPlanner:
+    """The launch arithmetic of BatchPredictor: which launch lengths an image size allows, how a batch is cut into them, and
+    how many source images or tiles make a launch group.  It touches no tensor and no device; it only asks LIB.query.
 
     The result for an image does not depend on its neighbours or on `batch`: every kernel of the eval forward computes a
     pixel from that image's data in a fixed order.  WHICH kernel runs, however, is chosen per launch in two places, and
@@ -147,7 +145,94 @@ class BatchPredictor:
     to the kernel one image gets (uh_conv3x3_fwd_affine_relu_plan, uh_convt2x2_mfma_ok_plan), so a launch of any length
     gives every image the bits it gets alone.  `launch_lengths` then asks the pinned queries and returns every B up to
     `batch` that no real-B limit (a tensor past the 2 GiB window: another kernel) excludes.  The masks are those of the
-    default mode; only the number of launches differs.
+    default mode; only the number of launches differs."""
+
+    def __init__(self, model: torch.nn.Module, batch: int, amp: bool, batch_invariant: bool = False, tta=None):
+        self.model, self.batch, self.amp = model, int(batch), bool(amp)
+        self.batch_invariant, self.tta = bool(batch_invariant), tta
+        self.lengths: Dict[Tuple[int, int], List[int]] = {}           # (H, W) -> launch_lengths(H, W)
+
+    def _layers(self):
+        """(kind, module, pyramid levels it may sit at) for the layers whose kernel choice can depend on B."""
+        depth = getattr(self.model, "depth", None)
+        if depth is None:
+            depth = sum(1 for n, _ in self.model.named_children() if n.startswith("down"))
+        out = []
+        for name, m in self.model.named_modules():
+            is_t = isinstance(m, torch.nn.ConvTranspose2d)
+            if not is_t and not (isinstance(m, torch.nn.Conv2d) and tuple(m.kernel_size) == (3, 3)):
+                continue
+            top = name.split(".")[0]
+            if top == "inc":
+                levels = [0]
+            elif top.startswith("down") and top[4:].isdigit():
+                levels = [int(top[4:])]
+            elif top.startswith("up") and top[2:].isdigit():
+                # block j works at level depth - j; its transposed convolution reads the level below
+                levels = [depth - int(top[2:]) + (1 if is_t else 0)]
+            else:
+                levels = list(range(0, depth + 1))                 # unknown place: every level is checked
+            out.append(("convt" if is_t else "conv", m, levels))
+        return out
+
+    def launch_lengths(self, H: int, W: int) -> List[int]:
+        """The launch lengths B <= batch at which an H x W image is computed by the kernels it gets alone (1 always is)."""
+        key = (int(H), int(W))
+        if key not in self.lengths:
+            from ._lib import LIB, UH_BF16, UH_F32
+            dt = UH_BF16 if self.amp else UH_F32
+            pin = 1 if self.batch_invariant else 0
+            layers = self._layers()                                    # walked once per new size: the lengths are kept
+
+            def choice(B, kind, m, k):
+                h, w = H >> k, W >> k
+                if h < 1 or w < 1:
+                    return 0
+                if kind == "convt":
+                    if pin and B > 1:
+                        return LIB.query("uh_convt2x2_mfma_ok_plan", B, pin, h, w, m.in_channels, m.out_channels, H >> (k - 1),
+                                         W >> (k - 1), dt)
+                    return LIB.query("uh_convt2x2_mfma_ok", B, h, w, m.in_channels, m.out_channels, H >> (k - 1), W >> (k - 1), dt)
+                if pin and B > 1:
+                    # the summation class of the kernel the pinned call runs: equal to one image's unless a real-B limit moved it
+                    code = LIB.query("uh_conv3x3_fwd_kernel_plan", B, pin, h, w, m.in_channels, 0, m.out_channels, dt)
+                    return LIB.query("uh_conv3x3_fwd_sum_class", code)
+                code = LIB.query("uh_conv3x3_fwd_kernel", B, h, w, m.in_channels, 0, m.out_channels, dt)
+                return LIB.query("uh_conv3x3_fwd_sum_class", code) if pin else code
+
+            self.lengths[key] = [B for B in range(1, self.batch + 1)
+                                 if all(choice(B, kind, m, k) == choice(1, kind, m, k)
+                                        for kind, m, levels in layers for k in levels if k >= (1 if kind == "convt" else 0))]
+        return self.lengths[key]
+
+    def cut(self, n: int, H: int, W: int) -> List[int]:
+        """`n` images of H x W as the fewest launches launch_lengths allows: each piece the longest that still fits."""
+        lengths = self.launch_lengths(H, W)
+        pieces = []
+        while n:
+            pieces.append(max(v for v in lengths if v <= n))
+            n -= pieces[-1]
+        return pieces
+
+    def tta_group(self, H: int, W: int) -> int:
+        """Source images of one size per launch group: `batch` is the number of images per forward launch, and a launch
+        carries every view of a square image, the larger of the two view shapes' counts otherwise."""
+        from .utils.tta import tta_forward_views
+        return max(1, self.batch // tta_forward_views(self.tta, H, W))
+
+    def tile_chunk(self, th: int, tw: int) -> int:
+        """Tiles of one shape per forward step: `batch`, or under test-time augmentation what tta_group allows (it counts
+        tiles here: `batch` stays the number of network inputs per forward launch)."""
+        return self.batch if self.tta is None else self.tta_group(th, tw)
+
+
+class BatchPredictor:
+    """`predictor(images)` -> one uint8 [H,W] grey-coded mask per image, in input order: what
+    mask_to_image(postprocess_mask(predict_img(model, image, device))) returns for that image (mask_to_image(predict_img(...))
+    with postprocess=False).  `predictor.classes(images)` returns the class maps instead.  Images may have mixed sizes; they
+    are grouped by (H, W) and run up to `batch` at a time.  A full batch of a size that has been seen before replays a
+    captured graph (at most MAX_GRAPHS are kept, least recently used first out); everything else runs un-graphed.  A batch
+    is cut into launches of the lengths `launch_lengths` allows, all lengths under `batch_invariant=True` (LaunchPlanner).
 
     `tta` (a mode of utils/tta.py: "hflip", "flips", "rot4", "d4"): test-time augmentation.  Every image is predicted in each
     view of the mode and the views' probabilities are averaged before the argmax (uh_tta_views, the forward, uh_tta_merge;
@@ -196,23 +281,25 @@ class BatchPredictor:
         self._flags = torch.empty(self.batch, dtype=torch.int32, device=self.device)
         self._graphs: "OrderedDict[Tuple[int, int, int], object]" = OrderedDict()
         self._seen = set()
-        self._lengths: Dict[Tuple[int, int], List[int]] = {}
-        self._layer_levels = None
+        self.planner = LaunchPlanner(self.model, self.batch, self.amp, self.batch_invariant, self.tta)
         self._pin_in: Optional[torch.Tensor] = None
         self._pin_out: Optional[torch.Tensor] = None
+        self._upload_done = torch.cuda.Event()                        # recorded behind every upload out of _pin_in
         self.events = None                    # set to a list to collect (stage, start event, end event) per batch
         self.graph_replays = 0
 
     # ---------------------------------------------------------------- stages
     def _mark(self, name, fn, *a, **kw):
-        if self.events is None:
-            return fn(*a, **kw)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn(*a, **kw)
-        e1.record()
-        self.events.append((name, e0, e1))
-        return r
+        return timed_stage(self.events, name, fn, *a, **kw)
+
+    def launch_lengths(self, H: int, W: int) -> List[int]:
+        return self.planner.launch_lengths(H, W)
+
+    def tta_group(self, H: int, W: int) -> int:
+        return self.planner.tta_group(H, W)
+
+    def tile_chunk(self, th: int, tw: int) -> int:
+        return self.planner.tile_chunk(th, tw)
 
     def _pinned(self, which: str, nbytes: int) -> torch.Tensor:
         buf = getattr(self, which)
@@ -231,62 +318,19 @@ class BatchPredictor:
         dev.copy_(stage, non_blocking=True)
         return dev
 
-    def _layers(self):
-        """(kind, module, pyramid levels it may sit at) for the layers whose kernel choice can depend on B."""
-        if self._layer_levels is None:
-            depth = getattr(self.model, "depth", None)
-            if depth is None:
-                depth = sum(1 for n, _ in self.model.named_children() if n.startswith("down"))
-            out = []
-            for name, m in self.model.named_modules():
-                is_t = isinstance(m, torch.nn.ConvTranspose2d)
-                if not is_t and not (isinstance(m, torch.nn.Conv2d) and tuple(m.kernel_size) == (3, 3)):
-                    continue
-                top = name.split(".")[0]
-                if top == "inc":
-                    levels = [0]
-                elif top.startswith("down") and top[4:].isdigit():
-                    levels = [int(top[4:])]
-                elif top.startswith("up") and top[2:].isdigit():
-                    # block j works at level depth - j; its transposed convolution reads the level below
-                    levels = [depth - int(top[2:]) + (1 if is_t else 0)]
-                else:
-                    levels = list(range(0, depth + 1))                 # unknown place: every level is checked
-                out.append(("convt" if is_t else "conv", m, levels))
-            self._layer_levels = out
-        return self._layer_levels
-
-    def launch_lengths(self, H: int, W: int) -> List[int]:
-        """The launch lengths B <= batch at which an H x W image is computed by the kernels it gets alone (1 always is)."""
-        key = (int(H), int(W))
-        if key not in self._lengths:
-            from ._lib import LIB, UH_BF16, UH_F32
-            dt = UH_BF16 if self.amp else UH_F32
-            pin = 1 if getattr(self, "batch_invariant", False) else 0     # (tests build the object without __init__)
-
-            def choice(B, kind, m, k):
-                h, w = H >> k, W >> k
-                if h < 1 or w < 1:
-                    return 0
-                if kind == "convt":
-                    if pin and B > 1:
-                        return LIB.query("uh_convt2x2_mfma_ok_plan", B, pin, h, w, m.in_channels, m.out_channels, H >> (k - 1),
-                                         W >> (k - 1), dt)
-                    return LIB.query("uh_convt2x2_mfma_ok", B, h, w, m.in_channels, m.out_channels, H >> (k - 1), W >> (k - 1), dt)
-                if pin and B > 1:
-                    # the summation class of the kernel the pinned call runs: equal to one image's unless a real-B limit moved it
-                    code = LIB.query("uh_conv3x3_fwd_kernel_plan", B, pin, h, w, m.in_channels, 0, m.out_channels, dt)
-                    return LIB.query("uh_conv3x3_fwd_sum_class", code)
-                code = LIB.query("uh_conv3x3_fwd_kernel", B, h, w, m.in_channels, 0, m.out_channels, dt)
-                return LIB.query("uh_conv3x3_fwd_sum_class", code) if pin else code
-
-            self._lengths[key] = [B for B in range(1, self.batch + 1)
-                                  if all(choice(B, kind, m, k) == choice(1, kind, m, k)
-                                         for kind, m, levels in self._layers() for k in levels if k >= (1 if kind == "convt" else 0))]
-        return self._lengths[key]
+    def _stage(self, arrays: List[np.ndarray]) -> torch.Tensor:
+        """Equally sized uint8 [H,W] images -> the network's input float32 [B,1,H,W], channels_last, on the device."""
+        H, W = arrays[0].shape
+        B = len(arrays)
+        self._upload_done.synchronize()            # the pinned staging buffer is free once the previous upload has left it
+        img = self._mark("upload", self._upload, arrays, H, W)
+        self._upload_done.record()
+        x = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
+        flags = self._flags if B <= self._flags.numel() else torch.empty(B, dtype=torch.int32, device=self.device)
+        self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
+        return x
 
     def _forward(self, x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
-        from .inference import GraphedForward
         full = self.launch_lengths(*size)[-1]                          # the longest launch this size allows
         size = (x.shape[0],) + tuple(size)
         if x.shape[0] == full and size in self._seen:
@@ -300,41 +344,28 @@ class BatchPredictor:
             return g(x)
         if x.shape[0] == full:
             self._seen.add(size)
-        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.amp):
-            if self.batch_invariant:
-                with ops.plan_images(1):
-                    return self.model(x)
-            return self.model(x)
+        return eval_forward(self.model, x, self.amp, plan_images=1 if self.batch_invariant else 0)
 
-    def run_batch(self, arrays: List[np.ndarray], grey: bool = True) -> np.ndarray:
+    def run_batch(self, arrays: List[np.ndarray], grey: bool = True, probs: bool = False) -> np.ndarray:
         """One batch of equally sized uint8 [H,W] images -> uint8 [B,H,W] on the host (grey-coded, or class indices), in as
-        few launches as launch_lengths allows."""
+        few launches as launch_lengths allows; or (probs, under `tta` or `tile`) float32 [B,NC,H,W]."""
         H, W = arrays[0].shape
-        if getattr(self, "tile", None) is not None:
-            return np.stack(self._run_tiled(arrays, grey))
-        if getattr(self, "tta", None) is not None:
+        if self.tile is not None:
+            return np.stack(self._run_tiled(arrays, grey, probs))
+        if self.tta is not None:
             g = self.tta_group(H, W)
-            out = [self._launch_tta(arrays[s:s + g], grey) for s in range(0, len(arrays), g)]
-            return out[0] if len(out) == 1 else np.concatenate(out)
-        lengths = self.launch_lengths(H, W)
-        if len(arrays) in lengths:
-            return self._launch(arrays, grey)
-        out, s = [], 0
-        while s < len(arrays):
-            b = max(v for v in lengths if v <= len(arrays) - s)
-            out.append(self._launch(arrays[s:s + b], grey))
-            s += b
-        return np.concatenate(out)
+            out = [self._launch_tta(arrays[s:s + g], grey, probs) for s in range(0, len(arrays), g)]
+        else:
+            out, s = [], 0
+            for b in self.planner.cut(len(arrays), H, W):
+                out.append(self._launch(arrays[s:s + b], grey))
+                s += b
+        return out[0] if len(out) == 1 else np.concatenate(out)
 
     def _launch(self, arrays: List[np.ndarray], grey: bool) -> np.ndarray:
         H, W = arrays[0].shape
-        B = len(arrays)
         with torch.cuda.device(self.device):
-            img = self._mark("upload", self._upload, arrays, H, W)
-            x = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
-            flags = self._flags if B <= self._flags.numel() else torch.empty(B, dtype=torch.int32, device=self.device)
-            self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
-            logits = self._mark("forward", self._forward, x, (H, W))
+            logits = self._mark("forward", self._forward, self._stage(arrays), (H, W))
             if tuple(logits.shape[-2:]) != (H, W):
                 raise RuntimeError(f"the network returned {tuple(logits.shape[-2:])} for a {(H, W)} input")     # predict.py:26 is dead at scale 1
             cls = self._mark("classes", ops.logits_to_classes_u8, logits)
@@ -354,24 +385,12 @@ class BatchPredictor:
         return out.numpy().copy()
 
     # ---------------------------------------------------------------- test-time augmentation
-    def tta_group(self, H: int, W: int) -> int:
-        """Source images of one size per launch group: `batch` is the number of images per forward launch, and a launch
-        carries every view of a square image, the larger of the two view shapes' counts otherwise."""
-        from .utils.tta import tta_forward_views
-        return max(1, self.batch // tta_forward_views(self.tta, H, W))
-
     def _forward_cut(self, x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
         """_forward for a view batch of any length, in as few launches as launch_lengths allows."""
-        lengths = self.launch_lengths(*size)
-        n = x.shape[0]
-        if n in lengths:
+        cut = self.planner.cut(x.shape[0], *size)
+        if len(cut) == 1:
             return self._forward(x, size)
-        pieces, s = [], 0
-        while s < n:
-            b = max(v for v in lengths if v <= n - s)
-            pieces.append(self._forward(x[s:s + b], size).clone())    # (a replayed graph returns its static buffer)
-            s += b
-        return torch.cat(pieces)
+        return torch.cat([self._forward(part, size).clone() for part in x.split(cut)])   # (a replayed graph returns its static buffer)
 
     def _tta_logits(self, x: torch.Tensor, H: int, W: int):
         """The logits of the views of a prepared batch [B,C,H,W]: (untransposed views, transposed views or None)."""
@@ -388,39 +407,18 @@ class BatchPredictor:
     def _launch_tta(self, arrays: List[np.ndarray], grey: bool, probs: bool = False) -> np.ndarray:
         """One launch group under test-time augmentation -> uint8 [B,H,W] as _launch, or (probs) float32 [B,NC,H,W]."""
         H, W = arrays[0].shape
-        B = len(arrays)
         with torch.cuda.device(self.device):
-            img = self._mark("upload", self._upload, arrays, H, W)
-            x = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
-            flags = self._flags if B <= self._flags.numel() else torch.empty(B, dtype=torch.int32, device=self.device)
-            self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
-            l0, l1 = self._tta_logits(x, H, W)
+            l0, l1 = self._tta_logits(self._stage(arrays), H, W)
             merged = self._mark("merge", ops.tta_merge, l0, l1, self.tta, (H, W), probs=probs)
             if probs:
                 return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
             return self._deliver(merged.classes, grey)
 
     # ---------------------------------------------------------------- tiled prediction
-    def tile_chunk(self, th: int, tw: int) -> int:
-        """Tiles of one shape per forward step: `batch`, or under test-time augmentation what tta_group allows (it counts
-        tiles here: `batch` stays the number of network inputs per forward launch)."""
-        return self.batch if getattr(self, "tta", None) is None else self.tta_group(th, tw)
-
     def _prepare_tiles(self, arrays: List[np.ndarray]) -> torch.Tensor:
         """Equally sized images -> their tiles [B*ny*nx,1,th,tw] on the device; the prepare sees the WHOLE images."""
-        H, W = arrays[0].shape
-        B = len(arrays)
         with torch.cuda.device(self.device):
-            busy = getattr(self, "_upload_done", None)
-            if busy is not None:
-                busy.synchronize()                 # the pinned staging buffer is free once the previous upload has left it
-            img = self._mark("upload", self._upload, arrays, H, W)
-            self._upload_done = torch.cuda.Event()
-            self._upload_done.record()
-            x = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
-            flags = self._flags if B <= self._flags.numel() else torch.empty(B, dtype=torch.int32, device=self.device)
-            self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
-            return self._mark("gather", ops.tile_gather, x, self.tile)
+            return self._mark("gather", ops.tile_gather, self._stage(arrays), self.tile)
 
     def _tile_forward(self, tiles: torch.Tensor, shape: Tuple[int, int]) -> torch.Tensor:
         """One forward step of the tiled flow: the logits [n,NC,th,tw] of the tiles, or under test-time augmentation the
@@ -494,15 +492,15 @@ class BatchPredictor:
             advance(True)
         return result
 
-    def _run(self, images, grey: bool) -> List[np.ndarray]:
+    def _run(self, images, grey: bool, probs: bool = False) -> List[np.ndarray]:
         arrays = [_as_grey_array(im) for im in images]
-        if getattr(self, "tile", None) is not None:
-            return self._run_tiled(arrays, grey)
+        if self.tile is not None:
+            return self._run_tiled(arrays, grey, probs)
         result: List[Optional[np.ndarray]] = [None] * len(arrays)
         for _, members in plan_batches([a.shape for a in arrays], self.batch):
-            out = self.run_batch([arrays[i] for i in members], grey)
+            out = self.run_batch([arrays[i] for i in members], grey, probs)
             for k, i in enumerate(members):
-                result[i] = out[k]
+                result[i] = np.ascontiguousarray(out[k])
         return result
 
     def __call__(self, images) -> List[np.ndarray]:
@@ -514,21 +512,10 @@ class BatchPredictor:
     def probabilities(self, images) -> List[np.ndarray]:
         """float32 [NC,H,W] per image: the mean over the views of the softmax probabilities (multiples of 2^-24 / V); under
         `tile` the weighted mean over the covering tiles (and their views), (float)(sum / (den V 2^24))."""
-        if getattr(self, "tta", None) is None and getattr(self, "tile", None) is None:
+        if self.tta is None and self.tile is None:
             raise RuntimeError("probabilities() returns the mean over the views of test-time augmentation (tta=...) or over the "
                                "covering tiles of tiled prediction (tile=...): build the predictor with one of them")
-        arrays = [_as_grey_array(im) for im in images]
-        if getattr(self, "tile", None) is not None:
-            return self._run_tiled(arrays, False, probs=True)
-        result: List[Optional[np.ndarray]] = [None] * len(arrays)
-        for (H, W), members in plan_batches([a.shape for a in arrays], self.batch):
-            g = self.tta_group(H, W)
-            for s in range(0, len(members), g):
-                part = members[s:s + g]
-                out = self._launch_tta([arrays[i] for i in part], False, probs=True)
-                for k, i in enumerate(part):
-                    result[i] = np.ascontiguousarray(out[k])
-        return result
+        return self._run(images, False, probs=True)
 
 
 def main(argv=None) -> int:

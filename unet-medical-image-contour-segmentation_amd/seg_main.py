@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .inference import GraphedForward
+from .inference import GraphedForward, eval_forward, timed_stage
 from .utils.mask2polygon import contour_json, external_contours, write_json
 from .utils.png_denormalize import CLASS_TO_GREY
 from .utils.png_normalize import TARGET, _IDENTITY, device_lut, letterbox_geometry, resample_into, resample_plan
@@ -70,14 +70,7 @@ class ContourPipeline:
 
     # ---------------------------------------------------------------- stages
     def _mark(self, name, fn, *a):
-        if self.events is None:
-            return fn(*a)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn(*a)
-        e1.record()
-        self.events.append((name, e0, e1))
-        return r
+        return timed_stage(self.events, name, fn, *a)
 
     def _to_device(self, raws):
         if isinstance(raws, np.ndarray):
@@ -107,15 +100,12 @@ class ContourPipeline:
         # predict.py:19 preprocess: float32 / 255 when the image holds a byte > 1 (decided per image), channels_last
         LIB.call("uh_batch_prepare", canvas.data_ptr(), 1, None, None, 0, x.data_ptr(), 1, None, flags.data_ptr(), B, TARGET,
                  TARGET, 0, ops._stream())
+        plan = 1 if self.batch_invariant else 0
         if B == self.batch:
             if self._graph is None:
-                self._graph = GraphedForward(self.model, x, amp=self.amp, plan_images=1 if self.batch_invariant else 0)
+                self._graph = GraphedForward(self.model, x, amp=self.amp, plan_images=plan)
             return self._graph(x)
-        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.amp):
-            if self.batch_invariant:
-                with ops.plan_images(1):
-                    return self.model(x)
-            return self.model(x)
+        return eval_forward(self.model, x, self.amp, plan)
 
     def _unletterbox(self, classes):
         nw, nh, px, py = self.geometry
