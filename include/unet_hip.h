@@ -325,8 +325,15 @@ int uh_upsample2x_bwd(const void* dy, int lddy, void* dx, int lddx, int B, int h
  * fp32 [B*H*W] gradient of a) is given.  ws = fp32 workspace of 3*B*H*W floats, 8-byte aligned (the gradient of pool, then
  * g_a * a * (1 - a)); dx = dy*a + d(mean)/dx + d(max)/dx in dt (pixel stride lddx); dw = fp32 [2*k*k], summed over
  * per-workgroup rows dw_partials = fp32 [nblk][2*k*k] with nblk >= uh_spatial_attn_dw_nblk(B, H, W) in a fixed order
- * (bit-identical between runs).  B <= 65535. */
+ * (bit-identical between runs).  B <= 65535.
+ * uh_spatial_attn_plan: the launch form a call takes; host only, no device touched.  aligned != 0: every channel tensor of the
+ * call (forward: x and y; backward: dx, and dy and x of the gate) is 16-byte aligned with a pixel stride of whole 16-byte
+ * pieces.  out[0..2] (HOST memory) = {V, G, steps}: V = channels per lane and step (8 bf16 / 4 fp32 where aligned and C is a
+ * multiple of that, else 1), G = the lanes that share a pixel in the channel reductions (the smallest power of two that holds
+ * ceil(C / V), at most 64; the map's backward, whose gradient is given per pixel, reduces nothing and uses one lane),
+ * steps = ceil(ceil(C / V) / G), the strides of G * V channels a lane takes.  UH_EINVAL for a bad size or dtype or out == NULL. */
 int uh_spatial_attn_dw_nblk(int B, int H, int W);
+int uh_spatial_attn_plan(int C, int dt, int aligned, int64_t* out);
 int uh_spatial_attn_fwd(const void* x, int ldx, const float* w, int k, float* pool, int* amax, float* a, void* y,
                         int ldy, int B, int H, int W, int C, int dt, uh_stream stream);
 int uh_spatial_attn_bwd(const void* dy, int lddy, const float* ga, const void* x, int ldx, const float* w, int k,

@@ -5,7 +5,7 @@ integer times one fixed power of two) below 2^24, fp32 addition is exact in ANY 
 bit for bit: no tolerance, and a missing, doubled or misplaced term, or an intermediate kept in fewer bits, changes the output.
 
 The pixel passes (BatchNorm + ReLU, the pool and head tails, max-pool) and the recomputed stem have their own "dyadic" family and
-case classes in the second half of this file.
+case classes in the second half of this file; the spatial-attention kernels have theirs (SaFwdCase, SaBwdCase) at its end.
 
 Families (all values are exact in bf16, so one set of inputs serves the fp32 and the bf16 kernels):
   ternary  {-1, 0, +1}; for a contraction of length K the densities obey p_a * p_b <= 1100 / K, which keeps the outputs (integers)
@@ -662,3 +662,243 @@ class StemCase:
 @functools.lru_cache(maxsize=4)
 def stem_case(B, H, W, family):
     return StemCase(B, H, W, family)
+
+
+# ------------------------------------------------------------------------------------------------ spatial attention
+# csrc/spatial_attn.hip: channel mean / max / first maximal channel, a k x k correlation of those two maps under a sigmoid, the gate
+# y = x a, and their backward.  x holds wide integers and w is dyadic (the integers +-1 .. +-k^2, each once, times a power of two:
+# every tap distinct), so the maximum, its channel, the channel sum, every correlation of the backward and the filter gradient have
+# ONE right value; the mean is one float32 division of an exact sum.  Only the map itself holds an expf and a division.
+SA_TH, SA_TW, SA_DW_BLOCKS = 8, 32, 1024       # the LDS tile of the k x k passes; the most workgroups the filter gradient is dealt to
+SA_A_VALUES = (0.125, 0.25, 0.5, 0.75, 0.875)  # the synthetic map of the backward cases: a, 1 - a and a (1 - a) are exact in a few bits
+SA_Q_GS = 1.0 / 64                             # quantum of g_s = d a (1 - a) with an integer d
+SA_Q_W = 1.0 / 64                              # quantum of the backward cases' w
+SA_D_MAX = 256                                 # |sum_c x dy| of the gate's backward: g_s then needs 9 + 6 bits
+SA_ACC_UNITS = 4.0                             # the most an inexact accumulator of the map may be off, in units of 2^-24 (SaFwdCase)
+SA_PLANTS = 7                               # pixel p holds plant p % 7: none, tie of two, tie of three, all equal, all negative, all zero, none
+
+
+def sa_taps(k, g):
+    """[1,2,k,k] float64: the integers 1 .. k^2 and their negatives, each once, in a seeded order (six bits and a sign at k = 7)."""
+    kk = k * k
+    v = torch.cat([torch.arange(1, kk + 1), -torch.arange(1, kk + 1)]).double()
+    w = v[torch.randperm(2 * kk, generator=g)].view(1, 2, k, k)
+    assert len(torch.unique(w)) == 2 * kk
+    return w
+
+
+def sa_first_max(x):
+    """x [B,C,H,W] (no NaN) -> the channel maximum [B,H,W] and the FIRST channel that holds it (int64), without relying on how a
+    library breaks ties."""
+    m = x.max(dim=1, keepdim=True).values
+    first = ((x == m).cumsum(1) == 0).sum(1)
+    return m[:, 0], first
+
+
+def sa_last_max(x):
+    m = x.max(dim=1, keepdim=True).values
+    return x.shape[1] - 1 - ((x == m).flip(1).cumsum(1) == 0).sum(1)
+
+
+def sa_mean32(x, drop=None):
+    """The kernel's mean: the exact integer channel sum divided ONCE in float32 by float(C).  drop: a channel left out (a mutant)."""
+    C = x.shape[1]
+    s = x.double().sum(1)
+    if drop is not None:
+        s = s - x[:, drop].double()
+    assert float(s.abs().max()) < F32_INT
+    return s.float() / torch.tensor(float(C), dtype=torch.float32)
+
+
+def sa_logits(pool, w):
+    """pool [B,2,H,W], w [1,2,k,k] (float64) -> [B,H,W]: the k x k correlation with zero padding k // 2."""
+    return F.conv2d(pool, w, padding=w.shape[-1] // 2)[:, 0]
+
+
+def sa_gate(x_nhwc, a, dtype):
+    """y = x a: ONE float32 product (x is exact in float32, a is the float32 map [B,H,W]) rounded once to the tensor dtype."""
+    y = x_nhwc.float() * a.float().unsqueeze(-1)
+    return y.bfloat16() if dtype == torch.bfloat16 else y
+
+
+def sa_tile_of(B, H, W):
+    """[B,H,W] int64: the index of the SA_TH x SA_TW tile a pixel lies in, in the order the filter gradient deals them out."""
+    ty, tx = (H + SA_TH - 1) // SA_TH, (W + SA_TW - 1) // SA_TW
+    t = (torch.arange(H) // SA_TH).view(1, H, 1) * tx + (torch.arange(W) // SA_TW).view(1, 1, W)
+    return t + torch.arange(B).view(B, 1, 1) * (ty * tx)
+
+
+def sa_tiles(B, H, W):
+    return B * ((H + SA_TH - 1) // SA_TH) * ((W + SA_TW - 1) // SA_TW)
+
+
+class SaFwdCase:
+    """uh_spatial_attn_fwd on x [B,C,H,W] of wide integers with planted pixels (SA_PLANTS) and w = sa_taps * 2^-shift.
+    Exact, float32: mean (sa_mean32), max, amax (the first maximal channel).  pool = [mean, max] as float64 [B,2,H,W].
+    a64 = sigmoid(correlation) in float64 on that pool; the shift is the smallest that leaves 90 % of the pixels of a64 inside
+    (0.02, 0.98) (asserted).  Where C is a power of two the mean is exact and every term of the correlation is a multiple of
+    2^-shift / C with an absolute sum below 2^24 of them (asserted): the kernel's accumulator is then exact in any order and its map
+    differs from a64 by its sigmoid alone.  For other C the mean is a rounded quotient and the accumulator rounds: the GPU test forms
+    the float64 map from the pool the kernel returned (checked bit for bit first) through `a_from_pool`, and the shift grows until
+    2 k^2 max_p sum |w| |pool| <= SA_ACC_UNITS: the accumulator's 2 k^2 roundings, each at most 2^-24 of a partial sum that never
+    exceeds sum |w| |pool|, then move the map's argument by at most 4 * 2^-24 -- and a by no more, relatively (d ln a = (1 - a) dz).
+    That map is flat (|z| < 0.05); the wide range of the sigmoid is the business of the power-of-two cases, and the map kernel
+    never sees C."""
+
+    def __init__(self, B, H, W, C, k):
+        g = torch.Generator().manual_seed(_seed(B, H, W, C, k, 71))
+        self.shape, self.k, self.npix = (B, H, W, C), k, B * H * W
+        x = wide((B, C, H, W), g)
+        plant = (torch.arange(self.npix).view(B, 1, H, W) % SA_PLANTS).expand(B, C, H, W)
+        ch = torch.arange(C).view(1, C, 1, 1).expand(B, C, H, W)
+        x = torch.where((plant == 1) | (plant == 2) | (plant == 6), x.clamp(max=WIDE_MAX - 1), x)      # the planted channels alone hold the maximum
+        x = torch.where((plant == 6) & (ch == C - 1), torch.tensor(float(WIDE_MAX)), x)
+        if C >= 2:
+            x = torch.where((plant == 1) & ((ch == C // 3) | (ch == C - 1)), torch.tensor(float(WIDE_MAX)), x)
+        if C >= 3:
+            x = torch.where((plant == 2) & ((ch == C // 4) | (ch == C // 2) | (ch == C - 1)), torch.tensor(float(WIDE_MAX)), x)
+        x = torch.where(plant == 3, wide((B, 1, H, W), g).expand(B, C, H, W), x)
+        x = torch.where(plant == 4, -1.0 - wide((B, C, H, W), g).abs().clamp(max=WIDE_MAX - 1), x)
+        x = torch.where(plant == 5, torch.zeros(()), x)
+        self.x = x.contiguous()
+        xd = self.x.double()
+        self.max, self.amax = sa_first_max(xd)
+        self.mean32 = sa_mean32(self.x)
+        self.pool = torch.stack([self.mean32.double(), self.max], 1)
+        if self.npix >= 2 * SA_PLANTS:
+            ties = (xd == self.max.unsqueeze(1)).sum(1)
+            assert bool((ties == 2).any()) or C < 3
+            assert bool((ties == 3).any()) or C < 4
+            assert bool((self.max < 0).any()) and bool(((xd == 0).all(1)).any()) and bool((ties == C).any())
+            assert bool((self.amax == 0).any()) and (C < 4 or bool((self.amax == C // 4).any())) and bool((self.amax == C - 1).any())
+        taps = sa_taps(k, g)
+        self.exact_acc = is_pow2(C)
+        for shift in range(0, 40):
+            self.w = taps * 2.0 ** -shift
+            self.a64 = torch.sigmoid(sa_logits(self.pool, self.w))
+            self.unsaturated = float(((self.a64 > 0.02) & (self.a64 < 0.98)).double().mean())
+            # the roundings of an accumulator that is NOT exact: 2 k^2 additions, each off by at most 2^-24 of a partial sum, and no
+            # partial sum exceeds sum |w| |pool|
+            self.acc_units = 0.0 if self.exact_acc else 2 * k * k * float(sa_logits(self.pool.abs(), self.w.abs()).max())
+            if self.unsaturated >= 0.9 and self.acc_units <= SA_ACC_UNITS:
+                break
+        assert self.unsaturated >= 0.9, f"SaFwdCase: only {self.unsaturated:.2f} of the map lies inside (0.02, 0.98)"
+        assert self.acc_units <= SA_ACC_UNITS
+        self.shift = shift
+        if self.exact_acc:
+            assert torch.equal(self.mean32.double(), xd.mean(1))
+            # per pixel sum |w| |pool| = the correlation of the absolute values: ONE stacked term whose size is the sum of all 2 k^2
+            q = 2.0 ** -shift / C
+            assert torch.equal(self.pool / (1.0 / C), (self.pool / (1.0 / C)).round())
+            require_exact_sum(sa_logits(self.pool.abs(), self.w.abs()).unsqueeze(0), q, 0, "SaFwdCase: the correlation")
+
+    def a_from_pool(self, pool_bhw2):
+        """float64 map from a float32 pool [B,H,W,2] as the kernel returned it."""
+        return torch.sigmoid(sa_logits(pool_bhw2.double().permute(0, 3, 1, 2), self.w))
+
+
+@functools.lru_cache(maxsize=64)
+def sa_fwd_case(B, H, W, C, k):
+    return SaFwdCase(B, H, W, C, k)
+
+
+def sa_gpool(gs, w):
+    """g_pool [B,2,H,W] = the transposed correlation of g_s [B,H,W] with w [1,2,k,k]: the adjoint of sa_logits."""
+    return F.conv_transpose2d(gs.unsqueeze(1), w, padding=w.shape[-1] // 2)
+
+
+def sa_dw(gs, pool, k):
+    """dw [1,2,k,k] = sum_p g_s[p] pool[p + (r - P, s - P)]: the filter gradient of sa_logits, by stock autograd."""
+    w0 = torch.zeros(1, 2, k, k, dtype=torch.float64, requires_grad=True)
+    (dw,) = torch.autograd.grad(F.conv2d(pool, w0, padding=k // 2), [w0], gs.unsqueeze(1))
+    return dw
+
+
+def sa_dx64(dya, gpool, amax, C):
+    """dx = dy a + g_avg / C + [c == amax] g_max in float64; dya [B,C,H,W] or None (the map's backward)."""
+    hot = torch.arange(C).view(1, C, 1, 1) == amax.unsqueeze(1)
+    base = gpool[:, 0:1] / C + hot * gpool[:, 1:2]
+    return base if dya is None else dya + base
+
+
+def sa_dx32(dya, gpool, amax, C, divide=True):
+    """The kernel's last three operations in float32, everything before them in float64: g_avg / C is one division, dy a + that one
+    rounding (dy a is exact, so a fused multiply-add gives the same bits), + g_max at the argmax channel one more.  -> float32."""
+    gavg = gpool[:, 0:1].float()
+    if divide:
+        gavg = gavg / torch.tensor(float(C), dtype=torch.float32)
+    t = gavg.expand(-1, C, -1, -1) if dya is None else dya.float() + gavg
+    hot = torch.arange(C).view(1, C, 1, 1) == amax.unsqueeze(1)
+    return torch.where(hot, t + gpool[:, 1:2].float(), t)
+
+
+class SaBwdCase:
+    """uh_spatial_attn_bwd with SYNTHETIC forward results (the call takes pool, amax and a as inputs): a from SA_A_VALUES, pool
+    integers in [-7, 7], amax any channel (0 and C - 1 forced), x wide, w = sa_taps / 64.
+      mode "gate": dy ternary of a density that keeps d = sum_c x dy within +-256 (asserted); mode "map": d = ga, ternary per pixel.
+      g_s = d a (1 - a): an integer of 9 bits times 64ths -- exact.  g_pool and dw: every term a multiple of 2^-12 resp. 2^-6 with an
+      absolute sum below 2^24 of them (asserted with require_exact_sum on the sums of absolute terms): exact in any order.
+      dx: sa_dx32, asserted equal to pure float64 where C is a power of two (every value is then exact).
+    p: density of dy / ga (None: 24 / C for the gate, 1/2 for the map); a_half: a = 1/2 everywhere; plant_tiles: force a non-zero ga
+    into every tile from that index on (the filter gradient's second round)."""
+
+    def __init__(self, B, H, W, C, k, mode, p=None, a_half=False, plant_tiles=None):
+        assert mode in ("gate", "map")
+        g = torch.Generator().manual_seed(_seed(B, H, W, C, k, 73, mode == "gate"))
+        self.shape, self.k, self.mode, self.npix = (B, H, W, C), k, mode, B * H * W
+        P = k // 2
+        self.a = torch.tensor(SA_A_VALUES, dtype=torch.float64)[torch.randint(0, len(SA_A_VALUES), (B, H, W), generator=g)]
+        if a_half:
+            self.a = torch.full((B, H, W), 0.5, dtype=torch.float64)
+        self.pool = torch.randint(-7, 8, (B, 2, H, W), generator=g).double()
+        self.amax = torch.randint(0, C, (B, H, W), generator=g)
+        self.amax.view(-1)[0] = C - 1
+        self.amax.view(-1)[-1] = 0
+        self.w = sa_taps(k, g) * SA_Q_W
+        self.x = wide((B, C, H, W), g)
+        if mode == "gate":
+            self.dy = ternary((B, C, H, W), min(1.0, 24.0 / C) if p is None else p, g)
+            self.ga = None
+            terms = self.x.double() * self.dy.double()
+            require_exact_sum(terms, 1.0, 1, "SaBwdCase: sum_c x dy")
+            self.d = terms.sum(1)
+            assert float(self.d.abs().max()) <= SA_D_MAX, f"SaBwdCase: |sum_c x dy| = {float(self.d.abs().max())} > {SA_D_MAX}"
+            dya = self.dy.double() * self.a.unsqueeze(1)
+        else:
+            self.dy = None
+            self.ga = ternary((B, H, W), 0.5 if p is None else p, g)
+            if plant_tiles is not None:
+                tile = sa_tile_of(B, H, W)
+                for t in range(plant_tiles, sa_tiles(B, H, W)):
+                    at = (tile == t).nonzero()[0]
+                    self.ga[tuple(at.tolist())] = 1.0 if t % 2 else -1.0
+            self.d = self.ga.double()
+            dya = None
+        assert bool((self.d != 0).any())
+        self.gs = self.d * self.a * (1 - self.a)
+        assert torch.equal(self.gs / SA_Q_GS, (self.gs / SA_Q_GS).round()) and torch.equal(self.gs.float().double(), self.gs)
+        assert torch.equal(self.w / SA_Q_W, (self.w / SA_Q_W).round())
+        # the sums of absolute terms, formed as the same contractions of the absolute values: one stacked term each
+        require_exact_sum(sa_gpool(self.gs.abs(), self.w.abs()).unsqueeze(0), SA_Q_GS * SA_Q_W, 0, "SaBwdCase: g_pool")
+        require_exact_sum(sa_dw(self.gs.abs(), self.pool.abs(), k).unsqueeze(0), SA_Q_GS, 0, "SaBwdCase: dw")
+        self.gpool = sa_gpool(self.gs, self.w)
+        self.dw = sa_dw(self.gs, self.pool, k)
+        assert bool((self.dw != 0).any()) and bool((self.gpool != 0).any())
+        self.dx64 = sa_dx64(dya, self.gpool, self.amax, C)
+        self.dx = sa_dx32(dya, self.gpool, self.amax, C)
+        self.dya = dya
+        if is_pow2(C):
+            terms = [self.gpool[:, 0:1].expand(-1, C, -1, -1) / C, self.gpool[:, 1:2].expand(-1, C, -1, -1)]
+            if dya is not None:
+                terms.append(dya)
+            require_exact_sum(torch.stack(terms), SA_Q_GS * SA_Q_W / C, 0, "SaBwdCase: dx")
+            assert torch.equal(self.dx.double(), self.dx64), "the float32 restatement of dx must BE float64 where C is a power of two"
+
+    def ws(self):
+        """The workspace as the kernel leaves it: g_pool [npix][2], then g_s [npix]; float32."""
+        return torch.cat([self.gpool.permute(0, 2, 3, 1).reshape(-1), self.gs.reshape(-1)]).float()
+
+
+@functools.lru_cache(maxsize=128)
+def sa_bwd_case(B, H, W, C, k, mode, p=None, a_half=False, plant_tiles=None):
+    return SaBwdCase(B, H, W, C, k, mode, p, a_half, plant_tiles)

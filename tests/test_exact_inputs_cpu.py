@@ -403,3 +403,191 @@ def test_stem_case_mutations_fail(family):
         assert _differs(E.stem_dw(c.dy, x).float(), c.dw.float())
         # dy passed through fp16 on its way to bf16 (a double rounding)
         assert _differs(E.stem_dw(c.dy.float().half().float().bfloat16().double(), x).float(), c.dw.float())
+
+
+# ================================================================================================ spatial attention
+# tests/test_gpu_exact_spatial_attention.py: (a) the launch forms its cases were chosen for are what uh_spatial_attn_plan answers, and
+# the query follows the rule restated here; (b) SaFwdCase and SaBwdCase meet their conditions at every shape that file runs; (c)
+# float32 sums in a shuffled order give the float64 values; (d) each mutation of the reference changes a compared value.
+import test_gpu_exact_spatial_attention as S  # noqa: E402
+
+SA_SHAPES = sorted({(*S.SHAPE, f[1]) for f in S.FORMS} | {(2, *hw, S.GEOMETRY_C) for hw in S.GEOMETRY} | {(*S.SHAPE, S.PITCH_C)})
+SA_TWO_STEPS = sorted({(C, V * G) for _, C, form, (V, G, steps) in S.FORMS if steps == 2})      # (C, channels of the first step)
+
+
+def test_spatial_attention_plan_query_and_the_forms_of_the_cases():
+    import ctypes
+    import unet_amd  # noqa: F401
+    from unet_amd._lib import LIB
+    assert len(S.check_forms()) == 12 and SA_TWO_STEPS == [(70, 64), (260, 256), (520, 512)]
+    for dt in (F32, BF16):
+        vec = 8 if dt == BF16 else 4
+        for aligned in (True, False):
+            for C in list(range(1, 132)) + [255, 256, 257, 260, 264, 511, 512, 513, 520, 1024, 4100]:
+                V = vec if aligned and C % vec == 0 else 1
+                nv = -(-C // V)
+                G = 1
+                while G < nv and G < 64:
+                    G *= 2
+                assert S.plan(C, dt, aligned) == (V, G, -(-nv // G)), (dt, aligned, C)
+    out = (ctypes.c_int64 * 3)()
+    assert LIB.query("uh_spatial_attn_plan", 0, 0, 1, ctypes.addressof(out)) < 0
+    assert LIB.query("uh_spatial_attn_plan", 8, 7, 1, ctypes.addressof(out)) < 0
+    assert LIB.query("uh_spatial_attn_plan", 8, 0, 1, None) < 0
+
+
+@pytest.mark.parametrize("shape", SA_SHAPES, ids=_ids)
+def test_spatial_attention_cases_meet_their_conditions(shape):
+    B, H, W, C = shape
+    for k in S.KS:
+        c = E.sa_fwd_case(*shape, k)                 # asserts: the plants, 90 % of the map unsaturated, the accumulator exact or bounded
+        assert _bf16_holds(c.x) and float(c.x.abs().max()) <= E.WIDE_MAX
+        taps = c.w * 2.0 ** c.shift
+        assert torch.equal(taps, taps.round()) and float(taps.abs().max()) == k * k and len(torch.unique(c.w)) == 2 * k * k
+        assert c.exact_acc == E.is_pow2(C) and c.unsaturated >= 0.9 and c.acc_units <= E.SA_ACC_UNITS
+        assert torch.equal(torch.max(c.x, dim=1).indices, c.amax) and torch.equal(torch.max(c.x, dim=1).values.double(), c.max)
+        if c.exact_acc and c.npix > 100:
+            assert float(c.a64.min()) < 0.1 and float(c.a64.max()) > 0.9          # the exact cases walk the sigmoid's range
+        for mode in ("gate", "map"):
+            b = E.sa_bwd_case(*shape, k, mode)       # asserts: |d| <= 256, g_s exact, g_pool / dw / dx order-free, dx32 == dx64 where C = 2^n
+            assert set(b.a.unique().tolist()) <= set(E.SA_A_VALUES) and int(b.amax.max()) == C - 1 and int(b.amax.min()) == 0
+            assert _bf16_holds(b.x, b.pool.float()) and (b.dy is None or _bf16_holds(b.dy))
+            for v in (b.gs, b.gpool, b.dw):
+                assert torch.equal(v.float().double(), v)
+            if C > 1 and not E.is_pow2(C) and b.npix > 100:
+                assert _differs(b.dx.double(), b.dx64)                             # ... and the roundings are exercised elsewhere
+
+
+@pytest.mark.parametrize("k", S.KS)
+def test_spatial_attention_big_case_reaches_the_second_round(k):
+    B, H, W, C = S.BIG
+    c = S.big_case(k)
+    tile = E.sa_tile_of(B, H, W)
+    assert E.sa_tiles(B, H, W) == 1032 == int(tile.max()) + 1 and B * H * W < 150000
+    assert bool((c.a == 0.5).all()) and 0.03 < float((c.ga != 0).float().mean()) < 0.1
+    for t in range(E.SA_DW_BLOCKS, 1032):
+        assert bool((c.gs[tile == t] != 0).any())
+    # one tile past the 1024th dropped, and the whole second round dropped
+    for keep in (tile != 1030, tile < E.SA_DW_BLOCKS):
+        assert _differs(E.sa_dw(c.gs * keep, c.pool, k).float(), c.dw.float())
+
+
+def _serial32(terms, dim, g):
+    """float32 accumulation of `terms` along `dim`, one term at a time, in a seeded shuffled order."""
+    t = terms.float().movedim(dim, 0)
+    assert torch.equal(t.double(), terms.movedim(dim, 0).double())
+    acc = torch.zeros_like(t[0])
+    for i in torch.randperm(t.shape[0], generator=g).tolist():
+        acc = acc + t[i]
+    return acc.double()
+
+
+@pytest.mark.parametrize("k", S.KS)
+def test_spatial_attention_float32_in_a_shuffled_order_equals_float64(k):
+    g = torch.Generator().manual_seed(5)
+    B, H, W = S.SHAPE
+    P = k // 2
+    c = E.sa_fwd_case(B, H, W, 260, k)
+    assert torch.equal(_serial32(c.x, 1, g), c.x.double().sum(1))
+    c = E.sa_fwd_case(B, H, W, 8, k)
+    terms = F.unfold(c.pool, k, padding=P) * c.w.view(1, -1, 1)                     # [B, 2 k^2, H W]
+    assert torch.equal(_serial32(terms, 1, g).view(B, H, W), E.sa_logits(c.pool, c.w))
+    b = E.sa_bwd_case(B, H, W, 260, k, "gate")
+    assert torch.equal(_serial32(b.x.double() * b.dy.double(), 1, g), b.d)
+    for ch in (0, 1):
+        terms = F.unfold(b.gs.unsqueeze(1), k, padding=P) * b.w[0, ch].flip(0, 1).reshape(1, -1, 1)
+        assert torch.equal(_serial32(terms, 1, g).view(B, H, W), b.gpool[:, ch])
+    terms = (F.unfold(b.pool, k, padding=P) * b.gs.view(B, 1, -1)).permute(1, 0, 2).reshape(2 * k * k, -1)
+    assert torch.equal(_serial32(terms, 1, g).view(1, 2, k, k), b.dw)
+
+
+def _rel(a, ref):
+    return float(((a - ref).abs() / ref).max())
+
+
+def _stacked(t):
+    """[B,C,H,W] -> [1,C,B*H,W]: the images one below the other, as they lie in memory."""
+    B, C, H, W = t.shape
+    return t.permute(1, 0, 2, 3).reshape(1, C, B * H, W)
+
+
+@pytest.mark.parametrize("k", S.KS)
+@pytest.mark.parametrize("hw", S.GEOMETRY, ids=_ids)
+def test_a_halo_that_reads_the_other_image_fails(hw, k):
+    """pool, g_s and the workspace are contiguous over the batch: a halo without the image border's test reads the neighbouring
+    image's rows.  At every extent of the geometry test that moves the map beyond its tolerance, and g_pool and dw exactly."""
+    H, W = hw
+    c = E.sa_fwd_case(2, H, W, S.GEOMETRY_C, k)
+    wrong = torch.sigmoid(E.sa_logits(_stacked(c.pool), c.w)).view(2, H, W)
+    assert _rel(wrong, c.a64) > 1000 * 8 * S.U
+    for mode in ("gate", "map"):
+        b = E.sa_bwd_case(2, H, W, S.GEOMETRY_C, k, mode)
+        assert _differs(E.sa_gpool(_stacked(b.gs.unsqueeze(1))[:, 0], b.w).view(2, 2, H, W).transpose(0, 1).float(), b.gpool.float())
+        assert _differs(E.sa_dw(_stacked(b.gs.unsqueeze(1))[:, 0], _stacked(b.pool), k).float(), b.dw.float())
+
+
+@pytest.mark.parametrize("k", S.KS)
+def test_spatial_attention_case_mutations_fail(k):
+    B, H, W = S.SHAPE
+    C = 8
+    P = k // 2
+    c = E.sa_fwd_case(B, H, W, C, k)
+    xd = c.x.double()
+    # a halo column dropped at the tile seam: the tile that starts at column 32 misses column 31
+    seam = E.SA_TW
+    right = (torch.arange(W) >= seam).view(1, 1, W)
+    cut = c.pool.clone()
+    cut[..., seam - 1] = 0
+    wrong = torch.where(right, torch.sigmoid(E.sa_logits(cut, c.w)), c.a64)
+    assert _rel(wrong, c.a64) > 1000 * 8 * S.U and torch.equal(wrong[..., :seam], c.a64[..., :seam])
+    # the last maximum instead of the first; a maximum started at 0
+    assert _differs(E.sa_last_max(xd).int(), c.amax.int()) and bool((c.amax <= E.sa_last_max(xd)).all())
+    assert _differs(c.max.clamp_min(0).float(), c.max.float())
+    wrong = torch.sigmoid(E.sa_logits(torch.stack([c.mean32.double(), c.max.clamp_min(0)], 1), c.w))
+    assert _rel(wrong, c.a64) > 1000 * 8 * S.U
+    # y rounded twice through bf16 (the map, then the product), and an fp32 y passed through bf16
+    a32 = c.a64.float()
+    x = E.nhwc(c.x)
+    twice = (x * a32.bfloat16().float().unsqueeze(-1)).bfloat16()
+    assert _differs(twice, E.sa_gate(x, a32, BF16)) and _differs(E.sa_gate(x, a32, F32).bfloat16().float(), E.sa_gate(x, a32, F32))
+    for mode in ("gate", "map"):
+        b = E.sa_bwd_case(B, H, W, C, k, mode)
+        # the same seam in the backward: g_pool right of the seam misses g_s of column 31, dw of that tile misses pool's column 31
+        gs_cut, pool_cut = b.gs.clone(), b.pool.clone()
+        gs_cut[..., seam - 1] = 0
+        pool_cut[..., seam - 1] = 0
+        assert _differs(torch.where(right.unsqueeze(1), E.sa_gpool(gs_cut, b.w), b.gpool).float(), b.gpool.float())
+        assert _differs((E.sa_dw(b.gs * right, pool_cut, k) + E.sa_dw(b.gs * ~right, b.pool, k)).float(), b.dw.float())
+        # correlation instead of transposed correlation
+        corr = F.conv2d(b.gs.unsqueeze(1), b.w.transpose(0, 1), padding=P)
+        assert _differs(corr.float(), b.gpool.float())
+        for dt in (F32, BF16):
+            want = b.dx.bfloat16() if dt == BF16 else b.dx
+            assert _differs(E.expected(E.sa_dx64(b.dya, corr, b.amax, C), dt), want)
+            # g_avg not divided by C
+            undivided = E.sa_dx32(b.dya, b.gpool, b.amax, C, divide=False)
+            assert _differs(undivided.bfloat16() if dt == BF16 else undivided, want)
+            # the max's gradient on another channel
+            other = E.sa_dx32(b.dya, b.gpool, (b.amax + 1) % C, C)
+            assert _differs(other.bfloat16() if dt == BF16 else other, want)
+        # a for a (1 - a)
+        gs_a = b.d * b.a
+        assert _differs(gs_a.float(), b.gs.float()) and _differs(E.sa_dw(gs_a, b.pool, k).float(), b.dw.float())
+        # one pixel dropped from dw
+        hole = b.gs.clone()
+        hole[tuple((b.gs != 0).nonzero()[0].tolist())] = 0
+        assert _differs(E.sa_dw(hole, b.pool, k).float(), b.dw.float())
+
+
+@pytest.mark.parametrize("C,first", SA_TWO_STEPS)
+def test_a_channel_of_the_second_step_dropped_fails(C, first):
+    """The forms whose lanes take a second step: the first channel past the first step left out of the channel sum, of the maximum
+    and of sum_c x dy."""
+    c = E.sa_fwd_case(*S.SHAPE, C, 7)
+    assert first < C and _differs(E.sa_mean32(c.x, drop=first), c.mean32)
+    head = c.x[:, :first].double()
+    assert _differs(E.sa_first_max(head)[0].float(), c.max.float()) and _differs(E.sa_first_max(head)[1].int(), c.amax.int())
+    b = E.sa_bwd_case(*S.SHAPE, C, 7, "gate")
+    d = b.d - b.x[:, first].double() * b.dy[:, first].double()
+    assert _differs((d * b.a * (1 - b.a)).float(), b.gs.float())
+    assert bool((b.amax >= first).any())             # the max's gradient lands in the second step too

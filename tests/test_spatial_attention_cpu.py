@@ -2,6 +2,8 @@
 has the reference's state_dict layout and initialisation order, the C ABI declares the spatial-attention entry points, the
 product path refuses CPU tensors, and the torch restatement of the attention map that the GPU tests compare against is
 pinned to the reference's own SpatialAttention."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -91,6 +93,10 @@ def test_spatial_attention_prototypes_parse():
     LIB.load()
     assert LIB.query("uh_spatial_attn_dw_nblk", 8, 512, 512) == 1024
     assert LIB.query("uh_spatial_attn_dw_nblk", 1, 1, 1) == 1
+    assert protos["uh_spatial_attn_plan"] == ("int", ["int", "int", "int", "ptr"])
+    out = (ctypes.c_int64 * 3)()
+    assert LIB.query("uh_spatial_attn_plan", 64, 1, 1, ctypes.addressof(out)) == 0 and list(out) == [8, 8, 1]
+    assert LIB.query("uh_spatial_attn_plan", 64, 1, 0, ctypes.addressof(out)) == 0 and list(out) == [1, 64, 1]
     # shape checks run on the host before anything is enqueued
     with pytest.raises(RuntimeError, match="k is 3 or 7"):
         LIB.call("uh_spatial_attn_fwd", 16, 8, 16, 5, 16, 16, 16, None, 8, 1, 4, 4, 8, 0, None)

@@ -25,6 +25,18 @@ static inline int sa_group(int C, int V) {
     return g;
 }
 
+// The launch form of the channel reductions (sa_pool_kernel, sa_gs_kernel) and of the flat passes (gate, dx): V channels per
+// lane and step (one 16-byte vector where every tensor of the call allows it, else 1), G lanes per pixel, and the steps a lane
+// takes to cover C.  The launches and uh_spatial_attn_plan both ask here.
+struct SaPlan { int V, G, steps; };
+
+static inline SaPlan sa_plan(int C, int vec, bool vec_ok) {
+    const int V = vec_ok && C % vec == 0 ? vec : 1;
+    const int G = sa_group(C, V);
+    const int nv = (C + V - 1) / V;
+    return SaPlan{V, G, (nv + G - 1) / G};
+}
+
 static inline unsigned sa_grid(int64_t npix, int G) {
     return (unsigned)((npix * G + SA_BLOCK - 1) / SA_BLOCK);
 }
@@ -300,8 +312,9 @@ static void sa_launch_fwd(const void* x, int ldx, float* pool, int* amax, const 
     const int64_t npix = (int64_t)B * H * W;
     const dim3 tiles((W + SA_TW - 1) / SA_TW, (H + SA_TH - 1) / SA_TH, B);
     UH_DISPATCH_DT(dt, T, {
-        if (uh_vec_ok<T>(x, ldx, C) && (!y || uh_vec_ok<T>(y, ldy, C))) {
-            const int G = sa_group(C, VEC);
+        const SaPlan p = sa_plan(C, VEC, uh_vec_ok<T>(x, ldx, C) && (!y || uh_vec_ok<T>(y, ldy, C)));
+        const int G = p.G;
+        if (p.V == VEC) {
             hipLaunchKernelGGL((sa_pool_kernel<T, VEC>), dim3(sa_grid(npix, G)), dim3(SA_BLOCK), 0, st, (const T*)x, ldx, pool,
                                amax, npix, C, G);
             hipLaunchKernelGGL((sa_map_tile_kernel<K>), tiles, dim3(SA_BLOCK), 0, st, pool, w, a, H, W);
@@ -309,7 +322,6 @@ static void sa_launch_fwd(const void* x, int ldx, float* pool, int* amax, const 
                 hipLaunchKernelGGL((sa_gate_kernel<T, VEC>), dim3(sa_flat_grid(npix * (C / VEC))), dim3(SA_BLOCK), 0, st,
                                    (const T*)x, ldx, a, (T*)y, ldy, npix, C);
         } else {
-            const int G = sa_group(C, 1);
             hipLaunchKernelGGL((sa_pool_kernel<T, 1>), dim3(sa_grid(npix, G)), dim3(SA_BLOCK), 0, st, (const T*)x, ldx, pool,
                                amax, npix, C, G);
             hipLaunchKernelGGL((sa_map_tile_kernel<K>), tiles, dim3(SA_BLOCK), 0, st, pool, w, a, H, W);
@@ -329,8 +341,9 @@ static void sa_launch_bwd(const void* dy, int lddy, const float* ga, const void*
     float* gs = ws + 2 * npix;          // [npix]
     const dim3 tiles((W + SA_TW - 1) / SA_TW, (H + SA_TH - 1) / SA_TH, B);
     UH_DISPATCH_DT(dt, T, {
-        const bool vec = uh_vec_ok<T>(dx, lddx, C) && (!dy || (uh_vec_ok<T>(dy, lddy, C) && uh_vec_ok<T>(x, ldx, C)));
-        const int G = ga ? 1 : sa_group(C, vec ? VEC : 1);
+        const SaPlan p = sa_plan(C, VEC, uh_vec_ok<T>(dx, lddx, C) && (!dy || (uh_vec_ok<T>(dy, lddy, C) && uh_vec_ok<T>(x, ldx, C))));
+        const bool vec = p.V == VEC;
+        const int G = ga ? 1 : p.G;         // the map's gradient is given per pixel: nothing to reduce
         if (vec)
             hipLaunchKernelGGL((sa_gs_kernel<T, VEC>), dim3(sa_grid(npix, G)), dim3(SA_BLOCK), 0, st, (const T*)dy, lddy,
                                (const T*)x, ldx, ga, a, gs, npix, C, G);
@@ -357,6 +370,15 @@ static bool sa_shape_ok(int B, int H, int W, int C, int k) {
 extern "C" int uh_spatial_attn_dw_nblk(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
     return sa_dw_nblk(B, H, W);
+}
+
+extern "C" int uh_spatial_attn_plan(int C, int dt, int aligned, int64_t* out) {
+    UH_REQUIRE(C > 0 && out && (dt == UH_F32 || dt == UH_BF16), "uh_spatial_attn_plan: bad args");
+    const SaPlan p = sa_plan(C, dt == UH_BF16 ? 8 : 4, aligned != 0);
+    out[0] = p.V;
+    out[1] = p.G;
+    out[2] = p.steps;
+    return UH_OK;
 }
 
 extern "C" int uh_spatial_attn_fwd(const void* x, int ldx, const float* w, int k, float* pool, int* amax, float* a, void* y,
