@@ -16,8 +16,11 @@ Where a kernel rounds by design the inputs are narrowed, never the comparison:
   * bf16x3 drops the low x low product: one operand of each product is ternary, so that term is zero.
 The pixel passes (BatchNorm + ReLU apply / backward, the pool and head tails, max-pool) and the recomputed stem (uh_stem_*) are
 held to float64 in the same way, on the dyadic family, by test_gpu_exact_pixel.py, which also calls them with pixel pitches.
-Not covered here or there: the BatchNorm statistics of the conv epilogue (divisions; test_gpu_ops.py, test_gpu_bnsum.py; the
-stem's statistics rows have a derived bound in test_gpu_exact_pixel.py), the bilinear pair (weights that are no dyadic numbers:
+The BatchNorm statistics of the conv epilogue (divisions) are held row by row by test_gpu_bn_stats.py: the rows every forward form
+here writes (counts exactly, moments within bounds derived from each producer's arithmetic, bit for bit on a family made for it),
+uh_bn_finalize and uh_bn_eval_coeffs on synthetic rows, and the chain against float64 BatchNorm2d; the recomputed stem's rows
+(uh_stem_stats) in test_gpu_exact_pixel.py.  Not covered here or there: the backward rows of uh_conv3x3_dgrad_bnsum
+(test_gpu_bnsum.py), the bilinear pair (weights that are no dyadic numbers:
 test_gpu_ops.py, and pitched against dense calls in test_gpu_exact_pixel.py), the narrow entry points (held bit for bit to the
 padded form there), tensors past 2 GiB (forward code 5, test_gpu_large.py), the optimizer (held to float64, one step and twenty
 chained, by test_gpu_ema.py).  The default loss (csrc/loss.hip) is held to float64 op by op, with derived bounds, by
