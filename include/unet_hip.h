@@ -596,6 +596,34 @@ int uh_focal_tversky_grad(const float* logits, const int64_t* mask, int mask_div
                           float gamma, double alpha, double beta, const int* classes, int K, const float* sums, const float* gscale,
                           float* dlogits, uh_stream stream);
 
+/* ---- knowledge distillation  (no counterpart in the reference; DESIGN.md section 3 "Distillation"; csrc/distill_loss.hip) ----
+ * The KL term between a teacher's and the student's temperature-softened class probabilities (Hinton et al.).  student, teacher:
+ * DEVICE fp32 logits of the same head, [npix][ncls] for a softmax head (ncls = 2..8) or [npix] for the one-channel head
+ * (ncls = 1), which is the two-class form on (0, z) and (0, v).  No labels.  With temperature T > 0, weight w > 0, n_mean the
+ * pixel count of the mean (that of the GLOBAL batch when sharded), q = softmax(teacher / T) and p = softmax(student / T):
+ *   kd       = T^2 / n_mean * sum_x sum_c q_c (log q_c - log p_c)
+ *   agree    = 1 / n_mean * sum_x [argmax student = argmax teacher]   (first maximum; a diagnostic without gradient)
+ * Per pixel the KL is formed from the shifted, scaled logits a_c = (v_c - max v) * (1 / T), b_c = (z_c - max z) * (1 / T) as
+ * sum_c q_c (a_c - b_c) - (log1p(rest_v) - log1p(rest_z)), the same instructions on both tensors: q_c = 0 contributes an exact 0,
+ * student == teacher gives kd = 0.0 and a gradient of +0.0 exactly, and nothing overflows at logits of magnitude 100.
+ * UH_EINVAL before any launch for a null pointer, ncls outside 1..8, npix < 1, a non-finite or non-positive T, w or n_mean, or a
+ * workspace that is too small.
+ * uh_distill_nsums:  the length of the sums vector, 2.
+ * uh_distill_sums:   sums DEVICE fp32 [2] = { sum_x KL, sum_x agree } of this call's pixels; after a sum over data-parallel ranks
+ *   they are the global batch's.  ws: uh_loss_ws_bytes(npix).
+ * uh_distill_finish: out DEVICE fp32 [3] = { w kd, kd, agree } from the sums and n_mean, in double.
+ * uh_distill_grad:   WRITES dlogits (every element, the student's layout) = gscale[0] * w T / n_mean * (p - q) (gscale DEVICE or
+ *   NULL = 1); the one-channel head gets the k = 1 component.  The component of the student's largest class is formed as
+ *   minus the sum of the others (sum_c (p_c - q_c) = 0), which keeps its digits where both sides are sure of that class.
+ * No floating-point atomics: a call gives the same bits every time, and a pixel's gradient depends on its own two logit vectors,
+ * n_mean, T, w and gscale only. */
+int uh_distill_nsums(void);
+int uh_distill_sums(const float* student, const float* teacher, int64_t npix, int ncls, double T, float* sums, void* ws,
+                    size_t ws_bytes, uh_stream stream);
+int uh_distill_finish(const float* sums, double n_mean, double T, double w, float* out, uh_stream stream);
+int uh_distill_grad(const float* student, const float* teacher, int64_t npix, int ncls, double n_mean, double T, double w,
+                    const float* gscale, float* dlogits, uh_stream stream);
+
 /* ---- input pipeline, device stage (utils/data_loading.py:65-132, train.py:113-114) ---------------------------
  * What BasicDataset.__getitem__ does to a DECODED image / mask pair, for a whole batch in one pass:
  *   img_u8   DEVICE uint8 [B][Hin][Win][C] (C = 1..4, what np.asarray(PIL image) holds), or NULL (masks only)

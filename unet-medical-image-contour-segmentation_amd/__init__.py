@@ -7,6 +7,7 @@ from .utils.boundary_loss import boundary_loss  # noqa: F401
 from .utils.connected_component_loss import connected_component_loss  # noqa: F401
 from .utils.surface_loss import surface_loss, surface_distance_map  # noqa: F401
 from .utils.focal_loss import LossConfig, focal_tversky_loss  # noqa: F401
+from .utils.distill import DistillConfig, Distiller, distill_loss  # noqa: F401
 from .train import FusedRMSprop, seg_loss, train_step, TrainStepper, GraphedTrainStepper, EmaConfig  # noqa: F401
 from .evaluate import evaluate  # noqa: F401
 from .utils.contour_metrics import contour_metrics, ContourMetrics  # noqa: F401

@@ -2313,3 +2313,68 @@ class FocalTverskyLossFn(Function):
         if dtype != torch.float32:
             dl = dl.to(dtype)
         return (dl,) + (None,) * 9
+
+
+# ----------------------------------------------------------------------------- knowledge distillation (csrc/distill_loss.hip)
+DISTILL_MAX_CLASSES = 8
+
+
+class DistillLossFn(Function):
+    """The distillation term of DESIGN.md section 3 in one node: student and teacher logits of the same shape, [B,H,W] (the
+    one-channel head: two classes on the logits (0, z)) or NHWC [B,H,W,C] (softmax), temperature T > 0, weight w > 0.  Returns
+    (w * kd, kd, agree) as 0-dim tensors; only the first carries gradient, and only to the student: the teacher's logits are
+    detached.  `reduce_sums` sums the two partial sums over data-parallel ranks between the two passes; value and agreement are
+    then those of the GLOBAL batch, n_mean = round(B H W world), and the gradient needs no collective.  Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, student_logits, teacher_logits, T: float, w: float, reduce_sums=None, world: float = 1):
+        _require_gpu(student_logits, "student logits")
+        _require_gpu(teacher_logits, "teacher logits")
+        if student_logits.dim() not in (3, 4) or tuple(student_logits.shape) != tuple(teacher_logits.shape):
+            raise RuntimeError(f"distillation expects student and teacher logits of one shape, [B,H,W] or [B,H,W,C], got "
+                               f"{tuple(student_logits.shape)} and {tuple(teacher_logits.shape)}")
+        ncls = 1 if student_logits.dim() == 3 else int(student_logits.shape[-1])
+        if ncls == 1 and student_logits.dim() == 4:
+            raise RuntimeError("distillation: the one-channel head passes its logits as [B,H,W]")
+        if not 1 <= ncls <= DISTILL_MAX_CLASSES:
+            raise ValueError(f"distillation: heads of 1 to {DISTILL_MAX_CLASSES} classes, got {ncls}")
+        T, w = float(T), float(w)
+        if not (math.isfinite(T) and T > 0.0):
+            raise ValueError(f"distillation: the temperature must be finite and > 0, got {T}")
+        if not (math.isfinite(w) and w > 0.0):
+            raise ValueError(f"distillation: the weight must be finite and > 0, got {w}")
+        lg = student_logits.detach().float().contiguous()
+        tl = teacher_logits.detach().float().contiguous()
+        B, H, W = lg.shape[:3]
+        npix = B * H * W
+        n_mean = float(round(npix * world))
+        dev = lg.device
+        sums = torch.empty(LIB.query("uh_distill_nsums"), dtype=torch.float32, device=dev)
+        ws = loss_workspace(dev)
+        LIB.call("uh_distill_sums", lg.data_ptr(), tl.data_ptr(), npix, ncls, T, sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        if reduce_sums is not None:
+            reduce_sums(sums)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        LIB.call("uh_distill_finish", sums.data_ptr(), n_mean, T, w, out.data_ptr(), _stream())
+        ctx.save_for_backward(lg, tl)
+        ctx.meta = (npix, ncls, n_mean, T, w, student_logits.shape, student_logits.dtype)
+        ctx.set_materialize_grads(False)
+        weighted, kd, agree = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(kd, agree)
+        return weighted, kd, agree
+
+    @staticmethod
+    def backward(ctx, g_weighted, *_unused):
+        if g_weighted is None:
+            return (None,) * 6
+        lg, tl = ctx.saved_tensors
+        npix, ncls, n_mean, T, w, shape, dtype = ctx.meta
+        g0 = g_weighted.reshape(1)
+        if g0.dtype != torch.float32 or not g0.is_contiguous():
+            g0 = g0.contiguous().float()
+        dl = torch.empty_like(lg)
+        LIB.call("uh_distill_grad", lg.data_ptr(), tl.data_ptr(), npix, ncls, n_mean, T, w, g0.data_ptr(), dl.data_ptr(), _stream())
+        dl = dl.view(shape)
+        if dtype != torch.float32:
+            dl = dl.to(dtype)
+        return (dl,) + (None,) * 5

@@ -42,6 +42,21 @@ def _add_surface(terms: Dict[str, torch.Tensor], lg: torch.Tensor, true_masks: t
     return terms
 
 
+def _add_distill(terms: Dict[str, torch.Tensor], masks_pred: torch.Tensor, teacher_logits: Optional[torch.Tensor], n_classes: int,
+                 distill, reduce_sums, world) -> Dict[str, torch.Tensor]:
+    """total += w * kd (DESIGN.md section 3 "Distillation"); `kd` and `kd_agree` join the reported terms.  The fused loss's NaN
+    flag was formed without the new term and is dropped, as _add_surface drops it."""
+    from .utils.distill import distill_terms
+    if teacher_logits is None:
+        raise ValueError("seg_loss: distill=... needs teacher_logits (Distiller.teacher_logits(images))")
+    weighted, kd, agree = distill_terms(masks_pred, teacher_logits, n_classes, distill, reduce_sums=reduce_sums, world=world)
+    terms["loss"] = terms["loss"] + weighted
+    terms["kd"] = kd
+    terms["kd_agree"] = agree
+    terms.pop("nan_flag", None)
+    return terms
+
+
 def _focal_tversky_terms(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int, loss, w_b: float, reduce_sums,
                          world) -> Dict[str, torch.Tensor]:
     """The loss node of seg_loss with `loss` (a LossConfig): focal + tversky (DESIGN.md section 3 "Focal / Tversky loss") in
@@ -65,14 +80,21 @@ def _focal_tversky_terms(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_c
 
 def seg_loss(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int, *, reduce_sums=None, world: float = 1,
              boundary_weight: Optional[float] = None, surface_weight: float = 0.0, surface_classes=None,
-             loss=None) -> Dict[str, torch.Tensor]:
+             loss=None, distill=None, teacher_logits: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """train.py:118-142.  masks_pred: logits [B,n_classes,H,W] (as returned by the model);
     true_masks: int64 [B,H,W] with the dataset's values {0,1,2,..} (NOT yet // 2).
     surface_weight != 0 adds surface_weight * surface loss over `surface_classes` (default: the class evaluate scores) and the
     term "surface"; with 0 nothing else is launched and the result is what it is without the option.
     loss (a utils.focal_loss.LossConfig or its spec string; default None: the code path, the launches and the results are what
     they are without the option): the class-weighted focal + Tversky node replaces the CE + Dice pair, and the terms carry
-    "focal" and "tversky" in place of "ce" / "bce" and "dice"; the boundary and surface terms stay on top."""
+    "focal" and "tversky" in place of "ce" / "bce" and "dice"; the boundary and surface terms stay on top.
+    distill (a utils.distill.DistillConfig or its spec string; default None: nothing is launched, allocated or imported for it)
+    with teacher_logits (the teacher's logits for the same images, shaped like masks_pred): adds w * kd after the surface term,
+    and the terms carry "kd" and "kd_agree"."""
+    if distill is not None:
+        terms = seg_loss(masks_pred, true_masks, n_classes, reduce_sums=reduce_sums, world=world, boundary_weight=boundary_weight,
+                         surface_weight=surface_weight, surface_classes=surface_classes, **({} if loss is None else {"loss": loss}))
+        return _add_distill(terms, masks_pred, teacher_logits, n_classes, distill, reduce_sums, world)
     if loss is not None:
         w_b = (0.25 if n_classes == 1 else 0.0) if boundary_weight is None else float(boundary_weight)
         terms = _focal_tversky_terms(masks_pred, true_masks, n_classes, loss, w_b, reduce_sums, world)
@@ -522,19 +544,24 @@ def _pinned_flag(device, n: int = 1) -> torch.Tensor:
 def train_step(model: nn.Module, optimizer, images: torch.Tensor, true_masks: torch.Tensor, *, amp: bool = True,
                gradient_clipping: float = 1.0, reduce_sums=None, world: int = 1, check_nan: bool = True,
                boundary_weight: Optional[float] = None, cc_loss: bool = False, surface_weight: float = 0.0,
-               surface_classes=None, loss=None) -> Dict[str, torch.Tensor]:
+               surface_classes=None, loss=None, distill=None) -> Dict[str, torch.Tensor]:
     """Statement sequence of train.py:113-159.  `optimizer` is a FusedRMSprop (clipping fused into
     its step) or any torch.optim optimizer (then clip_grad_norm_ is applied as in the reference).
     surface_weight / surface_classes: the surface term of seg_loss (0: off, the step is what it is without the option).
-    loss: the focal + Tversky configuration of seg_loss (None: off, likewise)."""
+    loss: the focal + Tversky configuration of seg_loss (None: off, likewise).
+    distill: a utils.distill.Distiller (None: off, likewise): its frozen teacher's eval forward runs on this step's images --
+    as they arrive here, augmented and cropped -- before the student's forward, and seg_loss adds w * kd."""
     assert images.shape[1] == model.n_channels, \
         f"Network has been defined with {model.n_channels} input channels, but loaded images have " \
         f"{images.shape[1]} channels. Please check that the images are loaded correctly."   # train.py:108-111
+    extra = {} if loss is None else {"loss": loss}
+    if distill is not None:
+        extra.update(distill=distill.config, teacher_logits=distill.teacher_logits(images))
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
         masks_pred = model(images)
         terms = seg_loss(masks_pred, true_masks, model.n_classes, reduce_sums=reduce_sums, world=world,
                          boundary_weight=boundary_weight, surface_weight=surface_weight, surface_classes=surface_classes,
-                         **({} if loss is None else {"loss": loss}))
+                         **extra)
     if cc_loss and model.n_classes == 1:
         # the block train.py:124-132 keeps commented out (BASELINE config 5 turns it on): a Python float, no gradient.
         # sigmoid(x) > 0.5 <=> x > 0, so the 0/1 threshold mask stands in for the probabilities.  The masks stay on the
@@ -597,8 +624,23 @@ class TrainStepper:
     def __init__(self, model: nn.Module, lr: float = 1e-5, weight_decay: float = 1e-8, momentum: float = 0.999,
                  gradient_clipping: float = 1.0, amp: bool = True, process_group=None, check_nan: bool = True,
                  wgrad_stream: Optional[bool] = None, cc_loss: bool = False, sync_bn: bool = False, fp32_mode: str = "exact",
-                 surface_weight: float = 0.0, surface_classes=None, ema: Union[None, str, EmaConfig] = None, loss=None):
+                 surface_weight: float = 0.0, surface_classes=None, ema: Union[None, str, EmaConfig] = None, loss=None,
+                 distill=None):
         self.model = model
+        # distill: a utils.distill.Distiller, DistillConfig or spec string: every step adds w * kd against the frozen teacher's
+        # logits for the step's images.  The teacher is an object beside the model: it is in no optimizer, flat buffer, moving
+        # average, state_dict or checkpoint, and no collective touches it (every rank holds its own copy).  A config or spec
+        # builds the Distiller here, on the model's device, with this stepper's amp.  None (default): nothing is imported,
+        # allocated or launched for it.
+        self.distill = None
+        if distill is not None:
+            from .utils.distill import Distiller
+            if not isinstance(distill, Distiller):
+                distill = Distiller(distill, model.n_channels, model.n_classes, next(model.parameters()).device, amp)
+            elif distill.teacher.n_classes != model.n_classes or distill.teacher.n_channels != model.n_channels:
+                raise ValueError(f"TrainStepper: the teacher has {distill.teacher.n_channels} input channels and a head of "
+                                 f"{distill.teacher.n_classes} outputs, the student {model.n_channels} and {model.n_classes}")
+            self.distill = distill
         # loss: a utils.focal_loss.LossConfig or its spec string: the focal + Tversky node replaces the CE + Dice pair of every
         # step, checked against the model's head here.  None (default): the step is what it is without the option.
         self.loss = None
@@ -778,7 +820,8 @@ class TrainStepper:
             return train_step(self.model, self.optimizer, images, true_masks, amp=self.amp,
                               reduce_sums=self.reduce_sums, world=world, check_nan=self.check_nan, cc_loss=self.cc_loss,
                               surface_weight=self.surface_weight, surface_classes=self.surface_classes,
-                              **({} if self.loss is None else {"loss": self.loss}))
+                              **({} if self.loss is None else {"loss": self.loss}),
+                              **({} if self.distill is None else {"distill": self.distill}))
 
 
 class GraphedTrainStepper(TrainStepper):
@@ -791,6 +834,8 @@ class GraphedTrainStepper(TrainStepper):
 
     def __init__(self, model: nn.Module, *args, warmup: int = 2, **kw):
         kw.setdefault("wgrad_stream", False)         # one stream unless asked for: the graph is for launch-bound small models
+        self.distill = kw.get("distill")
+        self._refuse_distill()                       # (before a teacher is built for it)
         super().__init__(model, *args, **kw)
         if self.world != 1:
             raise RuntimeError("GraphedTrainStepper is single-process; use TrainStepper with torch.distributed")
@@ -798,6 +843,7 @@ class GraphedTrainStepper(TrainStepper):
             raise RuntimeError("connected_component_loss returns a Python float (a device read-back every step): not capturable")
         self._refuse_surface()
         self._refuse_loss()
+        self._refuse_distill()
         self._warmup = max(1, warmup)
         self._graph = None
         self._key = None
@@ -809,6 +855,10 @@ class GraphedTrainStepper(TrainStepper):
     def _refuse_loss(self):
         if self.loss is not None:
             raise RuntimeError("GraphedTrainStepper does not capture the focal / Tversky loss (loss must be None): use TrainStepper")
+
+    def _refuse_distill(self):
+        if self.distill is not None:
+            raise RuntimeError("GraphedTrainStepper does not capture distillation (distill must be None): use TrainStepper")
 
     def _eager_step(self, images, masks):
         with self._step_state(images, None):         # (single process: per-rank BatchNorm statistics, world = self.world)
@@ -847,6 +897,7 @@ class GraphedTrainStepper(TrainStepper):
     def step(self, images, true_masks):
         self._refuse_surface()
         self._refuse_loss()
+        self._refuse_distill()
         self._refuse_averaged()
         key = (tuple(images.shape), tuple(true_masks.shape), float(self.optimizer.param_groups[0]["lr"]))
         if self._graph is None or key != self._key:

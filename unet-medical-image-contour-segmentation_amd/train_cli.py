@@ -4,7 +4,7 @@
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
                              [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--elastic [SPEC]] [--surface-loss [SPEC]]
                              [--loss [SPEC]] [--ema [DECAY[,warmup=N]]] [--save-state] [--resume STATE]
-                             [--crop [SPEC]] [--tile [SPEC]]
+                             [--crop [SPEC]] [--tile [SPEC]] [--distill SPEC]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -47,6 +47,14 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     untouched: whole images, one size per batch.  A spec that does not fit --classes ends the command with status 2;
   - --tile [SIZE[,overlap=N]] (default: off; bare: "512,overlap=128") runs every in-loop evaluation as the sliding-window
     prediction of utils/tiling.py (evaluate(tile=...)): what validates a patch-trained network on images larger than its crops;
+  - --distill PATH[,arch=UNet|UNet_S|UNet_T|UNet_SA][,T=t][,w=W] (default: off; arch UNet, T 2, w 1) is knowledge distillation
+    (utils/distill.py, csrc/distill_loss.hip): PATH is the checkpoint of a trained network of architecture `arch` with the
+    same head (a model_epoch{E}.pth, *_ema.pth or checkpoint_epoch{E}.pth file; no comma in the path).  Every training step
+    runs that frozen teacher on its own (cropped, augmented) images and adds W T^2 KL(softmax(teacher / T) || softmax(student /
+    T)) to the loss, on top of whichever loss the step runs.  A malformed spec, a missing file or a teacher whose head differs
+    from --classes ends the command with status 2 before a dataset or a GPU is touched.  One log line per epoch gives the
+    mean term and the mean share of pixels on which student and teacher pick the same class.  Validation, checkpoints and
+    the saved model hold the student alone; --save-state records the spec and the SHA-256 of the teacher file;
   - --save-state writes checkpoint_dir/train_state.pth at the end of every epoch (a temporary file renamed over it): model
     and optimizer state (both RMSprop buffers, the moving average and its update count), epoch, global step, lr, the
     loader's and the augmenter's seeds, and a record of the arguments that determine the run (RECORDED);
@@ -95,7 +103,8 @@ STATE_FILE = "train_state.pth"
 RECORDED = (("model", "--model"), ("classes", "--classes"), ("bilinear", "--bilinear"), ("batch_size", "--batch-size"),
             ("scale", "--scale"), ("amp", "--amp / --no-amp"), ("lr", "--learning-rate"), ("augment", "--augment"),
             ("elastic", "--elastic"), ("surface", "--surface-loss"), ("ema", "--ema"), ("loss", "--loss"),
-            ("crop", "--crop"), ("tile", "--tile"))
+            ("crop", "--crop"), ("tile", "--tile"), ("distill", "--distill"),
+            ("distill_sha256", "--distill (the SHA-256 of the teacher file)"))
 
 
 def parse_surface_spec(text: str) -> SurfaceSpec:
@@ -172,6 +181,14 @@ def _crop_arg(text: str):
         raise argparse.ArgumentTypeError(f"bad --crop {text!r}: {e}") from None
 
 
+def _distill_arg(text: str):
+    from .utils.distill import DistillConfig
+    try:
+        return DistillConfig.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"bad --distill {text!r}: {e}") from None
+
+
 def _tile_arg(text: str) -> str:
     from .utils.tiling import parse_tile_spec
     try:
@@ -182,8 +199,12 @@ def _tile_arg(text: str) -> str:
 
 def run_record(args: argparse.Namespace) -> Dict:
     """The arguments that determine what a run computes (RECORDED), specs in their canonical form, None for an option that is
-    off.  ValueError for a spec that does not parse."""
+    off.  With --distill the record also holds the SHA-256 of the teacher file's bytes.  ValueError for a spec that does not
+    parse or a teacher file that cannot be read."""
     from .utils.augment import AugmentConfig, ElasticConfig
+    distill = getattr(args, "distill", None)
+    if distill is not None:
+        from .utils.distill import teacher_sha256
     return {"model": args.model, "classes": int(args.classes), "bilinear": bool(args.bilinear),
             "batch_size": int(args.batch_size), "scale": float(args.scale), "amp": bool(args.amp), "lr": float(args.lr),
             "augment": AugmentConfig.parse(args.augment).spec() if args.augment is not None else None,
@@ -192,7 +213,9 @@ def run_record(args: argparse.Namespace) -> Dict:
             "ema": args.ema.spec() if args.ema is not None else None,
             "loss": args.loss.spec() if getattr(args, "loss", None) is not None else None,
             "crop": args.crop.spec() if getattr(args, "crop", None) is not None else None,
-            "tile": getattr(args, "tile", None)}
+            "tile": getattr(args, "tile", None),
+            "distill": distill.spec() if distill is not None else None,
+            "distill_sha256": teacher_sha256(distill.teacher) if distill is not None else None}
 
 
 def load_resume_state(args: argparse.Namespace) -> Optional[Dict]:
@@ -268,6 +291,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--tile", nargs="?", const=TILE_BARE, default=None, type=_tile_arg, metavar="SIZE[,overlap=N]",
                    help="Run the in-loop evaluations as the sliding-window prediction: tiles of SIZE pixels, overlap blended "
                         f"(bare flag: '{TILE_BARE}'; default: off)")
+    p.add_argument("--distill", default=None, type=_distill_arg, metavar="PATH[,arch=NAME][,T=t][,w=W]",
+                   help="Knowledge distillation: add W * T^2 * KL(teacher || student) at temperature T against the frozen network of "
+                        "architecture NAME (UNet, UNet_S, UNet_T, UNet_SA; default UNet) loaded from the checkpoint PATH "
+                        "(defaults: T=2, w=1; default: off)")
     p.add_argument("--save-state", dest="save_state", action="store_true", default=False,
                    help=f"Write checkpoint_dir/{STATE_FILE} after every epoch: everything --resume needs (default: off)")
     p.add_argument("--resume", default=None, metavar="STATE",
@@ -311,7 +338,8 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                  checkpoint_dir: str = "./checkpoints", seed: Optional[int] = None, workers: int = 8,
                  train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
                  augment=None, surface: Optional[SurfaceSpec] = None, elastic=None, ema=None, save_state: bool = False,
-                 resume: Optional[Dict] = None, record: Optional[Dict] = None, loss=None, crop=None, tile=None) -> List[Dict]:
+                 resume: Optional[Dict] = None, record: Optional[Dict] = None, loss=None, crop=None, tile=None,
+                 distill=None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
@@ -328,6 +356,9 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     `crop`: a CropConfig, a spec string or a BatchCrop for the TRAIN loader (a config is seeded with the loader's seed, which
     is the saved one on resume: the state file needs no key for it); the validation loader never gets one.
     `tile`: a TileConfig or a spec string, passed to every evaluation of the loop.
+    `distill`: a DistillConfig, a spec string or a Distiller; every step adds the distillation term against the frozen teacher, the
+    record gains the epoch's mean "kd" and "kd_agree", and one line per epoch logs them.  Evaluations and checkpoints hold the
+    student alone.
     `save_state`: write checkpoint_dir/train_state.pth after every epoch, holding `record` (run_record) as its "args".
     `resume`: such a state (load_resume_state); the model must already hold its weights.  Optimizer state, lr, counters
     and the seeds are restored and the loop continues with the epoch after the saved one: only those epochs are returned."""
@@ -362,7 +393,9 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                 + (f"; elastic {augment.elastic.spec()}" if augment.elastic is not None else ""))
     val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
     stepper = TrainStepper(model, lr=learning_rate, amp=amp, surface_classes=surface.classes if surface is not None else None,
-                           ema=ema, loss=loss)
+                           ema=ema, loss=loss, **({} if distill is None else {"distill": distill}))
+    if stepper.distill is not None and log:
+        log(f"Distillation: teacher {stepper.distill.config.spec()}")
     lr = learning_rate
     global_step = 0
     first_epoch = 1
@@ -381,7 +414,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     history = []
     for epoch in range(first_epoch, epochs + 1):
         model.train()
-        losses, surfaces, focals, tverskys = [], [], [], []
+        losses, surfaces, focals, tverskys, kds, agrees = [], [], [], [], [], []
         if surface is not None:
             stepper.surface_weight = surface_weight_at(surface, epoch)
             if log:
@@ -400,6 +433,9 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
             if "focal" in terms:
                 focals.append(terms["focal"].detach())
                 tverskys.append(terms["tversky"].detach())
+            if "kd" in terms:
+                kds.append(terms["kd"].detach())
+                agrees.append(terms["kd_agree"].detach())
             seen += images.shape[0]
             global_step += 1
             if eval_due(global_step, n_train, batch_size):
@@ -435,6 +471,12 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
         if stepper.loss is not None:
             rec["focal"] = float(torch.stack(focals).double().sum().item()) if focals else 0.0
             rec["tversky"] = float(torch.stack(tverskys).double().sum().item()) if tverskys else 0.0
+        if stepper.distill is not None:
+            rec["kd"] = float(torch.stack(kds).double().mean().item()) if kds else 0.0
+            rec["kd_agree"] = float(torch.stack(agrees).double().mean().item()) if agrees else 0.0
+            if log:
+                log(f"Epoch {epoch}/{epochs}: distillation kd (mean) {rec['kd']:.6g}, agreement with the teacher (mean) "
+                    f"{rec['kd_agree']:.4f}")
         if checkpoint_dir is not None and checkpoint_due(epoch, epochs):
             path = os.path.join(checkpoint_dir, f"checkpoint_epoch{epoch}.pth")
             save_checkpoint(model, path, mask_values=mask_values)
@@ -487,6 +529,12 @@ def main(argv=None) -> int:
                 args.crop.for_head(args.classes)                              # likewise
             except ValueError as e:
                 raise ValueError(f"--crop: {e}") from None
+        if args.distill is not None:
+            from .utils.distill import check_teacher
+            try:
+                check_teacher(args.distill, 1, args.classes)                  # the file and its head, likewise (build_model: 1 channel)
+            except ValueError as e:
+                raise ValueError(f"--distill: {e}") from None
         resume = load_resume_state(args)                                      # a refused --resume needs no GPU to say so
         record = run_record(args) if (args.save_state or resume is not None) else None
     except ValueError as e:
@@ -539,7 +587,7 @@ def main(argv=None) -> int:
                            workers=args.workers, log=logging.info, pred_dir=args.pred_dir, metrics=args.metrics,
                            augment=augment, surface=args.surface_loss, elastic=elastic, ema=args.ema,
                            save_state=args.save_state, resume=resume, record=record, loss=args.loss,
-                           crop=args.crop, tile=args.tile)
+                           crop=args.crop, tile=args.tile, distill=args.distill)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")
