@@ -1,6 +1,8 @@
 """Torch-float64 restatement of the focal + Tversky loss (DESIGN.md section 3 "Focal / Tversky loss"): the value as plain tensor
 arithmetic that autograd differentiates, and the closed-form gradient the kernels implement.  Logits are [n, C] (any leading
-shape flattened by the caller), labels int [n] in [0, C).  The one-channel head is `two_class_logits(z)`: logits (0, z)."""
+shape flattened by the caller), labels int [n].  The one-channel head is `two_class_logits(z)`: logits (0, z).
+A label outside [0, C) matches no class (what ft_pixel of csrc/focal_loss.hip documents): its indicator row tau is zero, its weight
+w_t is 0 -- the pixel adds nothing to F, W, TP or T -- and it still counts in P_c = sum p_c."""
 import torch
 
 EPS = 1e-6
@@ -16,17 +18,27 @@ def default_classes(C):
     return tuple(range(1, C))
 
 
+def indicators(t, C):
+    """(tau [n, C] float64, inside [n] bool): one_hot(t) for labels in [0, C), a zero row for a label outside the head."""
+    t = t.long()
+    inside = (t >= 0) & (t < C)
+    tau = torch.nn.functional.one_hot(torch.where(inside, t, torch.zeros_like(t)), C).double() * inside[:, None].double()
+    return tau, inside
+
+
 def _pieces(z, t, w):
     z = z.double()
     C = z.shape[1]
     w = torch.as_tensor(w, dtype=torch.float64, device=z.device)
     logp = z - torch.logsumexp(z, dim=1, keepdim=True)              # log p_t = z_t - logsumexp, never log of a rounded p
     p = logp.exp()
-    tau = torch.nn.functional.one_hot(t.long(), C).double()
-    # u = sum_{c != t} p_c, never 1 - p_t; in log space, so that autograd stays finite where u underflows to 0
+    tau, inside = indicators(t, C)
+    # u = sum_{c != t} p_c, never 1 - p_t; in log space, so that autograd stays finite where u underflows to 0 (outside the
+    # head nothing is left out: u = 1)
     log_u = torch.logsumexp(z.masked_fill(tau.bool(), float("-inf")), dim=1) - torch.logsumexp(z, dim=1)
     nlp = -(logp * tau).sum(dim=1)
-    return p, tau, log_u, nlp, w[t.long()]
+    wt = w[torch.where(inside, t.long(), torch.zeros_like(t.long()))] * inside.double()
+    return p, tau, log_u, nlp, wt
 
 
 def focal_term(z, t, w, gamma):
@@ -39,7 +51,7 @@ def tversky_term(z, t, alpha, beta, classes=None):
     z = z.double()
     C = z.shape[1]
     p = torch.softmax(z, dim=1)
-    tau = torch.nn.functional.one_hot(t.long(), C).double()
+    tau, _ = indicators(t, C)
     TP, P, T = (p * tau).sum(dim=0), p.sum(dim=0), tau.sum(dim=0)
     TI = (TP + EPS) / ((1.0 - alpha - beta) * TP + alpha * P + beta * T + EPS)
     K = list(default_classes(C) if classes is None else classes)
@@ -83,7 +95,7 @@ def tversky_gradient(z, t, alpha, beta, classes=None):
     z = z.double()
     C = z.shape[1]
     p = torch.softmax(z, dim=1)
-    tau = torch.nn.functional.one_hot(t.long(), C).double()
+    tau, _ = indicators(t, C)
     TP, P, T = (p * tau).sum(dim=0), p.sum(dim=0), tau.sum(dim=0)
     N = TP + EPS
     D = (1.0 - alpha - beta) * TP + alpha * P + beta * T + EPS

@@ -44,11 +44,14 @@ __device__ __forceinline__ double column_sum_256(const float* __restrict__ parti
 
 // mask / mask_div as the reference's `true_masks //= 2` leaves it for the class indices a mask holds (train.py:119).  A 64-bit
 // integer division is ~100 instructions on this chip and these kernels are instruction-bound (2 M elements, a few bytes each):
-// values in [0, 2^31) -- every real mask -- take a shift (divisor 2) or a 32-bit division; anything else the full division.
+// values in [0, 2^31) -- every real mask -- take a shift (divisor 2) or a 32-bit division; anything else the full division,
+// floored as `//` floors it: -1 // 2 is -1, a label outside every head, where the truncating -1 / 2 is class 0.
 __device__ __forceinline__ float uh_mask_quot(int64_t m, int mask_div) {
     if ((uint64_t)m < (1ull << 31)) {
         const int v = (int)m;
         return (float)(mask_div == 2 ? (v >> 1) : (mask_div == 1 ? v : v / mask_div));
     }
-    return (float)(m / mask_div);
+    int64_t q = m / mask_div;
+    if (m < 0 && q * mask_div != m) --q;
+    return (float)q;
 }
