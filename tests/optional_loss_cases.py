@@ -5,7 +5,7 @@ proof that float32 arithmetic meets the bounds and that a seeded mistake breaks 
 Shapes and what each reaches (asserted by launch_facts() from the launch formulas, so a change of the constants fails on the CPU):
 sub_wave (1,1,3); two_blocks (2,37,45) = 3330, two partial rows and a ragged tail; second_sweep (2,517,511): 258 rows, so
 column_sum_256 and sl_finish_kernel sweep twice; grid_wrap (1,1031,1021) = 1 052 651 > 4096 * 256: 514 rows and the gradient / map
-grids go round; above_cap (2,1031,1021): 1028 rows asked for, LOSS_MAXBLK = SL_MAXBLK = 1024 given (sums passes only).
+grids go round; above_cap (2,1031,1021): 1028 rows asked for, LOSS_MAXBLK = 1024 given (sums passes only).
 
 References.  focal_tversky_ref, distill_ref, surface_loss_ref in float64 on the CPU; their closed-form gradients, which
 test_optional_loss_ops_cpu.py shows equal to autograd at the two small shapes.
@@ -75,7 +75,7 @@ SUMS_FRAC_RESTATEMENT = 0.5              # of loss_cases.SUM_ULPS, as tests/test
 SHAPES = dict(L.SHAPES, above_cap=(2, 1031, 1021))
 SMALL = L.SMALL
 SCALES = L.SCALES
-ROW_STRIDE, ROW_CAP = 2048, 1024         # loss_nblk / sl_sums_nblk: (n + 2047) / 2048 rows, at most LOSS_MAXBLK = SL_MAXBLK
+ROW_STRIDE, ROW_CAP = 2048, 1024         # loss_nblk: (n + 2047) / 2048 rows, at most LOSS_MAXBLK
 GRID_CAP, BLOCK = 4096, 256              # uh_flat_grid(n, UH_GRID_CAP): (n + 255) / 256 blocks, at most 256 * 16
 SWEEP = 256                              # rows one sweep of column_sum_256 / sl_finish_kernel takes
 _CACHE = {}

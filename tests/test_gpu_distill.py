@@ -63,10 +63,10 @@ def _ref(C, z, v, T, w=1.0):
 
 
 def _gpu(z, v, T, w=1.0, reduce_sums=None, world=1, seed_grad=None):
-    from unet_amd import ops
+    from unet_amd import losses
     zz = z.cuda().requires_grad_()
     vv = v.cuda().requires_grad_()                                    # asks for a gradient: it must not get one
-    weighted, kd, agree = ops.DistillLossFn.apply(zz, vv, T, w, reduce_sums, world)
+    weighted, kd, agree = losses.DistillLossFn.apply(zz, vv, T, w, reduce_sums, world)
     assert weighted.requires_grad and not kd.requires_grad and not agree.requires_grad
     if seed_grad is None:
         weighted.backward()

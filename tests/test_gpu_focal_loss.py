@@ -59,11 +59,11 @@ def _ref_form(C, logits, mask):
 
 
 def _gpu(C, logits, mask, gamma, alpha, beta, weights=None, reduce_sums=None):
-    from unet_amd import ops
+    from unet_amd import losses
     z = logits.cuda().requires_grad_()
     w = weights if weights is not None else _weights(2 if C == 1 else C)
     cls = (1,) if C == 1 else tuple(range(1, C))
-    total, focal, tversky = ops.FocalTverskyLossFn.apply(z, mask.cuda(), 2 if C == 1 else 1, w, gamma, alpha, beta, cls, reduce_sums)
+    total, focal, tversky = losses.FocalTverskyLossFn.apply(z, mask.cuda(), 2 if C == 1 else 1, w, gamma, alpha, beta, cls, reduce_sums)
     total.backward()
     return (total.detach(), focal.detach(), tversky.detach()), z.grad
 
@@ -143,7 +143,7 @@ def test_gamma_zero_unit_weights_agree_with_todays_cross_entropy(C):
     """focal(gamma = 0, w = 1) is the CE / BCE mean of uh_ce_dice_sums / uh_bce_dice_sums; today's gradient with its Dice part
     switched off (w_dice = 0) is the restatement's focal-only gradient, and so is the new gradient less the Tversky part."""
     import unet_amd
-    from unet_amd import ops
+    from unet_amd import losses
     from unet_amd._lib import LIB
     logits, mask = _inputs(C, 1.0, "two_blocks", "all")
     ones = (1.0,) * (2 if C == 1 else C)
@@ -157,7 +157,7 @@ def test_gamma_zero_unit_weights_agree_with_todays_cross_entropy(C):
     lg, mk = logits.cuda().contiguous(), mask.cuda()
     n = mk.numel()
     dl = torch.empty_like(lg)
-    ws = ops.loss_workspace(lg.device)
+    ws = losses.loss_workspace(lg.device)
     if C == 1:
         sums = torch.empty(4, dtype=torch.float32, device=lg.device)
         LIB.call("uh_bce_dice_sums", lg.data_ptr(), mk.data_ptr(), 2, None, n, sums.data_ptr(), ws.data_ptr(), ws.numel(), None)

@@ -1,6 +1,6 @@
 """The default training loss (csrc/loss.hip) on the MI355X, entry point by entry point, against float64: uh_bce_dice_sums / _grad,
 uh_ce_dice_sums / _grad, the two finishes, uh_dice_sums / uh_dice_from_sums, uh_boundary_loss / _mask and the fused binary call,
-through LIB.call, and once per family through ops.SegLossBinaryFn (fused and separate), SegLossMulticlassFn and DiceCoeffFn.
+through LIB.call, and once per family through losses.SegLossBinaryFn (fused and separate), SegLossMulticlassFn and DiceCoeffFn.
 Cases, references and bounds are tests/loss_cases.py's; tests/test_loss_ops_cpu.py shows on the CPU that float32 arithmetic meets the
 bounds with half the room to spare and that a seeded mistake breaks them.
 
@@ -76,9 +76,9 @@ def _dev():
 
 def _lib():
     import unet_amd  # noqa: F401
-    from unet_amd import ops
+    from unet_amd import losses
     from unet_amd._lib import LIB
-    return ops, LIB
+    return losses, LIB
 
 
 def _p(t):
@@ -100,9 +100,9 @@ def _f32_sums(ref, dev):
 
 # ------------------------------------------------------------------------------------------------ the C ABI, one call each
 def binary_sums(lg, mk, div, tf):
-    ops, LIB = _lib()
+    losses, LIB = _lib()
     sums = torch.empty(4, dtype=torch.float32, device=lg.device)
-    ws = ops.loss_workspace(lg.device)
+    ws = losses.loss_workspace(lg.device)
     LIB.call("uh_bce_dice_sums", lg.data_ptr(), _p(mk), int(div), _p(tf), lg.numel(), sums.data_ptr(), ws.data_ptr(), ws.numel(), None)
     return sums
 
@@ -124,10 +124,10 @@ def binary_grad(lg, mk, div, tf, sums, n_mean, w_bce, w_dice, gscale):
 
 
 def multiclass_sums(lg, mk):
-    ops, LIB = _lib()
+    losses, LIB = _lib()
     C = lg.shape[-1]
     sums = torch.empty(1 + 3 * C, dtype=torch.float32, device=lg.device)
-    ws = ops.loss_workspace(lg.device)
+    ws = losses.loss_workspace(lg.device)
     LIB.call("uh_ce_dice_sums", lg.data_ptr(), mk.data_ptr(), mk.numel(), C, sums.data_ptr(), ws.data_ptr(), ws.numel(), None)
     return sums
 
@@ -236,7 +236,7 @@ def test_binary_half_batches_with_the_whole_sums_give_the_whole_gradient():
 def test_seg_loss_binary_fn_against_float64(fuse):
     """The node train_step uses: every term, the total with the boundary term in it, and the gradient that backward() returns
     from the kernel's own sums."""
-    ops, _ = _lib()
+    losses, _ = _lib()
     dev = _dev()
     ew, wt, w_b = 5, 3.0, 0.25
     logits, mask = K.binary_inputs("two_blocks", 1.0, 2)
@@ -246,16 +246,16 @@ def test_seg_loss_binary_fn_against_float64(fuse):
     target = (mask // 2).float()
     bnd64 = K.boundary_oracle(logits, target, ew, wt)
     K.assert_boundary_condition(logits, target, ew, wt, bnd64)
-    default = ops.FUSE_LOSS
+    default = losses.FUSE_LOSS
     try:
-        ops.FUSE_LOSS = fuse
+        losses.FUSE_LOSS = fuse
         lg = logits.to(dev).requires_grad_()
-        total, bce, dice, bnd, nan_flag = ops.SegLossBinaryFn.apply(lg, mask.to(dev), 2, w_b, ew, wt, None, 1)
+        total, bce, dice, bnd, nan_flag = losses.SegLossBinaryFn.apply(lg, mask.to(dev), 2, w_b, ew, wt, None, 1)
         assert (nan_flag is not None) == fuse
         total.backward()
         total, bce, dice, bnd = (v.detach() for v in (total, bce, dice, bnd))
     finally:
-        ops.FUSE_LOSS = default
+        losses.FUSE_LOSS = default
     b_mean = K.mean_bound(ref["sums"][0], n, n)
     b_bnd = K.BOUNDARY_TOL * abs(bnd64)
     want = ref["bce"] + ref["dice"] + w_b * bnd64
@@ -310,7 +310,7 @@ def test_multiclass_half_batches_with_the_whole_sums_give_the_whole_gradient(C):
 
 def test_seg_loss_multiclass_fn_against_float64():
     """The multi-class node with its boundary term: channel 1 of the NHWC logits, pstride = C, bstride = H W C."""
-    ops, _ = _lib()
+    losses, _ = _lib()
     dev = _dev()
     (B, H, W, C, ew, wt, w_b), logits, mask = K.multiclass_node_case()
     ref = K.multiclass_ref(logits, mask)
@@ -318,7 +318,7 @@ def test_seg_loss_multiclass_fn_against_float64():
     bnd64 = K.boundary_oracle(logits, mask.float(), ew, wt)
     K.assert_boundary_condition(logits, mask.float(), ew, wt, bnd64)
     lg = logits.to(dev).requires_grad_()
-    out = ops.SegLossMulticlassFn.apply(lg, mask.to(dev), w_b, ew, wt, None, 1)
+    out = losses.SegLossMulticlassFn.apply(lg, mask.to(dev), w_b, ew, wt, None, 1)
     out[0].backward()
     total, ce, dice, bnd = (float(v) for v in out.detach().cpu())
     b_mean = K.mean_bound(ref["sums"][0], n, n)
@@ -349,12 +349,12 @@ def test_multiclass_entry_points_refuse_1_and_9_classes_with_an_error_code():
 # ------------------------------------------------------------------------------------------------ dice_coeff
 @pytest.mark.parametrize("ngroups,group_len", K.DICE_LAYOUTS)
 def test_dice_sums_of_small_integers_are_exact(ngroups, group_len):
-    ops, LIB = _lib()
+    losses, LIB = _lib()
     dev = _dev()
     x, t, want = K.dice_integer_inputs(ngroups, group_len)
     xf, tf = x.to(dev).float(), t.to(dev).float()
     sums = torch.empty(ngroups * 3, dtype=torch.float32, device=dev)
-    ws = ops.loss_workspace(dev)
+    ws = losses.loss_workspace(dev)
     assert ws.numel() // 16 == K.DICE_WS_ROWS
     LIB.call("uh_dice_sums", xf.data_ptr(), tf.data_ptr(), ngroups, group_len, sums.data_ptr(), ws.data_ptr(), ws.numel(), None)
     assert torch.equal(sums.cpu().double().view(ngroups, 3), want)
@@ -381,7 +381,7 @@ def test_dice_sums_refuses_more_groups_than_the_workspace_holds():
 @pytest.mark.parametrize("rbf", [True, False])
 @pytest.mark.parametrize("shape", [(2, 37, 45), (3, 64, 65)], ids=_ids)
 def test_dice_coeff_fn_value_and_backward_against_float64(shape, rbf):
-    ops, _ = _lib()
+    losses, _ = _lib()
     dev = _dev()
     g = torch.Generator().manual_seed(shape[1] + rbf)
     x = torch.rand(shape, generator=g)
@@ -391,7 +391,7 @@ def test_dice_coeff_fn_value_and_backward_against_float64(shape, rbf):
     want.backward()
     ngroups = 1 if rbf else shape[0]
     xg = x.to(dev).requires_grad_()
-    got = ops.DiceCoeffFn.apply(xg, t.to(dev), ngroups, x.numel() // ngroups, 1e-6)
+    got = losses.DiceCoeffFn.apply(xg, t.to(dev), ngroups, x.numel() // ngroups, 1e-6)
     got.backward()
     got, want = got.detach(), want.detach()
     rel = abs(float(got) - float(want)) / float(want)
@@ -402,15 +402,15 @@ def test_dice_coeff_fn_value_and_backward_against_float64(shape, rbf):
 
 # ------------------------------------------------------------------------------------------------ boundary_loss
 def _boundary(pred, pstride, bstride, target, B, H, W, ew, wt, out):
-    ops, LIB = _lib()
-    ws = ops.loss_workspace(pred.device)
+    losses, LIB = _lib()
+    ws = losses.loss_workspace(pred.device)
     LIB.call("uh_boundary_loss", pred.data_ptr(), pstride, bstride, target.data_ptr(), B, H, W, ew, wt, 1e-6, out.data_ptr(),
              ws.data_ptr(), ws.numel(), None)
 
 
 def _boundary_mask(pred, mask, div, B, H, W, ew, wt, out):
-    ops, LIB = _lib()
-    ws = ops.loss_workspace(pred.device)
+    losses, LIB = _lib()
+    ws = losses.loss_workspace(pred.device)
     LIB.call("uh_boundary_loss_mask", pred.data_ptr(), 1, H * W, mask.data_ptr(), div, B, H, W, ew, wt, 1e-6, out.data_ptr(),
              ws.data_ptr(), ws.numel(), None)
 

@@ -1,7 +1,7 @@
 """The three optional training losses on the MI355X, entry point by entry point, against float64 per element:
 uh_focal_tversky_sums / _finish / _grad (csrc/focal_loss.hip), uh_distill_sums / _finish / _grad (csrc/distill_loss.hip),
 uh_surface_loss_sums / _grad with rebuild 0 and 1 and uh_surface_dist_map (csrc/surface_loss.hip), each through LIB.call, and once
-per family through ops.FocalTverskyLossFn, SurfaceLossFn and DistillLossFn.  Cases, references, bounds and the constants R / 2 R are
+per family through losses.FocalTverskyLossFn, SurfaceLossFn and DistillLossFn.  Cases, references, bounds and the constants R / 2 R are
 tests/optional_loss_cases.py's (its docstring derives the bounds); tests/test_optional_loss_ops_cpu.py shows on the CPU that a float32
 restatement stays within R and that each seeded mistake breaks an assertion made here.
 
@@ -20,7 +20,7 @@ equalities, at second_sweep.  Not reached: pixel counts past 2^31 (the 64-bit in
 Kernel change (csrc/uh_loss_reduce.h, uh_mask_quot): a mask outside [0, 2^31) took the truncating 64-bit division, so the mask -1
 under mask_div 2 became class 0 and was given weight, where `//` of the reference makes it -1, a label outside the head.  Read from
 the code while the out-of-head cases were written (it never ran on the device in that form); the quotient is now floored, as
-sl_quot of surface_loss.hip always was.  The case that holds it: the saturated one-channel focal head, whose W and T_0 are equalities
+the label quotient of surface_loss.hip always was.  The case that holds it: the saturated one-channel focal head, whose W and T_0 are equalities
 (test_saturated_focal_sums_are_exact_and_the_finish_bit_for_bit).  Masks in [0, 2^31) take the same instructions as before.
 
 Measured on the MI355X (worst over all cases; the tests print each next to its bound; no bound was exceeded):
@@ -55,9 +55,9 @@ def _dev():
 
 def _lib():
     import unet_amd  # noqa: F401
-    from unet_amd import ops
+    from unet_amd import losses
     from unet_amd._lib import LIB
-    return ops, LIB
+    return losses, LIB
 
 
 def _up(key, *tensors):
@@ -95,9 +95,9 @@ def _floats(v):
 
 # ------------------------------------------------------------------------------------------------ the C ABI, one call each
 def focal_sums(lg, mk, div, ncls, w, gamma):
-    ops, LIB = _lib()
+    losses, LIB = _lib()
     sums = torch.full((LIB.query("uh_focal_tversky_nsums", ncls),), float("nan"), dtype=torch.float32, device=lg.device)
-    ws = ops.loss_workspace(lg.device)
+    ws = losses.loss_workspace(lg.device)
     LIB.call("uh_focal_tversky_sums", lg.data_ptr(), mk.data_ptr(), int(div), mk.numel(), ncls, _floats(w), float(gamma), sums.data_ptr(),
              ws.data_ptr(), ws.numel(), None)
     return sums
@@ -120,9 +120,9 @@ def focal_grad(lg, mk, div, ncls, w, gamma, alpha, beta, cls, sums, gscale):
 
 
 def distill_sums(z, v, ncls, T):
-    ops, LIB = _lib()
+    losses, LIB = _lib()
     sums = torch.full((2,), float("nan"), dtype=torch.float32, device=z.device)
-    ws = ops.loss_workspace(z.device)
+    ws = losses.loss_workspace(z.device)
     LIB.call("uh_distill_sums", z.data_ptr(), v.data_ptr(), z.shape[0], ncls, float(T), sums.data_ptr(), ws.data_ptr(), ws.numel(), None)
     return sums
 
@@ -420,14 +420,14 @@ def test_two_calls_give_the_same_bits_and_half_batches_the_whole_gradient_at_sec
 
 # ------------------------------------------------------------------------------------------------ the autograd nodes
 def test_focal_tversky_loss_fn_against_float64():
-    ops, _ = _lib()
+    losses, _ = _lib()
     dev = _dev()
     case = ("two_blocks", 10.0, 3, 1.5)
     B, H, W = K.SHAPES[case[0]]
     logits, mask, div = K.focal_inputs(*case[:3])
     ref = K.focal_ref_cached(*case)
     lg = logits.reshape(B, H, W, 3).to(dev).requires_grad_()
-    total, focal, tversky = ops.FocalTverskyLossFn.apply(lg, mask.reshape(B, H, W).to(dev), div, ref["w"], 1.5, 0.3, 0.7, (1, 2))
+    total, focal, tversky = losses.FocalTverskyLossFn.apply(lg, mask.reshape(B, H, W).to(dev), div, ref["w"], 1.5, 0.3, 0.7, (1, 2))
     total.backward()
     want = K.focal_finish64(ref["sums"], 3, 0.3, 0.7, (1, 2), rounded=False)
     # the node's own sums: F within 24 u and its slack of F64, relative to W exactly; each Tversky index moves by at most the
@@ -446,7 +446,7 @@ def test_focal_tversky_loss_fn_against_float64():
 
 
 def test_distill_loss_fn_against_float64():
-    ops, _ = _lib()
+    losses, _ = _lib()
     dev = _dev()
     case = ("two_blocks", 10.0, 3, "free")
     B, H, W = K.SHAPES[case[0]]
@@ -454,7 +454,7 @@ def test_distill_loss_fn_against_float64():
     ref = K.distill_ref_cached(*case)
     n, T = ref["n"], ref["T"]
     zg = z.reshape(B, H, W, 3).to(dev).requires_grad_()
-    weighted, kd, agree = ops.DistillLossFn.apply(zg, v.reshape(B, H, W, 3).to(dev), T, K.KD_W)
+    weighted, kd, agree = losses.DistillLossFn.apply(zg, v.reshape(B, H, W, 3).to(dev), T, K.KD_W)
     weighted.backward()
     weighted, kd, agree = (t.detach() for t in (weighted, kd, agree))
     want = K.distill_finish64(ref["sums"], float(n), T, K.KD_W, rounded=False)
@@ -471,7 +471,7 @@ def test_distill_loss_fn_against_float64():
 
 @pytest.mark.parametrize("ncls,classes", [(1, (1,)), (3, (1, 2))], ids=_ids)
 def test_surface_loss_fn_against_float64(ncls, classes):
-    ops, _ = _lib()
+    losses, _ = _lib()
     dev = _dev()
     shape = "two_blocks"
     B, H, W = K.SHAPES[shape]
@@ -480,7 +480,7 @@ def test_surface_loss_fn_against_float64(ncls, classes):
     logits = K.surface_inputs(shape, 10.0, ncls)
     lg = (logits.reshape(B, H, W) if ncls == 1 else logits.reshape(B, H, W, ncls)).to(dev).requires_grad_()
     labels = torch.from_numpy(K.surface_labels(shape, ncls == 1)).to(dev)
-    weighted, value = ops.SurfaceLossFn.apply(lg, labels, 2 if ncls == 1 else 1, classes, K.SURFACE_W)
+    weighted, value = losses.SurfaceLossFn.apply(lg, labels, 2 if ncls == 1 else 1, classes, K.SURFACE_W)
     weighted.backward()
     weighted, value = weighted.detach(), value.detach()
     err = abs(float(value) - K.surface_value64(ref, float(n)))

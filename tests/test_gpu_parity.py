@@ -481,23 +481,23 @@ def test_dice_after_training_matches_oracle():
 def test_fused_binary_loss_is_bit_identical_to_the_separate_kernels(B, H, W, scale, w_b):
     """uh_seg_loss_binary_fused (three launches) against uh_bce_dice_sums + uh_boundary_loss_mask + uh_seg_loss_binary_finish
     (six): every loss term, the sums kept for the backward pass, the gradient of the logits and the NaN flag."""
-    from unet_amd import ops
+    from unet_amd import losses
     dev = _dev()
     g = torch.Generator().manual_seed(B * 1000 + H)
     logits = (torch.randn(B, H, W, generator=g) * scale).to(dev)
     mask = torch.randint(0, 3, (B, H, W), generator=g).to(dev)
     res = []
-    default = ops.FUSE_LOSS
+    default = losses.FUSE_LOSS
     try:
         for fuse in (False, True):
-            ops.FUSE_LOSS = fuse
+            losses.FUSE_LOSS = fuse
             lg = logits.clone().requires_grad_(True)
-            total, bce, dice, bnd, nan_flag = ops.SegLossBinaryFn.apply(lg, mask, 2, w_b, 51, 15.0, None, 1)
+            total, bce, dice, bnd, nan_flag = losses.SegLossBinaryFn.apply(lg, mask, 2, w_b, 51, 15.0, None, 1)
             assert (nan_flag is not None) == fuse
             total.backward()
             res.append((total.detach().clone(), bce.clone(), dice.clone(), bnd.clone(), lg.grad.clone(), nan_flag))
     finally:
-        ops.FUSE_LOSS = default
+        losses.FUSE_LOSS = default
     torch.cuda.synchronize()
     for a, b, name in zip(res[0][:5], res[1][:5], ("total", "bce", "dice", "boundary", "dlogits")):
         assert torch.equal(a, b), (name, a, b)
@@ -505,7 +505,7 @@ def test_fused_binary_loss_is_bit_identical_to_the_separate_kernels(B, H, W, sca
     # a NaN logit raises the flag (and nothing else changes shape)
     bad = logits.clone()
     bad[0, 3, 5] = float("nan")
-    out = ops.SegLossBinaryFn.apply(bad, mask, 2, w_b, 51, 15.0, None, 1)
+    out = losses.SegLossBinaryFn.apply(bad, mask, 2, w_b, 51, 15.0, None, 1)
     assert float(out[4]) == 1.0 and bool(torch.isnan(out[0]))
 
 

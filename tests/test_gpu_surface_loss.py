@@ -51,13 +51,13 @@ def test_distance_maps_equal_the_restatement_bit_for_bit(name, labels, classes, 
 
 def test_border_comes_straight_from_the_int64_labels():
     import contour_metrics_ref as C
-    from unet_amd import ops
+    from unet_amd import losses
     rng = np.random.default_rng(2)
     labels = R.blob_labels(rng, 2, 37, 100)
-    got = ops.surface_border(torch.from_numpy(labels).cuda(), (2, 1)).cpu().numpy()
+    got = losses.surface_border(torch.from_numpy(labels).cuda(), (2, 1)).cpu().numpy()
     want = np.stack([np.stack([C.border(labels[b] == c) for b in range(2)]) for c in (2, 1)]).astype(np.uint8)
     assert got.dtype == np.uint8 and np.array_equal(got, want)
-    got2 = ops.surface_border(torch.from_numpy(labels).cuda(), (1,), mask_div=2).cpu().numpy()
+    got2 = losses.surface_border(torch.from_numpy(labels).cuda(), (1,), mask_div=2).cpu().numpy()
     assert np.array_equal(got2[0], np.stack([C.border(labels[b] // 2 == 1) for b in range(2)]).astype(np.uint8))
 
 
@@ -113,7 +113,7 @@ def test_two_calls_return_the_same_bits(name):
 @pytest.mark.parametrize("n_classes,classes", [(1, (1,)), (3, (1, 2))])
 def test_gradient_of_a_batch_is_that_of_its_halves(n_classes, classes):
     """Each half is computed with the n_mean of the whole batch (world = 2), as a data-parallel rank would."""
-    from unet_amd import ops
+    from unet_amd import losses
     rng = np.random.default_rng(4)
     B, H, W = 4, 24, 40
     labels = torch.from_numpy(R.blob_labels(rng, B, H, W)).cuda()
@@ -123,7 +123,7 @@ def test_gradient_of_a_batch_is_that_of_its_halves(n_classes, classes):
     def grad(lo, hi, world):
         z = logits[lo:hi].clone().requires_grad_()
         lg = z.squeeze(1) if n_classes == 1 else z.permute(0, 2, 3, 1)
-        weighted, _ = ops.SurfaceLossFn.apply(lg, labels[lo:hi], 2 if n_classes == 1 else 1, classes, 1.0, None, world)
+        weighted, _ = losses.SurfaceLossFn.apply(lg, labels[lo:hi], 2 if n_classes == 1 else 1, classes, 1.0, None, world)
         weighted.backward()
         return z.grad
 
@@ -138,7 +138,7 @@ def test_two_losses_of_one_shape_in_flight_keep_their_own_distances(n_classes, c
     """Forward A, forward B (other labels, same shape: the same workspace), then backward A and backward B.  B's forward wrote
     its distances over A's, so A's backward forms them again (rebuild), and that in turn makes B's do so: each gradient is
     bit for bit the one computed alone."""
-    from unet_amd import ops
+    from unet_amd import losses
     B, H, W = 2, 24, 40
     div = 2 if n_classes == 1 else 1
     labels = [torch.from_numpy(R.blob_labels(np.random.default_rng(s), B, H, W)).cuda() for s in (21, 22)]
@@ -149,7 +149,7 @@ def test_two_losses_of_one_shape_in_flight_keep_their_own_distances(n_classes, c
     def forward(i):
         z = logits[i].clone().requires_grad_()
         lg = z.squeeze(1) if n_classes == 1 else z.permute(0, 2, 3, 1)
-        weighted, _ = ops.SurfaceLossFn.apply(lg, labels[i], div, classes, 1.0)
+        weighted, _ = losses.SurfaceLossFn.apply(lg, labels[i], div, classes, 1.0)
         return z, weighted
 
     alone = []
@@ -165,7 +165,7 @@ def test_two_losses_of_one_shape_in_flight_keep_their_own_distances(n_classes, c
     assert torch.equal(_bits(zb.grad), _bits(alone[1]))
     # ... and with the distance-map helper using the workspace between a forward and its backward
     za, wa = forward(0)
-    ops.surface_dist_map(labels[1], classes, div)
+    losses.surface_dist_map(labels[1], classes, div)
     wa.backward()
     assert torch.equal(_bits(za.grad), _bits(alone[0]))
 

@@ -178,3 +178,16 @@ def test_python_surface_has_no_cpu_fallback_and_the_graph_stepper_signature():
     for fn in (unet_amd.seg_loss, unet_amd.train_step, unet_amd.TrainStepper.__init__):
         params = inspect.signature(fn).parameters
         assert params["surface_weight"].default == 0.0 and params["surface_classes"].default is None
+
+
+def test_the_shared_head_check_refuses_a_one_channel_head_with_a_channel_axis():
+    """One head check for the surface, focal and distillation nodes: [B,H,W] is the one-channel head, [B,H,W,C] a softmax head of
+    C >= 2, and [B,H,W,1] is refused for all three (the surface node used to read it as the one-channel head)."""
+    from unet_amd import losses
+    assert losses._head_of(torch.zeros(2, 4, 5), (2, 4, 5), "surface loss") == 1
+    assert losses._head_of(torch.zeros(2, 4, 5, 3), (2, 4, 5), "surface loss") == 3
+    for who in ("surface loss", "focal / Tversky loss", "distillation"):
+        with pytest.raises(RuntimeError, match=f"{who}: the one-channel head passes its logits as \\[B,H,W\\]"):
+            losses._head_of(torch.zeros(2, 4, 5, 1), (2, 4, 5), who)
+    with pytest.raises(RuntimeError, match="surface loss expects logits \\[B,H,W\\] or \\[B,H,W,C\\] matching labels"):
+        losses._head_of(torch.zeros(2, 4, 6), (2, 4, 5), "surface loss")

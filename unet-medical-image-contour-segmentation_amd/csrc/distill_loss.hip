@@ -6,7 +6,7 @@
 //   kd    = T^2 / n sum_x sum_c q_c (log q_c - log p_c)
 //   agree = 1 / n sum_x [argmax z = argmax v]                 (first maximum; a diagnostic, no gradient)
 //   1. kd_sums_kernel    one pass over both logit tensors: per-block rows { sum KL, sum agree }
-//      kd_colsum_kernel  the rows' column sums in double -> sums[2] (what a data-parallel run all-reduces)
+//      loss_finish_kernel  the rows' column sums in double -> sums[2] (uh_loss_colsum_launch; what a data-parallel run all-reduces)
 //   2. kd_finish_kernel  { w kd, kd, agree } from the sums and n, in double
 //   3. kd_grad_kernel    one pass: d(w kd)/dz_k = w T / n (p_k - q_k); it WRITES dlogits (the largest class's component is
 //                        minus the sum of the others: no cancellation where both sides are sure of a class)
@@ -18,7 +18,6 @@
 // No floating-point atomics; grid sizes depend on the shape alone: a call gives the same bits every time, and a pixel's gradient
 // depends on that pixel's two logit vectors, n, T, w and the scale factor only.
 #include <math.h>
-#include "uh_launch.h"
 #include "uh_loss_reduce.h"
 
 namespace {
@@ -66,18 +65,6 @@ __device__ __forceinline__ void kd_side(const float (&z)[NC], float inv_t, KdSid
     o.am = am;
 }
 
-// ONE: the one-channel head, logits [npix], the two-class form on (0, z)
-template <int NC, bool ONE>
-__device__ __forceinline__ void kd_load(const float* __restrict__ logits, int64_t p, float (&z)[NC]) {
-    if constexpr (ONE) {
-        z[0] = 0.f;
-        z[1] = logits[p];
-    } else {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) z[c] = logits[p * NC + c];
-    }
-}
-
 template <int NC, bool ONE>
 __global__ __launch_bounds__(256) void kd_sums_kernel(const float* __restrict__ student, const float* __restrict__ teacher, float inv_t,
                                                       int64_t npix, float* __restrict__ partials) {
@@ -85,8 +72,8 @@ __global__ __launch_bounds__(256) void kd_sums_kernel(const float* __restrict__ 
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
 #pragma clang fp contract(off)          // KD_NO_FMA
         float z[NC], v[NC];
-        kd_load<NC, ONE>(student, p, z);
-        kd_load<NC, ONE>(teacher, p, v);
+        uh_head_load<NC, ONE>(student, p, z);
+        uh_head_load<NC, ONE>(teacher, p, v);
         KdSide<NC> s, t;
         kd_side<NC>(z, inv_t, s);
         kd_side<NC>(v, inv_t, t);
@@ -98,14 +85,6 @@ __global__ __launch_bounds__(256) void kd_sums_kernel(const float* __restrict__ 
         acc[1] += (s.am == t.am) ? 1.f : 0.f;
     }
     block_reduce_store<2>(acc, partials + (int64_t)blockIdx.x * LOSS_ROW);
-}
-
-__global__ __launch_bounds__(256) void kd_colsum_kernel(const float* __restrict__ partials, int nblk, float* __restrict__ out) {
-    __shared__ double red[256];
-    for (int k = 0; k < 2; ++k) {
-        const double s = column_sum_256(partials, nblk, k, red);
-        if (threadIdx.x == 0) out[k] = (float)s;
-    }
 }
 
 __global__ void kd_finish_kernel(const float* __restrict__ sums, double n_mean, double T, double w, float* __restrict__ out) {
@@ -125,8 +104,8 @@ __global__ __launch_bounds__(256) void kd_grad_kernel(const float* __restrict__ 
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
 #pragma clang fp contract(off)          // KD_NO_FMA
         float z[NC], v[NC];
-        kd_load<NC, ONE>(student, p, z);
-        kd_load<NC, ONE>(teacher, p, v);
+        uh_head_load<NC, ONE>(student, p, z);
+        uh_head_load<NC, ONE>(teacher, p, v);
         KdSide<NC> s, t;
         kd_side<NC>(z, inv_t, s);
         kd_side<NC>(v, inv_t, t);
@@ -151,21 +130,7 @@ __global__ __launch_bounds__(256) void kd_grad_kernel(const float* __restrict__ 
     }
 }
 
-// f(NC, ONE): (2, true) for the one-channel head, (ncls, false) otherwise
-template <typename F>
-inline void kd_head_dispatch(int ncls, F&& f) {
-    uh_class_dispatch<KD_MAXC>(ncls, [&](auto nc) {
-        if constexpr (decltype(nc)::value == 1) f(std::integral_constant<int, 2>{}, std::true_type{});
-        else f(nc, std::false_type{});
-    });
-}
-
 inline bool kd_positive(double v) { return v > 0.0 && v <= 1.0e30; }      // finite and > 0 (a NaN fails both)
-
-bool kd_head_ok(const char* who, int ncls) {
-    if (ncls < 1 || ncls > KD_MAXC) { uh_set_error("%s: heads of 1 (sigmoid) to %d (softmax) classes, got %d", who, KD_MAXC, ncls); return false; }
-    return true;
-}
 
 }  // namespace
 
@@ -174,20 +139,18 @@ extern "C" int uh_distill_nsums(void) { return 2; }
 extern "C" int uh_distill_sums(const float* student, const float* teacher, int64_t npix, int ncls, double T, float* sums, void* ws,
                                size_t ws_bytes, uh_stream stream) {
     UH_REQUIRE(student && teacher && sums && ws && npix > 0, "uh_distill_sums: bad args");
-    if (!kd_head_ok("uh_distill_sums", ncls)) return UH_EINVAL;
+    if (!uh_loss_head_ok("uh_distill_sums", ncls, KD_MAXC)) return UH_EINVAL;
     UH_REQUIRE(kd_positive(T), "uh_distill_sums: the temperature must be finite and > 0, got %g", T);
     UH_REQUIRE(ws_bytes >= uh_loss_ws_bytes(npix), "uh_distill_sums: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int nblk = loss_nblk(npix);
     const float inv_t = (float)(1.0 / T);
-    kd_head_dispatch(ncls, [&](auto nc, auto one) {
+    uh_loss_head_dispatch<KD_MAXC>(ncls, [&](auto nc, auto one) {
         hipLaunchKernelGGL((kd_sums_kernel<decltype(nc)::value, decltype(one)::value>), dim3(nblk), dim3(256), 0, st, student, teacher,
                            inv_t, npix, (float*)ws);
     });
     UH_CHECK_LAUNCH("kd_sums_kernel");
-    hipLaunchKernelGGL(kd_colsum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nblk, sums);
-    UH_CHECK_LAUNCH("kd_colsum_kernel");
-    return UH_OK;
+    return uh_loss_colsum_launch((const float*)ws, nblk, uh_distill_nsums(), sums, st);
 }
 
 extern "C" int uh_distill_finish(const float* sums, double n_mean, double T, double w, float* out, uh_stream stream) {
@@ -202,13 +165,13 @@ extern "C" int uh_distill_finish(const float* sums, double n_mean, double T, dou
 extern "C" int uh_distill_grad(const float* student, const float* teacher, int64_t npix, int ncls, double n_mean, double T, double w,
                                const float* gscale, float* dlogits, uh_stream stream) {
     UH_REQUIRE(student && teacher && dlogits && npix > 0, "uh_distill_grad: bad args");
-    if (!kd_head_ok("uh_distill_grad", ncls)) return UH_EINVAL;
+    if (!uh_loss_head_ok("uh_distill_grad", ncls, KD_MAXC)) return UH_EINVAL;
     UH_REQUIRE(kd_positive(n_mean) && kd_positive(T) && kd_positive(w),
                "uh_distill_grad: n_mean, the temperature and the weight must be finite and > 0, got %g, %g, %g", n_mean, T, w);
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = uh_flat_grid(npix, UH_GRID_CAP);
     const float inv_t = (float)(1.0 / T), coef = (float)(w * T / n_mean);
-    kd_head_dispatch(ncls, [&](auto nc, auto one) {
+    uh_loss_head_dispatch<KD_MAXC>(ncls, [&](auto nc, auto one) {
         hipLaunchKernelGGL((kd_grad_kernel<decltype(nc)::value, decltype(one)::value>), dim3(grid), dim3(256), 0, st, student, teacher,
                            inv_t, coef, npix, gscale, dlogits);
     });

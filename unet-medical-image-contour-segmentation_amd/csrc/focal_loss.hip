@@ -7,7 +7,7 @@
 //   TI_c     = (TP_c + eps) / ((1 - alpha - beta) TP_c + alpha P_c + beta T_c + eps),  TP = sum p_c [t = c], P = sum p_c, T = sum [t = c]
 //   tversky  = 1 / |K| sum_{c in K} (1 - TI_c)
 //   1. ft_sums_kernel    one pass over the logits: per-block rows { F, W, TP_c.., P_c.., T_c.. } (2 + 3 C floats <= one LOSS_ROW)
-//      ft_colsum_kernel  the rows' column sums in double -> sums (what a data-parallel run all-reduces)
+//      loss_finish_kernel  the rows' column sums in double -> sums (uh_loss_colsum_launch; what a data-parallel run all-reduces)
 //   2. ft_finish_kernel  { total, focal, tversky } from the sums, in double
 //   3. ft_grad_kernel    one pass: dL/dz_k = w_t / W s (tau_k - p_k) + p_k (g_k - sum_c p_c g_c); it WRITES dlogits
 // The exponential of the largest logit is exactly 1, so logsumexp - max = log1p(sum of the others) and, where the label is the
@@ -15,7 +15,6 @@
 // multiplications for gamma in {0, 1, 2} and exp2(gamma log2 u) otherwise, chosen per launch (a template parameter).
 // No floating-point atomics; grid sizes depend on the shape alone: a call gives the same bits every time, and a pixel's gradient
 // depends on that pixel's logits, its label, the sums and the scale factor only.
-#include "uh_launch.h"
 #include "uh_loss_reduce.h"
 
 namespace {
@@ -73,18 +72,6 @@ __device__ __forceinline__ void ft_pixel(const float (&z)[NC], int t, const FtPa
     o.wt = wt;
 }
 
-// ONE: the one-channel head, logits [npix], the two-class form on (0, z)
-template <int NC, bool ONE>
-__device__ __forceinline__ void ft_load(const float* __restrict__ logits, int64_t p, float (&z)[NC]) {
-    if constexpr (ONE) {
-        z[0] = 0.f;
-        z[1] = logits[p];
-    } else {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) z[c] = logits[p * NC + c];
-    }
-}
-
 template <int NC, int GM, bool ONE>
 __global__ __launch_bounds__(256) void ft_sums_kernel(const float* __restrict__ logits, const int64_t* __restrict__ mask, int mask_div,
                                                       FtParams prm, int64_t npix, float* __restrict__ partials) {
@@ -93,7 +80,7 @@ __global__ __launch_bounds__(256) void ft_sums_kernel(const float* __restrict__ 
     for (int k = 0; k < 2 + 3 * NC; ++k) v[k] = 0.f;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
         float z[NC];
-        ft_load<NC, ONE>(logits, p, z);
+        uh_head_load<NC, ONE>(logits, p, z);
         const int t = (int)uh_mask_quot(mask[p], mask_div);
         FtPixel<NC> px;
         ft_pixel<NC>(z, t, prm, px);
@@ -107,14 +94,6 @@ __global__ __launch_bounds__(256) void ft_sums_kernel(const float* __restrict__ 
         }
     }
     block_reduce_store<2 + 3 * NC>(v, partials + (int64_t)blockIdx.x * LOSS_ROW);
-}
-
-__global__ __launch_bounds__(256) void ft_colsum_kernel(const float* __restrict__ partials, int nblk, int K, float* __restrict__ out) {
-    __shared__ double red[256];
-    for (int k = 0; k < K; ++k) {
-        const double s = column_sum_256(partials, nblk, k, red);
-        if (threadIdx.x == 0) out[k] = (float)s;
-    }
 }
 
 // sel: bit c set when class c is in K; nsel = |K|
@@ -163,7 +142,7 @@ __global__ __launch_bounds__(256) void ft_grad_kernel(const float* __restrict__ 
     const float gs = gscale ? gscale[0] : 1.f;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
         float z[NC];
-        ft_load<NC, ONE>(logits, p, z);
+        uh_head_load<NC, ONE>(logits, p, z);
         const int t = (int)uh_mask_quot(mask[p], mask_div);
         FtPixel<NC> px;
         ft_pixel<NC>(z, t, prm, px);
@@ -192,15 +171,6 @@ __global__ __launch_bounds__(256) void ft_grad_kernel(const float* __restrict__ 
     }
 }
 
-// f(NC, ONE): (2, true) for the one-channel head, (ncls, false) otherwise
-template <typename F>
-inline void ft_head_dispatch(int ncls, F&& f) {
-    uh_class_dispatch<FT_MAXC>(ncls, [&](auto nc) {
-        if constexpr (decltype(nc)::value == 1) f(std::integral_constant<int, 2>{}, std::true_type{});
-        else f(nc, std::false_type{});
-    });
-}
-
 template <typename F>
 inline void ft_pow_dispatch(float gamma, F&& f) {
     if (gamma == 0.f) f(std::integral_constant<int, FT_POW0>{});
@@ -213,7 +183,7 @@ inline int ft_classes_of(int ncls) { return ncls == 1 ? 2 : ncls; }
 
 // head, weights (HOST, one per class; two for the one-channel head) and gamma
 bool ft_focal_ok(const char* who, int ncls, const float* weights, float gamma, FtParams* prm) {
-    if (ncls < 1 || ncls > FT_MAXC) { uh_set_error("%s: heads of 1 (sigmoid) to %d (softmax) classes, got %d", who, FT_MAXC, ncls); return false; }
+    if (!uh_loss_head_ok(who, ncls, FT_MAXC)) return false;
     if (!weights) { uh_set_error("%s: null class weights", who); return false; }
     const int C = ft_classes_of(ncls);
     for (int c = 0; c < FT_MAXC; ++c) prm->w[c] = 0.f;
@@ -228,7 +198,7 @@ bool ft_focal_ok(const char* who, int ncls, const float* weights, float gamma, F
 
 // alpha, beta and the class subset K (HOST ids, distinct, inside the head)
 bool ft_tversky_ok(const char* who, int ncls, double alpha, double beta, const int* classes, int K, unsigned* sel) {
-    if (ncls < 1 || ncls > FT_MAXC) { uh_set_error("%s: heads of 1 (sigmoid) to %d (softmax) classes, got %d", who, FT_MAXC, ncls); return false; }
+    if (!uh_loss_head_ok(who, ncls, FT_MAXC)) return false;
     if (!(alpha >= 0.0) || !(beta >= 0.0) || !(alpha + beta > 0.0) || !(alpha + beta <= 1.0e30)) {
         uh_set_error("%s: alpha and beta must be finite and >= 0 with alpha + beta > 0, got %g and %g", who, alpha, beta);
         return false;
@@ -258,15 +228,13 @@ extern "C" int uh_focal_tversky_sums(const float* logits, const int64_t* mask, i
     hipStream_t st = (hipStream_t)stream;
     const int nblk = loss_nblk(npix);
     ft_pow_dispatch(gamma, [&](auto gm) {
-        ft_head_dispatch(ncls, [&](auto nc, auto one) {
+        uh_loss_head_dispatch<FT_MAXC>(ncls, [&](auto nc, auto one) {
             hipLaunchKernelGGL((ft_sums_kernel<decltype(nc)::value, decltype(gm)::value, decltype(one)::value>), dim3(nblk), dim3(256), 0,
                                st, logits, mask, mask_div, prm, npix, (float*)ws);
         });
     });
     UH_CHECK_LAUNCH("ft_sums_kernel");
-    hipLaunchKernelGGL(ft_colsum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nblk, uh_focal_tversky_nsums(ncls), sums);
-    UH_CHECK_LAUNCH("ft_colsum_kernel");
-    return UH_OK;
+    return uh_loss_colsum_launch((const float*)ws, nblk, uh_focal_tversky_nsums(ncls), sums, st);
 }
 
 extern "C" int uh_focal_tversky_finish(const float* sums, int ncls, double alpha, double beta, const int* classes, int K, float* out,
@@ -291,7 +259,7 @@ extern "C" int uh_focal_tversky_grad(const float* logits, const int64_t* mask, i
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = uh_flat_grid(npix, UH_GRID_CAP);
     ft_pow_dispatch(gamma, [&](auto gm) {
-        ft_head_dispatch(ncls, [&](auto nc, auto one) {
+        uh_loss_head_dispatch<FT_MAXC>(ncls, [&](auto nc, auto one) {
             hipLaunchKernelGGL((ft_grad_kernel<decltype(nc)::value, decltype(gm)::value, decltype(one)::value>), dim3(grid), dim3(256), 0,
                                st, logits, mask, mask_div, prm, alpha, beta, sel, K, npix, sums, gscale, dlogits);
         });

@@ -8,7 +8,7 @@
 //   uh_dice_sums               per-group sums for dice_coeff(reduce_batch_first=False) (evaluate.py:65).
 //   uh_boundary_loss           utils/boundary_loss.py:5-118, literal behaviour: value only.
 // Reductions: per-thread -> wave shuffle -> LDS -> per-block partial row -> one finishing block in double.
-#include "uh_loss_reduce.h"     // LOSS_MAXBLK, LOSS_ROW, loss_nblk, block_reduce_store, column_sum_256, uh_mask_quot
+#include "uh_loss_reduce.h"     // LOSS_MAXBLK, LOSS_ROW, loss_nblk, block_reduce_store, column_sum_256, uh_mask_quot, uh_loss_colsum_launch
 
 extern "C" size_t uh_loss_ws_bytes(int64_t n) {
     (void)n;
@@ -22,6 +22,12 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* __restric
         double s = column_sum_256(partials, nblk, k, red);
         if (threadIdx.x == 0) out[k] = (float)s;
     }
+}
+
+int uh_loss_colsum_launch(const float* partials, int nblk, int K, float* sums, hipStream_t st) {
+    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, partials, nblk, K, sums);
+    UH_CHECK_LAUNCH("loss_finish_kernel");
+    return UH_OK;
 }
 
 __device__ __forceinline__ float bin_target(const int64_t* mask, int mask_div, const float* tf, int64_t i) {
@@ -80,9 +86,7 @@ extern "C" int uh_bce_dice_sums(const float* logits, const int64_t* mask, int ma
     int nblk = loss_nblk(n);
     hipLaunchKernelGGL(bce_dice_sums_kernel, dim3(nblk), dim3(256), 0, st, logits, mask, mask_div, target_f, n, (float*)ws);
     UH_CHECK_LAUNCH("bce_dice_sums_kernel");
-    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nblk, 4, sums);
-    UH_CHECK_LAUNCH("loss_finish_kernel");
-    return UH_OK;
+    return uh_loss_colsum_launch((const float*)ws, nblk, 4, sums, st);
 }
 
 __global__ __launch_bounds__(256) void bce_dice_grad_kernel(const float* __restrict__ logits, const int64_t* __restrict__ mask,
@@ -115,9 +119,7 @@ extern "C" int uh_bce_dice_grad(const float* logits, const int64_t* mask, int ma
                                 const float* sums, double n_mean, float w_bce, float w_dice, const float* gscale,
                                 float* dlogits, uh_stream stream) {
     UH_REQUIRE(logits && (mask || target_f) && sums && dlogits && n > 0 && n_mean > 0, "uh_bce_dice_grad: bad args");
-    int64_t g = (n + 255) / 256;
-    if (g > 256 * 16) g = 256 * 16;
-    hipLaunchKernelGGL(bce_dice_grad_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, logits, mask, mask_div,
+    hipLaunchKernelGGL(bce_dice_grad_kernel, dim3(uh_flat_grid(n, UH_GRID_CAP)), dim3(256), 0, (hipStream_t)stream, logits, mask, mask_div,
                        target_f, n, sums, (float)(1.0 / n_mean), w_bce, w_dice, gscale, dlogits);
     UH_CHECK_LAUNCH("bce_dice_grad_kernel");
     return UH_OK;
@@ -198,29 +200,23 @@ __global__ __launch_bounds__(256) void ce_dice_grad_kernel(const float* __restri
     }
 }
 
-#define UH_NC_SWITCH(ncls, ...)                \
-    switch (ncls) {                            \
-        case 2: { constexpr int NC = 2; __VA_ARGS__ } break; \
-        case 3: { constexpr int NC = 3; __VA_ARGS__ } break; \
-        case 4: { constexpr int NC = 4; __VA_ARGS__ } break; \
-        case 5: { constexpr int NC = 5; __VA_ARGS__ } break; \
-        case 6: { constexpr int NC = 6; __VA_ARGS__ } break; \
-        case 7: { constexpr int NC = 7; __VA_ARGS__ } break; \
-        case 8: { constexpr int NC = 8; __VA_ARGS__ } break; \
-        default: uh_set_error("multi-class losses support 2..8 classes, got %d", ncls); return UH_EINVAL; \
-    }
+static bool ce_head_ok(int ncls) {
+    if (ncls < 2 || ncls > MAXC) { uh_set_error("multi-class losses support 2..8 classes, got %d", ncls); return false; }
+    return true;
+}
 
 extern "C" int uh_ce_dice_sums(const float* logits, const int64_t* mask, int64_t npix, int ncls, float* sums, void* ws,
                                size_t ws_bytes, uh_stream stream) {
     UH_REQUIRE(logits && mask && sums && ws && npix > 0, "uh_ce_dice_sums: bad args");
     UH_REQUIRE(ws_bytes >= uh_loss_ws_bytes(npix), "uh_ce_dice_sums: workspace too small");
     hipStream_t st = (hipStream_t)stream;
+    if (!ce_head_ok(ncls)) return UH_EINVAL;
     int nblk = loss_nblk(npix);
-    UH_NC_SWITCH(ncls, hipLaunchKernelGGL(ce_dice_sums_kernel<NC>, dim3(nblk), dim3(256), 0, st, logits, mask, npix, (float*)ws););
+    uh_class_dispatch<MAXC, 2>(ncls, [&](auto nc) {
+        hipLaunchKernelGGL(ce_dice_sums_kernel<decltype(nc)::value>, dim3(nblk), dim3(256), 0, st, logits, mask, npix, (float*)ws);
+    });
     UH_CHECK_LAUNCH("ce_dice_sums_kernel");
-    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, nblk, 1 + 3 * ncls, sums);
-    UH_CHECK_LAUNCH("loss_finish_kernel");
-    return UH_OK;
+    return uh_loss_colsum_launch((const float*)ws, nblk, 1 + 3 * ncls, sums, st);
 }
 
 extern "C" int uh_ce_dice_grad(const float* logits, const int64_t* mask, int64_t npix, int ncls, const float* sums,
@@ -228,11 +224,13 @@ extern "C" int uh_ce_dice_grad(const float* logits, const int64_t* mask, int64_t
                                uh_stream stream) {
     UH_REQUIRE(logits && mask && sums && dlogits && npix > 0 && n_mean > 0, "uh_ce_dice_grad: bad args");
     hipStream_t st = (hipStream_t)stream;
-    int64_t g = (npix + 255) / 256;
-    if (g > 256 * 16) g = 256 * 16;
+    if (!ce_head_ok(ncls)) return UH_EINVAL;
+    const unsigned grid = uh_flat_grid(npix, UH_GRID_CAP);
     float inv_n = (float)(1.0 / n_mean);
-    UH_NC_SWITCH(ncls, hipLaunchKernelGGL(ce_dice_grad_kernel<NC>, dim3((unsigned)g), dim3(256), 0, st, logits, mask, npix, sums,
-                                          inv_n, w_ce, w_dice, gscale, dlogits););
+    uh_class_dispatch<MAXC, 2>(ncls, [&](auto nc) {
+        hipLaunchKernelGGL(ce_dice_grad_kernel<decltype(nc)::value>, dim3(grid), dim3(256), 0, st, logits, mask, npix, sums, inv_n, w_ce,
+                           w_dice, gscale, dlogits);
+    });
     UH_CHECK_LAUNCH("ce_dice_grad_kernel");
     return UH_OK;
 }

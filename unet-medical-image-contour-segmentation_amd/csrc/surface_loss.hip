@@ -18,28 +18,16 @@
 // 16-byte aligned; other heads (NC = 3: 12-byte rows) move them as NC dwords, which a wave still spends on whole cache lines.
 // No floating-point atomics; grid sizes depend on the shape alone: a call gives the same bits every time, and a pixel's
 // gradient depends on that pixel's logits, its own image's labels and the scale factor only.
-#include "uh_launch.h"
+#include "uh_loss_reduce.h"     // LOSS_MAXBLK, loss_nblk, uh_label_quot, uh_loss_head_ok
 #include "uh_vec.h"
 
 namespace {
 
 constexpr int SL_MAXC = 8;                     // classes of the head, and selected classes per call
-constexpr int SL_MAXBLK = 1024;                // partial sums of the value
 constexpr int SL_MAX_DIM = 32768;              // uh_edt_sq_u8's limits (squared distances are kept in 31 bits)
 constexpr unsigned SL_NO_FEATURE = 0xFFFFFFFFu;
 
 struct SlClasses { int k; int id[SL_MAXC]; };  // by value: every index below is a compile-time constant after unrolling
-
-// floor(m / div), torch's `//`; class ids in [0, 2^31) -- every real mask -- take a shift or a 32-bit division (loss.hip)
-__device__ __forceinline__ long long sl_quot(long long m, int div) {
-    if ((unsigned long long)m < (1ull << 31)) {
-        const int v = (int)m;
-        return div == 1 ? v : (div == 2 ? (v >> 1) : v / div);
-    }
-    long long q = m / div;
-    if (m < 0 && q * div != m) --q;
-    return q;
-}
 
 __device__ __forceinline__ float sl_phi(unsigned d2, bool inside) {
     if (d2 == SL_NO_FEATURE) return 0.0f;                          // T_c is empty in this image
@@ -114,12 +102,12 @@ __global__ __launch_bounds__(256) void sl_border_kernel(const int64_t* __restric
     const int b = blockIdx.y;
     const int64_t* img = mask + (long long)b * hw;
     const int x = (int)(p % W), y = (int)(p / W);
-    const long long q = sl_quot(img[p], div);
+    const long long q = uh_label_quot(img[p], div);
     const bool frame = x == 0 || y == 0 || x == W - 1 || y == H - 1;
     long long ql = q, qr = q, qu = q, qd = q;
     if (!frame) {
-        ql = sl_quot(img[p - 1], div); qr = sl_quot(img[p + 1], div);
-        qu = sl_quot(img[p - W], div); qd = sl_quot(img[p + W], div);
+        ql = uh_label_quot(img[p - 1], div); qr = uh_label_quot(img[p + 1], div);
+        qu = uh_label_quot(img[p - W], div); qd = uh_label_quot(img[p + W], div);
     }
 #pragma unroll
     for (int k = 0; k < SL_MAXC; ++k)
@@ -144,7 +132,7 @@ __global__ __launch_bounds__(256) void sl_map_kernel(const unsigned* __restrict_
     const long long c = sl_class_of(cls, k);
     const long long base = (long long)k * n;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        phi[base + i] = sl_phi(d2[base + i], sl_quot(mask[i], div) == c);
+        phi[base + i] = sl_phi(d2[base + i], uh_label_quot(mask[i], div) == c);
 }
 
 // sum over the selected classes of p_c phi_c at pixel i, phi formed here; NC = 1: the sigmoid head (one map)
@@ -179,7 +167,7 @@ __global__ __launch_bounds__(256) void sl_sums_kernel(const float* __restrict__ 
     double acc = 0.0;
     const bool vec = sl_aligned16(logits);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        acc = __dadd_rn(acc, sl_pixel_term<NC>(logits, d2, sl_quot(mask[i], div), cls, i, n, vec));
+        acc = __dadd_rn(acc, sl_pixel_term<NC>(logits, d2, uh_label_quot(mask[i], div), cls, i, n, vec));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc = __dadd_rn(acc, __shfl_xor(acc, o, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(256) void sl_grad_kernel(const float* __restrict__ 
     const float gs = (gscale ? gscale[0] : 1.f) * scale;
     const bool vec = sl_aligned16(logits) && sl_aligned16(dl);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const long long q = sl_quot(mask[i], div);
+        const long long q = uh_label_quot(mask[i], div);
         if constexpr (NC == 1) {
             const float sg = sl_sigmoid(logits[i]);
             dl[i] = gs * (sl_phi(d2[i], q == cls.id[0]) * (sg * (1.f - sg)));
@@ -269,7 +257,7 @@ bool sl_classes_ok(const char* who, const int* classes, int K, int ncls, SlClass
     return true;
 }
 
-// workspace: [D K*B*H*W u32][border K*B*H*W u8][EDT workspace][partials SL_MAXBLK f64]
+// workspace: [D K*B*H*W u32][border K*B*H*W u8][EDT workspace][partials LOSS_MAXBLK f64]
 struct SlWs { unsigned* d2; unsigned char* border; void* edt; size_t edt_bytes; double* partials; };
 
 SlWs sl_carve(void* ws, int B, int H, int W, int K) {
@@ -284,11 +272,6 @@ SlWs sl_carve(void* ws, int B, int H, int W, int K) {
     return s;
 }
 
-int sl_head_ok(const char* who, int ncls) {
-    if (ncls < 1 || ncls > SL_MAXC) { uh_set_error("%s: heads of 1 (sigmoid) to %d (softmax) classes, got %d", who, SL_MAXC, ncls); return 0; }
-    return 1;
-}
-
 // border of every selected class, then D over the K * B border images into the workspace
 int sl_build_d2(const char* who, const int64_t* mask, int mask_div, const SlClasses& cls, int B, int H, int W, const SlWs& s,
                 hipStream_t st) {
@@ -298,18 +281,13 @@ int sl_build_d2(const char* who, const int64_t* mask, int mask_div, const SlClas
     return uh_edt_sq_u8(s.border, s.d2, cls.k * B, H, W, s.edt, s.edt_bytes, (uh_stream)st);
 }
 
-int sl_sums_nblk(long long n) {
-    long long b = (n + 2047) / 2048;
-    return (int)(b > SL_MAXBLK ? SL_MAXBLK : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" size_t uh_surface_loss_ws_bytes(int B, int H, int W, int K) {
     if (B <= 0 || H <= 0 || W <= 0 || K < 1 || K > SL_MAXC || (long long)K * B > 65535) return 0;
     const size_t n = (size_t)K * B * H * W;
     return sl_align16(n * sizeof(unsigned)) + sl_align16(n) + sl_align16(uh_edt_sq_ws_bytes(K * B, H, W)) +
-           (size_t)SL_MAXBLK * sizeof(double) + 256;
+           (size_t)LOSS_MAXBLK * sizeof(double) + 256;
 }
 
 #define SL_COMMON_CHECKS(who, ncls)                                                                             \
@@ -358,12 +336,12 @@ extern "C" int uh_surface_dist_map(const int64_t* mask, int mask_div, const int*
 extern "C" int uh_surface_loss_sums(const float* logits, const int64_t* mask, int mask_div, const int* classes, int K, int ncls, int B,
                                     int H, int W, double n_mean, float w, float* out, void* ws, size_t ws_bytes, uh_stream stream) {
     UH_REQUIRE(logits && mask && classes && out && ws, "uh_surface_loss_sums: null pointer");
-    if (!sl_head_ok("uh_surface_loss_sums", ncls)) return UH_EINVAL;
+    if (!uh_loss_head_ok("uh_surface_loss_sums", ncls, SL_MAXC)) return UH_EINVAL;
     UH_REQUIRE(n_mean > 0, "uh_surface_loss_sums: n_mean must be positive");
     SL_COMMON_CHECKS("uh_surface_loss_sums", ncls);
     const int rc = sl_build_d2("uh_surface_loss_sums", mask, mask_div, cls, B, H, W, s, st);
     if (rc != UH_OK) return rc;
-    const int nblk = sl_sums_nblk(n);
+    const int nblk = loss_nblk(n);
     uh_class_dispatch<SL_MAXC>(ncls, [&](auto nc) {
         hipLaunchKernelGGL((sl_sums_kernel<decltype(nc)::value>), dim3(nblk), dim3(256), 0, st, logits, mask, mask_div, cls,
                            (const unsigned*)s.d2, n, s.partials);
@@ -378,7 +356,7 @@ extern "C" int uh_surface_loss_grad(const float* logits, const int64_t* mask, in
                                     int H, int W, double n_mean, float w, const float* gscale, float* dlogits, int rebuild,
                                     void* ws, size_t ws_bytes, uh_stream stream) {
     UH_REQUIRE(logits && mask && classes && dlogits && ws, "uh_surface_loss_grad: null pointer");
-    if (!sl_head_ok("uh_surface_loss_grad", ncls)) return UH_EINVAL;
+    if (!uh_loss_head_ok("uh_surface_loss_grad", ncls, SL_MAXC)) return UH_EINVAL;
     UH_REQUIRE(n_mean > 0, "uh_surface_loss_grad: n_mean must be positive");
     SL_COMMON_CHECKS("uh_surface_loss_grad", ncls);
     if (rebuild) {

@@ -1,6 +1,7 @@
 """The optimizer step of /root/reference/train.py:113-159 on the HIP path.
 
-    seg_loss(...)     loss assembly of train.py:118-142 (fused single-pass kernels)
+    seg_loss(...)     loss assembly of train.py:118-142 over the nodes of losses.py: the base node (BCE / CE + Dice, or
+                      focal + Tversky), then the surface term, then the distillation term
     FusedRMSprop      clip_grad_norm_(1.0) + RMSprop(lr, weight_decay=1e-8, momentum=0.999) of
                       train.py:80-81,157-158 as two passes over one flat fp32 buffer; optionally an exponential moving
                       average of the parameters in the same pass (EmaConfig), and state_dict / load_state_dict
@@ -24,57 +25,55 @@ import torch
 import torch.nn as nn
 
 from . import dp as dpmod
+from . import losses
 from . import ops
 from ._lib import LIB
 
 
 # ----------------------------------------------------------------------------------- loss
-def _add_surface(terms: Dict[str, torch.Tensor], lg: torch.Tensor, true_masks: torch.Tensor, n_classes: int, weight: float,
-                 classes, reduce_sums, world) -> Dict[str, torch.Tensor]:
-    """total += weight * surface (DESIGN.md section 3 "Surface loss"); `surface` joins the reported terms.  The fused loss's
-    NaN flag was formed without the new term and is dropped: train_step tests the new total itself."""
-    from .utils.surface_loss import head_classes
-    weighted, value = ops.SurfaceLossFn.apply(lg, true_masks, 2 if n_classes == 1 else 1, head_classes(n_classes, classes),
-                                              float(weight), reduce_sums, world)
+def _add_term(terms: Dict[str, torch.Tensor], weighted: torch.Tensor, **reported) -> None:
+    """total += weighted; `reported` joins the terms.  The fused loss's NaN flag was formed without the new term and is dropped:
+    train_step tests the new total itself."""
     terms["loss"] = terms["loss"] + weighted
-    terms["surface"] = value
+    terms.update(reported)
     terms.pop("nan_flag", None)
-    return terms
 
 
-def _add_distill(terms: Dict[str, torch.Tensor], masks_pred: torch.Tensor, teacher_logits: Optional[torch.Tensor], n_classes: int,
-                 distill, reduce_sums, world) -> Dict[str, torch.Tensor]:
-    """total += w * kd (DESIGN.md section 3 "Distillation"); `kd` and `kd_agree` join the reported terms.  The fused loss's NaN
-    flag was formed without the new term and is dropped, as _add_surface drops it."""
-    from .utils.distill import distill_terms
-    if teacher_logits is None:
-        raise ValueError("seg_loss: distill=... needs teacher_logits (Distiller.teacher_logits(images))")
-    weighted, kd, agree = distill_terms(masks_pred, teacher_logits, n_classes, distill, reduce_sums=reduce_sums, world=world)
-    terms["loss"] = terms["loss"] + weighted
-    terms["kd"] = kd
-    terms["kd_agree"] = agree
-    terms.pop("nan_flag", None)
-    return terms
+def _pair_terms(lg: torch.Tensor, true_masks: torch.Tensor, mask_div: int, boundary_weight, reduce_sums, world):
+    """The default base node: BCE + Dice + 0.25 boundary for the one-channel head (train.py:119-134), CE + Dice otherwise
+    (train.py:136-142; its boundary term, train.py:143-147, is commented out: weight 0)."""
+    if lg.dim() == 3:
+        w_b = 0.25 if boundary_weight is None else boundary_weight
+        total, bce, dice, bnd, nan_flag = losses.SegLossBinaryFn.apply(lg, true_masks, mask_div, w_b, 51, 15.0, reduce_sums, world)
+        terms = {"loss": total, "bce": bce, "dice": dice, "boundary": bnd}
+        if nan_flag is not None:
+            terms["nan_flag"] = nan_flag          # float 0 / 1 written by the loss's finishing block (train.py:149)
+        return terms
+    w_b = 0.0 if boundary_weight is None else boundary_weight
+    out = losses.SegLossMulticlassFn.apply(lg, true_masks, w_b, 51, 7.0, reduce_sums, world)
+    return {"loss": out[0], "ce": out[1].detach(), "dice": out[2].detach(), "boundary": out[3].detach()}
 
 
-def _focal_tversky_terms(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int, loss, w_b: float, reduce_sums,
+def _focal_tversky_terms(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int, loss, boundary_weight, reduce_sums,
                          world) -> Dict[str, torch.Tensor]:
-    """The loss node of seg_loss with `loss` (a LossConfig): focal + tversky (DESIGN.md section 3 "Focal / Tversky loss") in
-    place of the CE + Dice pair, + w_b * boundary_loss as the pair has it (a value without gradient, per rank)."""
+    """The base node with `loss` (a LossConfig): focal + tversky (DESIGN.md section 3 "Focal / Tversky loss") in place of the
+    CE + Dice pair, + w_b * boundary_loss as the pair has it (a value without gradient, per rank)."""
     from .utils.focal_loss import focal_tversky_terms
+    w_b = (0.25 if n_classes == 1 else 0.0) if boundary_weight is None else float(boundary_weight)
     total, focal, tversky = focal_tversky_terms(masks_pred, true_masks, n_classes, loss, reduce_sums=reduce_sums, world=world)
     terms = {"loss": total, "focal": focal, "tversky": tversky}
-    if w_b != 0.0:
-        B, _, H, W = masks_pred.shape
-        if n_classes == 1:
-            bnd = ops.boundary_loss_mask_value(masks_pred.detach().squeeze(1), true_masks, 2, 51, 15.0)[0]      # train.py:134
-        else:
-            lg = masks_pred.detach().permute(0, 2, 3, 1).float().contiguous()
-            bnd = ops.boundary_loss_value(lg[..., 1], n_classes, H * W * n_classes, true_masks.float(), B, H, W, 51, 7.0)[0]
-        terms["loss"] = total + w_b * bnd
-        terms["boundary"] = bnd
-    else:
+    if w_b == 0.0:
         terms["boundary"] = torch.zeros((), dtype=torch.float32, device=total.device)
+        return terms
+    lg, mask_div = losses.head_layout(masks_pred.detach(), n_classes)
+    if n_classes == 1:
+        bnd = losses.boundary_loss_mask_value(lg, true_masks, mask_div, 51, 15.0)[0]                               # train.py:134
+    else:
+        lg = lg.float().contiguous()
+        B, H, W, C = lg.shape
+        bnd = losses.boundary_loss_value(lg[..., 1], C, H * W * C, true_masks.float(), B, H, W, 51, 7.0)[0]
+    terms["loss"] = total + w_b * bnd
+    terms["boundary"] = bnd
     return terms
 
 
@@ -91,33 +90,27 @@ def seg_loss(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int,
     distill (a utils.distill.DistillConfig or its spec string; default None: nothing is launched, allocated or imported for it)
     with teacher_logits (the teacher's logits for the same images, shaped like masks_pred): adds w * kd after the surface term,
     and the terms carry "kd" and "kd_agree"."""
-    if distill is not None:
-        terms = seg_loss(masks_pred, true_masks, n_classes, reduce_sums=reduce_sums, world=world, boundary_weight=boundary_weight,
-                         surface_weight=surface_weight, surface_classes=surface_classes, **({} if loss is None else {"loss": loss}))
-        return _add_distill(terms, masks_pred, teacher_logits, n_classes, distill, reduce_sums, world)
-    if loss is not None:
-        w_b = (0.25 if n_classes == 1 else 0.0) if boundary_weight is None else float(boundary_weight)
-        terms = _focal_tversky_terms(masks_pred, true_masks, n_classes, loss, w_b, reduce_sums, world)
-        if surface_weight:
-            lg = masks_pred.squeeze(1) if n_classes == 1 else masks_pred.permute(0, 2, 3, 1)
-            _add_surface(terms, lg, true_masks, n_classes, surface_weight, surface_classes, reduce_sums, world)
-        return terms
-    if n_classes == 1:
-        w_b = 0.25 if boundary_weight is None else boundary_weight          # train.py:134
-        lg = masks_pred.squeeze(1)
-        total, bce, dice, bnd, nan_flag = ops.SegLossBinaryFn.apply(lg, true_masks, 2, w_b, 51, 15.0, reduce_sums, world)
-        terms = {"loss": total, "bce": bce, "dice": dice, "boundary": bnd}
-        if nan_flag is not None:
-            terms["nan_flag"] = nan_flag          # float 0 / 1 written by the loss's finishing block (train.py:149)
-        if surface_weight:
-            _add_surface(terms, lg, true_masks, 1, surface_weight, surface_classes, reduce_sums, world)
-        return terms
-    w_b = 0.0 if boundary_weight is None else boundary_weight               # train.py:143-147 is commented out
-    lg = masks_pred.permute(0, 2, 3, 1)
-    out = ops.SegLossMulticlassFn.apply(lg, true_masks, w_b, 51, 7.0, reduce_sums, world)
-    terms = {"loss": out[0], "ce": out[1].detach(), "dice": out[2].detach(), "boundary": out[3].detach()}
+    if loss is None:
+        lg, mask_div = losses.head_layout(masks_pred, n_classes)
+        terms = _pair_terms(lg, true_masks, mask_div, boundary_weight, reduce_sums, world)
+    else:
+        terms = _focal_tversky_terms(masks_pred, true_masks, n_classes, loss, boundary_weight, reduce_sums, world)
+        # (the surface term's view of masks_pred is made behind the focal node, which has one of its own: autograd sums the
+        # nodes' gradients in the reverse order of their views, and three fp32 summands do not commute)
+        lg, mask_div = losses.head_layout(masks_pred, n_classes)
     if surface_weight:
-        _add_surface(terms, lg, true_masks, n_classes, surface_weight, surface_classes, reduce_sums, world)
+        # DESIGN.md section 3 "Surface loss"
+        from .utils.surface_loss import head_classes
+        weighted, value = losses.SurfaceLossFn.apply(lg, true_masks, mask_div, head_classes(n_classes, surface_classes),
+                                                     float(surface_weight), reduce_sums, world)
+        _add_term(terms, weighted, surface=value)
+    if distill is not None:
+        # DESIGN.md section 3 "Distillation"
+        from .utils.distill import distill_terms
+        if teacher_logits is None:
+            raise ValueError("seg_loss: distill=... needs teacher_logits (Distiller.teacher_logits(images))")
+        weighted, kd, agree = distill_terms(masks_pred, teacher_logits, n_classes, distill, reduce_sums=reduce_sums, world=world)
+        _add_term(terms, weighted, kd=kd, kd_agree=agree)
     return terms
 
 
@@ -554,14 +547,12 @@ def train_step(model: nn.Module, optimizer, images: torch.Tensor, true_masks: to
     assert images.shape[1] == model.n_channels, \
         f"Network has been defined with {model.n_channels} input channels, but loaded images have " \
         f"{images.shape[1]} channels. Please check that the images are loaded correctly."   # train.py:108-111
-    extra = {} if loss is None else {"loss": loss}
-    if distill is not None:
-        extra.update(distill=distill.config, teacher_logits=distill.teacher_logits(images))
+    teacher_logits = None if distill is None else distill.teacher_logits(images)
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
         masks_pred = model(images)
         terms = seg_loss(masks_pred, true_masks, model.n_classes, reduce_sums=reduce_sums, world=world,
                          boundary_weight=boundary_weight, surface_weight=surface_weight, surface_classes=surface_classes,
-                         **extra)
+                         loss=loss, distill=None if distill is None else distill.config, teacher_logits=teacher_logits)
     if cc_loss and model.n_classes == 1:
         # the block train.py:124-132 keeps commented out (BASELINE config 5 turns it on): a Python float, no gradient.
         # sigmoid(x) > 0.5 <=> x > 0, so the 0/1 threshold mask stands in for the probabilities.  The masks stay on the
@@ -820,8 +811,7 @@ class TrainStepper:
             return train_step(self.model, self.optimizer, images, true_masks, amp=self.amp,
                               reduce_sums=self.reduce_sums, world=world, check_nan=self.check_nan, cc_loss=self.cc_loss,
                               surface_weight=self.surface_weight, surface_classes=self.surface_classes,
-                              **({} if self.loss is None else {"loss": self.loss}),
-                              **({} if self.distill is None else {"distill": self.distill}))
+                              loss=self.loss, distill=self.distill)
 
 
 class GraphedTrainStepper(TrainStepper):
@@ -834,31 +824,24 @@ class GraphedTrainStepper(TrainStepper):
 
     def __init__(self, model: nn.Module, *args, warmup: int = 2, **kw):
         kw.setdefault("wgrad_stream", False)         # one stream unless asked for: the graph is for launch-bound small models
-        self.distill = kw.get("distill")
-        self._refuse_distill()                       # (before a teacher is built for it)
+        self._refuse_uncaptured(distill=kw.get("distill"))          # (before a teacher is built for it)
         super().__init__(model, *args, **kw)
         if self.world != 1:
             raise RuntimeError("GraphedTrainStepper is single-process; use TrainStepper with torch.distributed")
         if self.cc_loss:
             raise RuntimeError("connected_component_loss returns a Python float (a device read-back every step): not capturable")
-        self._refuse_surface()
-        self._refuse_loss()
-        self._refuse_distill()
+        self._refuse_uncaptured(self.surface_weight, self.loss, self.distill)
         self._warmup = max(1, warmup)
         self._graph = None
         self._key = None
 
-    def _refuse_surface(self):
-        if self.surface_weight:
-            raise RuntimeError("GraphedTrainStepper does not capture the surface loss (surface_weight must be 0): use TrainStepper")
-
-    def _refuse_loss(self):
-        if self.loss is not None:
-            raise RuntimeError("GraphedTrainStepper does not capture the focal / Tversky loss (loss must be None): use TrainStepper")
-
-    def _refuse_distill(self):
-        if self.distill is not None:
-            raise RuntimeError("GraphedTrainStepper does not capture distillation (distill must be None): use TrainStepper")
+    @staticmethod
+    def _refuse_uncaptured(surface_weight=0.0, loss=None, distill=None):
+        for on, what, off in ((bool(surface_weight), "the surface loss", "surface_weight must be 0"),
+                              (loss is not None, "the focal / Tversky loss", "loss must be None"),
+                              (distill is not None, "distillation", "distill must be None")):
+            if on:
+                raise RuntimeError(f"GraphedTrainStepper does not capture {what} ({off}): use TrainStepper")
 
     def _eager_step(self, images, masks):
         with self._step_state(images, None):         # (single process: per-rank BatchNorm statistics, world = self.world)
@@ -895,9 +878,7 @@ class GraphedTrainStepper(TrainStepper):
         self._key = (tuple(images.shape), tuple(masks.shape), float(opt.param_groups[0]["lr"]))
 
     def step(self, images, true_masks):
-        self._refuse_surface()
-        self._refuse_loss()
-        self._refuse_distill()
+        self._refuse_uncaptured(self.surface_weight, self.loss, self.distill)
         self._refuse_averaged()
         key = (tuple(images.shape), tuple(true_masks.shape), float(self.optimizer.param_groups[0]["lr"]))
         if self._graph is None or key != self._key:

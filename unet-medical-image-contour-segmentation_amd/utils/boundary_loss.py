@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from .. import ops
+from .. import losses
 
 
 def boundary_loss(pred_mask, target_mask, edge_width=64, edge_weight=5.0, smooth=1e-6):
@@ -38,5 +38,5 @@ def boundary_loss(pred_mask, target_mask, edge_width=64, edge_weight=5.0, smooth
     target = target.contiguous()
     if tuple(target.shape) != (B, H, W):
         raise ValueError(f"target {tuple(target.shape)} does not match predictions {(B, H, W)}")
-    out = ops.boundary_loss_value(pred, ps, bs, target, B, H, W, int(edge_width), float(edge_weight), float(smooth))
+    out = losses.boundary_loss_value(pred, ps, bs, target, B, H, W, int(edge_width), float(edge_weight), float(smooth))
     return out.view(())

@@ -12,7 +12,7 @@ import math
 import torch
 from torch import Tensor
 
-from .. import ops
+from .. import losses
 
 
 def _groups(shape, all_dims: bool) -> int:
@@ -24,7 +24,7 @@ def dice_coeff(input: Tensor, target: Tensor, reduce_batch_first: bool = False, 
     assert input.size() == target.size()
     assert input.dim() == 3 or not reduce_batch_first
     ngroups = _groups(input.shape, all_dims=(input.dim() == 2 or reduce_batch_first))
-    return ops.DiceCoeffFn.apply(input, target, ngroups, input.numel() // ngroups, float(epsilon))
+    return losses.DiceCoeffFn.apply(input, target, ngroups, input.numel() // ngroups, float(epsilon))
 
 
 def multiclass_dice_coeff(input: Tensor, target: Tensor, reduce_batch_first: bool = False, epsilon: float = 1e-6):

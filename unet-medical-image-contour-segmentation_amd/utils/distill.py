@@ -150,21 +150,16 @@ def distill_terms(student_logits: torch.Tensor, teacher_logits: torch.Tensor, n_
                   world: float = 1):
     """(w * kd, kd, agree) of student and teacher logits [B,n_classes,H,W] (or [B,H,W] for the one-channel head) as the models
     return them.  Only the first carries gradient, and only to the student."""
-    from .. import ops
+    from .. import losses
     cfg = DistillConfig.of(config)
     if cfg is None:
         raise ValueError("distill_loss needs a DistillConfig or a spec string")
     if tuple(student_logits.shape) != tuple(teacher_logits.shape):
         raise ValueError(f"distill_loss: student logits {tuple(student_logits.shape)} and teacher logits {tuple(teacher_logits.shape)} "
                          "differ in shape")
-    if n_classes == 1:
-        s = student_logits.squeeze(1) if student_logits.dim() == 4 else student_logits
-        t = teacher_logits.squeeze(1) if teacher_logits.dim() == 4 else teacher_logits
-        return ops.DistillLossFn.apply(s, t, cfg.T, cfg.w, reduce_sums, world)
-    if student_logits.dim() != 4 or student_logits.shape[1] != n_classes:
-        raise ValueError(f"distill_loss expects logits [B,{n_classes},H,W], got {tuple(student_logits.shape)}")
-    return ops.DistillLossFn.apply(student_logits.permute(0, 2, 3, 1), teacher_logits.permute(0, 2, 3, 1), cfg.T, cfg.w,
-                                   reduce_sums, world)
+    s, _ = losses.head_layout(student_logits, n_classes, "distill_loss")
+    t, _ = losses.head_layout(teacher_logits, n_classes, "distill_loss")
+    return losses.DistillLossFn.apply(s, t, cfg.T, cfg.w, reduce_sums, world)
 
 
 def distill_loss(student_logits: torch.Tensor, teacher_logits: torch.Tensor, n_classes: int, config) -> torch.Tensor:

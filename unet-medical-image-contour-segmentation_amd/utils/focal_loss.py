@@ -123,8 +123,8 @@ class LossConfig:
     def for_head(self, n_classes: int) -> Tuple[Tuple[float, ...], Tuple[int, ...]]:
         """(weights, classes) of this config on a head of `n_classes` outputs (1: the one-channel head, two classes); ValueError
         when the number of weights or a class does not fit the head."""
-        from .. import ops
-        return ops.focal_head(n_classes, self.weights, self.classes)
+        from .. import losses
+        return losses.focal_head(n_classes, self.weights, self.classes)
 
 
 LOSS_BARE = "focal=2,tversky=0.3/0.7"
@@ -133,18 +133,13 @@ LOSS_BARE = "focal=2,tversky=0.3/0.7"
 def focal_tversky_terms(logits: torch.Tensor, true_masks: torch.Tensor, n_classes: int, config, *, reduce_sums=None, world: float = 1):
     """(total, focal, tversky) of logits [B,n_classes,H,W] (or [B,H,W] for the one-channel head) as the model returns them and
     int labels [B,H,W] with the dataset's values (NOT yet // 2 for the one-channel head).  Only `total` carries gradient."""
-    from .. import ops
+    from .. import losses
     cfg = LossConfig.of(config)
     if cfg is None:
         raise ValueError("focal_tversky_loss needs a LossConfig or a spec string")
     w, cls = cfg.for_head(n_classes)
-    if n_classes == 1:
-        lg = logits.squeeze(1) if logits.dim() == 4 else logits
-        return ops.FocalTverskyLossFn.apply(lg, true_masks, 2, w, cfg.gamma, cfg.alpha, cfg.beta, cls, reduce_sums, world)
-    if logits.dim() != 4 or logits.shape[1] != n_classes:
-        raise ValueError(f"focal_tversky_loss expects logits [B,{n_classes},H,W], got {tuple(logits.shape)}")
-    return ops.FocalTverskyLossFn.apply(logits.permute(0, 2, 3, 1), true_masks, 1, w, cfg.gamma, cfg.alpha, cfg.beta, cls,
-                                        reduce_sums, world)
+    lg, mask_div = losses.head_layout(logits, n_classes, "focal_tversky_loss")
+    return losses.FocalTverskyLossFn.apply(lg, true_masks, mask_div, w, cfg.gamma, cfg.alpha, cfg.beta, cls, reduce_sums, world)
 
 
 def focal_tversky_loss(logits: torch.Tensor, true_masks: torch.Tensor, n_classes: int, config) -> torch.Tensor:

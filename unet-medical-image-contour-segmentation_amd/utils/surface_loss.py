@@ -30,36 +30,31 @@ def default_classes(n_classes: int) -> Tuple[int, ...]:
 
 def head_classes(n_classes: int, classes=None) -> Tuple[int, ...]:
     """`classes` checked against the head.  The binary head has one map, the foreground's."""
-    from .. import ops
+    from .. import losses
     if classes is None:
         return default_classes(n_classes)
     if n_classes == 1:
-        cls = ops.surface_classes(classes)
+        cls = losses.surface_classes(classes)
         if cls != (1,):
             raise ValueError(f"surface loss: the binary head has one class, the foreground (1); got {cls}")
         return cls
-    return ops.surface_classes(classes, n_classes)
+    return losses.surface_classes(classes, n_classes)
 
 
 def surface_distance_map(labels: torch.Tensor, classes, *, binary: bool = False) -> torch.Tensor:
     """Signed distance maps fp32 [K,B,H,W] of int labels [B,H,W] (or [H,W]) on the GPU, one per class id in `classes`.
     binary=True: the labels are the dataset's {0,1,2} and class c means (label // 2 == c), the binary head's target."""
-    from .. import ops
+    from .. import losses
     if labels.dim() == 2:
         labels = labels.unsqueeze(0)
-    return ops.surface_dist_map(labels, classes, 2 if binary else 1)
+    return losses.surface_dist_map(labels, classes, 2 if binary else 1)
 
 
 def surface_loss(logits: torch.Tensor, labels: torch.Tensor, n_classes: int, classes=None) -> torch.Tensor:
     """logits [B,n_classes,H,W] (or [B,H,W] for the binary head) as the model returns them, labels int [B,H,W] with the
     dataset's values (NOT yet // 2).  Returns the surface term; its gradient reaches the logits."""
-    from .. import ops
+    from .. import losses
     cls = head_classes(n_classes, classes)
-    if n_classes == 1:
-        lg = logits.squeeze(1) if logits.dim() == 4 else logits
-        weighted, _ = ops.SurfaceLossFn.apply(lg, labels, 2, cls, 1.0, None, 1)
-    else:
-        if logits.dim() != 4 or logits.shape[1] != n_classes:
-            raise ValueError(f"surface_loss expects logits [B,{n_classes},H,W], got {tuple(logits.shape)}")
-        weighted, _ = ops.SurfaceLossFn.apply(logits.permute(0, 2, 3, 1), labels, 1, cls, 1.0, None, 1)
+    lg, mask_div = losses.head_layout(logits, n_classes, "surface_loss")
+    weighted, _ = losses.SurfaceLossFn.apply(lg, labels, mask_div, cls, 1.0, None, 1)
     return weighted
