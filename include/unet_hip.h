@@ -448,6 +448,29 @@ int uh_rmsprop_step_ema(float* p, float* g, float* square_avg, float* momentum_b
                         uh_stream stream);
 int uh_ema_tick(int32_t* updates, const float* total_norm, uh_stream stream);
 int uh_swap_f32(float* a, float* b, int64_t n, uh_stream stream);
+/* The two other rules of the same pass (no counterpart in the reference; train.OptimConfig, --optimizer), with the conventions of
+ * uh_rmsprop_step: coef = min(1, max_norm/(norm+1e-6)) from the device norm, g *= coef written back, nothing written when the
+ * norm is not finite, 16-byte aligned buffers.  The _ema forms add the moving average of uh_rmsprop_step_ema and write the same
+ * bits to p, g and the state as the plain forms.
+ * uh_adamw_step: torch.optim.AdamW(amsgrad=False): m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g^2;
+ * p = (p - lr*wd*p) - (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps), bc_i = 1 - b_i^t, t = steps[0] + 1.  steps is a DEVICE int32[1],
+ * the number of updates applied so far (the step may be replayed from a captured graph); lr/bc1 and 1/sqrt(bc2) are formed in
+ * double from the float32 betas and t and rounded to float32 once.  uh_ema_tick(steps, norm) advances it, once per optimizer
+ * step, behind the step's launches.  lr, eps, weight_decay >= 0, betas in [0, 1).
+ * uh_sgd_step: torch.optim.SGD(dampening=0): g += wd*p; buf = mu*buf + g; p -= lr * (nesterov ? g + mu*buf : buf).  A zero
+ * buffer gives torch's first step.  lr, weight_decay, momentum >= 0; nesterov is 0 or 1 and needs momentum > 0. */
+int uh_adamw_step(float* p, float* g, float* exp_avg, float* exp_avg_sq, int64_t n, const float* total_norm,
+                  float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+                  const int32_t* steps, uh_stream stream);
+int uh_adamw_step_ema(float* p, float* g, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                      const float* total_norm, float max_norm, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, const int32_t* steps, float decay, int warmup, const int32_t* updates,
+                      uh_stream stream);
+int uh_sgd_step(float* p, float* g, float* momentum_buf, int64_t n, const float* total_norm, float max_norm, float lr,
+                float weight_decay, float momentum, int nesterov, uh_stream stream);
+int uh_sgd_step_ema(float* p, float* g, float* momentum_buf, float* ema, int64_t n, const float* total_norm,
+                    float max_norm, float lr, float weight_decay, float momentum, int nesterov, float decay, int warmup,
+                    const int32_t* updates, uh_stream stream);
 
 /* ---- scalar assembly ------------------------------------------------------------------------
  * dice_coeff from per-group sums {sum x*t, sum x, sum t} (dice_score.py:14-25): out[0] = mean over

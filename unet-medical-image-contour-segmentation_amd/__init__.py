@@ -9,6 +9,7 @@ from .utils.surface_loss import surface_loss, surface_distance_map  # noqa: F401
 from .utils.focal_loss import LossConfig, focal_tversky_loss  # noqa: F401
 from .utils.distill import DistillConfig, Distiller, distill_loss  # noqa: F401
 from .train import FusedRMSprop, seg_loss, train_step, TrainStepper, GraphedTrainStepper, EmaConfig  # noqa: F401
+from .train import OptimConfig, FusedOptimizer, FusedAdamW, FusedSGD  # noqa: F401
 from .evaluate import evaluate  # noqa: F401
 from .utils.contour_metrics import contour_metrics, ContourMetrics  # noqa: F401
 from .predict import predict_img, mask_to_image, preprocess_image, BatchPredictor, plan_batches  # noqa: F401

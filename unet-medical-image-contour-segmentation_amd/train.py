@@ -5,6 +5,8 @@
     FusedRMSprop      clip_grad_norm_(1.0) + RMSprop(lr, weight_decay=1e-8, momentum=0.999) of
                       train.py:80-81,157-158 as two passes over one flat fp32 buffer; optionally an exponential moving
                       average of the parameters in the same pass (EmaConfig), and state_dict / load_state_dict
+    FusedAdamW, FusedSGD   the same pass (FusedOptimizer) under torch.optim.AdamW's and torch.optim.SGD's (Nesterov) rule,
+                      chosen with OptimConfig / TrainStepper(optimizer=...) / --optimizer
     train_step(...)   zero_grad -> forward (autocast) -> loss -> NaN check -> backward -> clip -> step
     TrainStepper      model + optimizer (+ data-parallel sync) bundle used by bench.py
     train_model(...)  the epoch loop of train.py:29-220 on a user-supplied iterable of batches
@@ -117,7 +119,7 @@ def seg_loss(masks_pred: torch.Tensor, true_masks: torch.Tensor, n_classes: int,
 # ----------------------------------------------------------------------------------- optimizer
 @dataclasses.dataclass(frozen=True)
 class EmaConfig:
-    """The exponential moving average of the parameters kept by FusedRMSprop: e <- e + (1 - d_t) (p - e) after every
+    """The exponential moving average of the parameters kept by the fused optimizer: e <- e + (1 - d_t) (p - e) after every
     update, d_t = min(decay, (1 + t) / (warmup + t)) at the t-th update (0-based) when warmup > 0, else decay.  The
     average starts as a copy of the parameters, so it needs no bias correction; the warm-up lets it follow the fast first
     updates instead of holding on to the initialisation for 1 / (1 - decay) steps."""
@@ -164,8 +166,126 @@ class EmaConfig:
         raise TypeError(f"ema is an EmaConfig or a spec string, not {type(ema).__name__}")
 
 
-class FusedRMSprop:
-    """clip_grad_norm_ + torch.optim.RMSprop(momentum > 0, centered=False) over ONE flat buffer.
+_OPTIM_RULES = {      # rule -> its keys and their defaults (adamw: torch's, sgd: nnU-Net's, rmsprop: the reference's train.py)
+    "adamw": dict(betas=(0.9, 0.999), eps=1e-8, wd=0.01),
+    "sgd": dict(momentum=0.99, nesterov=True, wd=3e-5),
+    "rmsprop": dict(alpha=0.99, eps=1e-8, momentum=0.999, wd=1e-8),
+}
+
+
+@dataclasses.dataclass(frozen=True)
+class OptimConfig:
+    """The update rule of the fused optimizer pass and its hyper-parameters (TrainStepper(optimizer=...), --optimizer):
+        adamw[,betas=B1/B2][,eps=E][,wd=W]                      torch.optim.AdamW, defaults 0.9/0.999, 1e-8, 0.01
+        sgd[,momentum=M][,nesterov|plain][,wd=W]                torch.optim.SGD(dampening=0), defaults 0.99, nesterov, 3e-5
+        rmsprop[,alpha=A][,eps=E][,momentum=M][,wd=W]           torch.optim.RMSprop, defaults 0.99, 1e-8, 0.999, 1e-8
+    A field that does not belong to the rule is None.  The learning rate is not part of it: it stays the stepper's `lr`, a
+    kernel argument read from param_groups[0]["lr"] at every step."""
+    rule: str = "rmsprop"
+    betas: Optional[tuple] = None
+    eps: Optional[float] = None
+    wd: Optional[float] = None
+    momentum: Optional[float] = None
+    alpha: Optional[float] = None
+    nesterov: Optional[bool] = None
+
+    def __post_init__(self):
+        if self.rule not in _OPTIM_RULES:
+            raise ValueError(f"OptimConfig: the rule is one of {', '.join(_OPTIM_RULES)}, not {self.rule!r}")
+        own = _OPTIM_RULES[self.rule]
+        for k in ("betas", "eps", "wd", "momentum", "alpha", "nesterov"):
+            v = getattr(self, k)
+            if k not in own:
+                if v is not None:
+                    raise ValueError(f"OptimConfig: {k} does not belong to {self.rule}")
+                continue
+            object.__setattr__(self, k, self._checked(k, own[k] if v is None else v))
+        if self.nesterov and self.momentum == 0.0:
+            raise ValueError("OptimConfig: nesterov needs momentum > 0 (momentum=0 is plain SGD)")
+
+    @staticmethod
+    def _checked(k: str, v):
+        """The value of key k in its canonical type; ValueError says what it should have been."""
+        if k == "betas":
+            try:
+                b = (float(v[0]), float(v[1])) if len(v) == 2 else None
+            except (TypeError, ValueError):
+                b = None
+            if b is None or not all(0.0 <= x < 1.0 for x in b):
+                raise ValueError(f"OptimConfig: betas are two numbers in [0, 1), not {v!r}")
+            return b
+        if k == "nesterov":
+            return bool(v)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= float(v) < math.inf) or (k == "alpha" and v > 1.0):
+            raise ValueError(f"OptimConfig: {k} is a number " + ("in [0, 1]" if k == "alpha" else ">= 0") + f", not {v!r}")
+        return float(v)
+
+    @classmethod
+    def parse(cls, spec: str) -> "OptimConfig":
+        """'RULE[,key=value ...]' -> config, e.g. 'adamw,betas=0.9/0.99,wd=0.05' or 'sgd,momentum=0.9,plain'; ValueError names
+        the token that is wrong."""
+        parts = [t.strip() for t in str(spec).split(",")]
+        rule = parts[0]
+        if rule not in _OPTIM_RULES:
+            raise ValueError(f"OptimConfig.parse: the rule {rule!r} in {spec!r} is none of {', '.join(_OPTIM_RULES)}")
+        own, vals, toks = _OPTIM_RULES[rule], {}, {}
+        for tok in parts[1:]:
+            name, eq, val = (t.strip() for t in tok.partition("="))
+            if name in ("nesterov", "plain") and not eq:
+                name, val = "nesterov", name == "nesterov"
+            elif not eq or not val:
+                raise ValueError(f"OptimConfig.parse: {tok!r} is not key=value in {spec!r}")
+            if name not in own:
+                raise ValueError(f"OptimConfig.parse: {tok!r} does not belong to {rule} (its keys: {', '.join(own)}) in {spec!r}")
+            if name in vals:
+                raise ValueError(f"OptimConfig.parse: {tok!r} gives {name} a second time in {spec!r}")
+            try:
+                if name == "betas":
+                    b1, slash, b2 = val.partition("/")
+                    if not slash:
+                        raise ValueError
+                    val = (float(b1), float(b2))
+                elif name != "nesterov":
+                    val = float(val)
+            except ValueError:
+                raise ValueError(f"OptimConfig.parse: {tok!r} is not " + ("betas=B1/B2" if name == "betas" else f"{name}=NUMBER")
+                                 + f" in {spec!r}") from None
+            try:
+                vals[name] = cls._checked(name, val)
+            except ValueError as e:
+                raise ValueError(f"OptimConfig.parse: {tok!r} in {spec!r}: {e}") from None
+            toks[name] = tok
+        if vals.get("nesterov", own.get("nesterov")) and vals.get("momentum") == 0.0:
+            raise ValueError(f"OptimConfig.parse: {toks['momentum']!r} in {spec!r}: nesterov needs momentum > 0 "
+                             "(say 'plain' for SGD without momentum)")
+        return cls(rule=rule, **vals)
+
+    def spec(self) -> str:
+        """The canonical spec, every key of the rule spelled out: OptimConfig.parse(cfg.spec()) == cfg."""
+        out = [self.rule]
+        for k in sorted(_OPTIM_RULES[self.rule]):
+            v = getattr(self, k)
+            if k == "betas":
+                out.append(f"betas={v[0]!r}/{v[1]!r}")
+            elif k == "nesterov":
+                out.append("nesterov" if v else "plain")
+            else:
+                out.append(f"{k}={v!r}")
+        return ",".join(out)
+
+    @classmethod
+    def of(cls, optimizer: Union[None, str, "OptimConfig"]) -> Optional["OptimConfig"]:
+        """None, a spec string or a config -> None or a config."""
+        if optimizer is None or isinstance(optimizer, cls):
+            return optimizer
+        if isinstance(optimizer, str):
+            return cls.parse(optimizer)
+        raise TypeError(f"optimizer is an OptimConfig or a spec string, not {type(optimizer).__name__}")
+
+
+class FusedOptimizer:
+    """clip_grad_norm_ + one update rule over ONE flat buffer: everything of the fused pass that is not the rule.  The rules
+    are the subclasses FusedRMSprop, FusedAdamW and FusedSGD; each owns its state buffers and launches its own kernel.
 
     Every parameter is re-pointed at a view of `flat_p` (values preserved, strides preserved, so
     channels_last weights stay channels_last); gradients are gathered into `flat_g` by
@@ -174,23 +294,26 @@ class FusedRMSprop:
 
     ema_decay (default None: off -- nothing is allocated and the launches are what they are without the option): keep an
     exponential moving average of the parameters in `flat_ema`, laid out like `flat_p` and initialised to a copy of it,
-    updated inside the same pass (uh_rmsprop_step_ema) with the decay of EmaConfig(ema_decay, ema_warmup) at update number
-    `ema_updates` (a device int32[1], advanced once per applied step by uh_ema_tick: a step skipped for a non-finite
+    updated inside the same pass (the rule's _ema entry point) with the decay of EmaConfig(ema_decay, ema_warmup) at update
+    number `ema_updates` (a device int32[1], advanced once per applied step by uh_ema_tick: a step skipped for a non-finite
     gradient norm does not count).  A parameter skipped as stale (no gradient this step) keeps its average untouched, like
     the rest of its state.  Data parallel: the average is a function of parameters that are identical on every rank, so
     every rank keeps the same one without communication.  swap_ema() exchanges the parameters and their average in place."""
 
-    def __init__(self, params: Iterable[nn.Parameter], lr: float = 1e-5, alpha: float = 0.99, eps: float = 1e-8,
-                 weight_decay: float = 1e-8, momentum: float = 0.999, gradient_clipping: float = 1.0,
+    KIND = None                  # the "kind" of state_dict()
+    HYPER = ()                   # the keys of param_groups[0] beside "lr"
+
+    def __init__(self, params: Iterable[nn.Parameter], defaults: Dict, gradient_clipping: float = 1.0,
                  process_group=None, bucket_bytes: int = 8 << 20, ema_decay: Optional[float] = None, ema_warmup: int = EmaConfig.warmup):
+        name = type(self).__name__
         plist = [p for p in params if p.requires_grad]
         if not plist:
-            raise ValueError("FusedRMSprop got no parameters")
+            raise ValueError(f"{name} got no parameters")
         dev = plist[0].device
         if dev.type != "cuda":
-            raise RuntimeError("FusedRMSprop needs parameters on the GPU (no CPU fallback)")
+            raise RuntimeError(f"{name} needs parameters on the GPU (no CPU fallback)")
         self.params = list(reversed(plist))          # backward produces gradients roughly in this order
-        self.defaults = dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, momentum=momentum)
+        self.defaults = dict(defaults)
         self.param_groups = [dict(self.defaults, params=self.params)]
         self.gradient_clipping = float(gradient_clipping) if gradient_clipping else 0.0
         slices, off = [], 0
@@ -202,8 +325,7 @@ class FusedRMSprop:
         self.slices = slices
         self.flat_p = torch.zeros(off, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_sq = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_buf = torch.zeros(off, dtype=torch.float32, device=dev)
+        self._alloc_state(off, dev)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.ws = torch.empty(LIB.query("uh_optim_ws_bytes", off), dtype=torch.uint8, device=dev)
         self._index = {}
@@ -217,10 +339,10 @@ class FusedRMSprop:
         with torch.no_grad():
             for i, (p, (o, n)) in enumerate(zip(self.params, slices)):
                 if p.dtype != torch.float32:
-                    raise RuntimeError("FusedRMSprop expects fp32 master parameters")
+                    raise RuntimeError(f"{name} expects fp32 master parameters")
                 if not _is_dense(p):
                     raise RuntimeError("parameters must be dense (contiguous or channels_last)")
-                # a parameter belongs to ONE FusedRMSprop: a stale owner's hook would steal the gradient (it fires first,
+                # a parameter belongs to ONE FusedOptimizer: a stale owner's hook would steal the gradient (it fires first,
                 # copies p.grad into its dead buffer and clears it), so an earlier owner is closed here (take-over)
                 prev = getattr(p, "_uh_owner", None)
                 prev = prev() if prev is not None else None
@@ -274,7 +396,7 @@ class FusedRMSprop:
 
     def _mark(self, i: int, event=None):
         if self._fresh[i]:
-            raise RuntimeError("FusedRMSprop: a second gradient for the same parameter arrived before step(): the backward "
+            raise RuntimeError(f"{type(self).__name__}: a second gradient for the same parameter arrived before step(): the backward "
                                "kernels overwrite the flat gradient buffer, so gradient accumulation over several "
                                "backward() calls is not supported (call zero_grad() + step() once per backward)")
         self._fresh[i] = True
@@ -346,7 +468,7 @@ class FusedRMSprop:
                 # (every rank takes this branch: the buckets are drained and the step is abandoned before anyone raises)
                 self.sync.wait()
                 self._fresh = [False] * len(self.params)
-                raise RuntimeError("FusedRMSprop (data parallel): a parameter received a gradient on some ranks and none on "
+                raise RuntimeError(f"{type(self).__name__} (data parallel): a parameter received a gradient on some ranks and none on "
                                    "others; the replicas would diverge (give every rank the same set of trainable / used "
                                    "parameters)")
         self._stale_verified = pattern
@@ -355,14 +477,14 @@ class FusedRMSprop:
         """Host side of pattern_probe: s1 = sum of the ranks' codes, s2 = sum of their squares (read with the NaN flag)."""
         if abs(s2 * world - s1 * s1) > 0.5:
             self.abort_step()
-            raise RuntimeError("FusedRMSprop (data parallel): in the previous step the set of parameters that received gradients "
+            raise RuntimeError(f"{type(self).__name__} (data parallel): in the previous step the set of parameters that received gradients "
                                "differed between the ranks; the replicas have diverged by one update (give every rank the same "
                                "set of trainable / used parameters)")
 
     @torch.no_grad()
     def step(self):
         if self._closed:
-            raise RuntimeError("FusedRMSprop.step() after close() (another FusedRMSprop took the parameters over)")
+            raise RuntimeError(f"{type(self).__name__}.step() after close() (another {type(self).__name__} took the parameters over)")
         ops.flush_slabs()
         if ops.STEP.wgrad_stream is not None:
             torch.cuda.current_stream().wait_stream(ops.STEP.wgrad_stream)     # weight gradients written on the side stream
@@ -372,7 +494,7 @@ class FusedRMSprop:
         # meets a matching all-reduce -- and the update runs over the contiguous runs of fresh slices only.
         stale = [i for i, f in enumerate(self._fresh) if not f]
         if stale and len(stale) == len(self._fresh):
-            raise RuntimeError("FusedRMSprop.step() without a backward pass since the last step / zero_grad")
+            raise RuntimeError(f"{type(self).__name__}.step() without a backward pass since the last step / zero_grad")
         runs = [(0, self.total)]
         if stale:
             for i in stale:
@@ -403,22 +525,43 @@ class FusedRMSprop:
         st = torch.cuda.current_stream().cuda_stream
         LIB.call("uh_grad_sumsq", self.flat_g.data_ptr(), self.total, self.norm.data_ptr(), self.ws.data_ptr(),
                  self.ws.numel(), st)
-        if self.ema is None:
-            for o, n in runs:
-                LIB.call("uh_rmsprop_step", self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(), self.flat_sq[o:].data_ptr(),
-                         self.flat_buf[o:].data_ptr(), n, self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]),
-                         float(g["alpha"]), float(g["eps"]), float(g["weight_decay"]), float(g["momentum"]), st)
-        else:
-            for o, n in runs:
-                LIB.call("uh_rmsprop_step_ema", self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(),
-                         self.flat_sq[o:].data_ptr(), self.flat_buf[o:].data_ptr(), self.flat_ema[o:].data_ptr(), n,
-                         self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]), float(g["alpha"]), float(g["eps"]),
-                         float(g["weight_decay"]), float(g["momentum"]), float(self.ema.decay), int(self.ema.warmup),
-                         self.ema_updates.data_ptr(), st)
-            # behind every run's launch: all of them read the same update number
-            LIB.call("uh_ema_tick", self.ema_updates.data_ptr(), self.norm.data_ptr(), st)
+        for o, n in runs:
+            self._launch(o, n, g, st)
+        # behind every run's launch: all of them read the same step and update numbers
+        for counter in self.counters():
+            LIB.call("uh_ema_tick", counter.data_ptr(), self.norm.data_ptr(), st)
         ops.WEIGHT_EPOCH += 1        # parameters changed behind torch's version counters (see ops.packed_w3x3_cached)
         return self.norm
+
+    # ---- what a rule provides
+    def _alloc_state(self, total: int, dev):
+        """Allocate the rule's zeroed state buffers (and its step counter, if it has one)."""
+        raise NotImplementedError
+
+    def _launch(self, o: int, n: int, g: Dict, st: int):
+        """Enqueue the rule's kernel (its _ema form when self.ema is set) over the n floats at offset o of the flat buffers."""
+        raise NotImplementedError
+
+    def _rule_state(self) -> Dict[str, torch.Tensor]:
+        """state_dict key -> the rule's flat state buffer, in the order of the kernel's arguments."""
+        raise NotImplementedError
+
+    step_count = None            # a device int32[1] of applied steps where the rule needs one (FusedAdamW)
+
+    def counters(self):
+        """The device int32[1] counters uh_ema_tick advances once per applied step."""
+        return [c for c in (self.step_count, self.ema_updates) if c is not None]
+
+    def state_tensors(self):
+        """Every device tensor a step changes beside the gradient: the parameters, the rule's buffers, the moving average and
+        the counters.  What a snapshot has to cover (GraphedTrainStepper's capture warm-up)."""
+        out = [self.flat_p] + list(self._rule_state().values())
+        if self.ema is not None:
+            out.append(self.flat_ema)
+        return out + self.counters()
+
+    def _ema_args(self):
+        return float(self.ema.decay), int(self.ema.warmup), self.ema_updates.data_ptr()
 
     @torch.no_grad()
     def swap_ema(self):
@@ -427,7 +570,7 @@ class FusedRMSprop:
         folded BatchNorm caches are keyed on ops.WEIGHT_EPOCH (ops.packed_w3x3_cached, ops.bn_eval_coeffs_cached,
         ops.ConvWeightPack), which is bumped."""
         if self.ema is None:
-            raise RuntimeError("FusedRMSprop.swap_ema() without ema_decay")
+            raise RuntimeError(f"{type(self).__name__}.swap_ema() without ema_decay")
         LIB.call("uh_swap_f32", self.flat_p.data_ptr(), self.flat_ema.data_ptr(), self.total,
                  torch.cuda.current_stream().cuda_stream)
         ops.WEIGHT_EPOCH += 1
@@ -437,42 +580,56 @@ class FusedRMSprop:
 
     def state_dict(self) -> Dict:
         """The state a resumed run needs beside the parameters themselves (they travel in the model's state_dict): clones of
-        the two RMSprop buffers, the moving average and its update count (None / 0 without one), the slice layout they are
-        laid out by, and the hyper-parameters (the current lr among them)."""
+        the rule's buffers (RMSprop: square_avg, momentum_buffer; AdamW: exp_avg, exp_avg_sq and the step count; SGD:
+        momentum_buffer), the moving average and its update count (None / 0 without one), the slice layout they are laid out
+        by, and the hyper-parameters (the current lr among them).  AdamW and SGD states also say their "kind"; an RMSprop
+        state has no such key."""
         g = self.param_groups[0]
-        hyper = {k: float(g[k]) for k in ("lr", "alpha", "eps", "weight_decay", "momentum")}
+        hyper = {k: (g[k] if isinstance(g[k], bool) else float(g[k])) for k in ("lr",) + self.HYPER}
         hyper["gradient_clipping"] = self.gradient_clipping
         hyper["ema_decay"] = float(self.ema.decay) if self.ema is not None else None
         hyper["ema_warmup"] = int(self.ema.warmup) if self.ema is not None else None
-        return {"square_avg": self.flat_sq.detach().clone(), "momentum_buffer": self.flat_buf.detach().clone(),
-                "ema": self.flat_ema.detach().clone() if self.ema is not None else None,
-                "ema_updates": int(self.ema_updates.item()) if self.ema is not None else 0,
-                "layout": self._layout(), "total": int(self.total), "hyper": hyper}
+        out = {} if self.KIND == "rmsprop" else {"kind": self.KIND}
+        out.update((k, v.detach().clone()) for k, v in self._rule_state().items())
+        if self.step_count is not None:
+            out["step"] = int(self.step_count.item())
+        out.update({"ema": self.flat_ema.detach().clone() if self.ema is not None else None,
+                    "ema_updates": int(self.ema_updates.item()) if self.ema is not None else 0,
+                    "layout": self._layout(), "total": int(self.total), "hyper": hyper})
+        return out
 
     @torch.no_grad()
     def load_state_dict(self, state: Dict):
         """Restore what state_dict() returned.  ValueError when the slice layout differs (another model, another parameter
         order), when the state and this optimizer disagree about keeping a moving average, or when they keep it with another
-        decay or warm-up (the average is part of the run: it is not continued under other settings silently)."""
+        decay or warm-up (the average is part of the run: it is not continued under other settings silently), or when the
+        state was written by another rule (a state without "kind" is RMSprop's)."""
+        name = type(self).__name__
+        kind = state.get("kind", "rmsprop")
+        if kind != self.KIND:
+            raise ValueError(f"{name}.load_state_dict: the state is an optimizer state of kind {kind!r}, this optimizer's is "
+                             f"{self.KIND!r}")
         layout = [[int(o), int(n), [int(d) for d in shape]] for o, n, shape in state["layout"]]
         if layout != self._layout() or int(state["total"]) != self.total:
-            raise ValueError("FusedRMSprop.load_state_dict: the state's slice layout is not this optimizer's "
+            raise ValueError(f"{name}.load_state_dict: the state's slice layout is not this optimizer's "
                              f"({len(layout)} slices over {int(state['total'])} floats against {len(self.slices)} over {self.total})")
         if (state.get("ema") is not None) != (self.ema is not None):
-            raise ValueError("FusedRMSprop.load_state_dict: the state " + ("has" if state.get("ema") is not None else "lacks")
+            raise ValueError(f"{name}.load_state_dict: the state " + ("has" if state.get("ema") is not None else "lacks")
                              + " a moving average and this optimizer " + ("keeps one" if self.ema is not None else "keeps none"))
         hyper = dict(state["hyper"])
         if self.ema is not None:
             saved = EmaConfig(float(hyper["ema_decay"]), int(hyper["ema_warmup"]))
             if saved != self.ema:
-                raise ValueError(f"FusedRMSprop.load_state_dict: the state's moving average was kept with {saved.spec()!r}, "
+                raise ValueError(f"{name}.load_state_dict: the state's moving average was kept with {saved.spec()!r}, "
                                  f"this optimizer keeps one with {self.ema.spec()!r}")
             self.flat_ema.copy_(state["ema"])
             self.ema_updates.fill_(int(state["ema_updates"]))
-        self.flat_sq.copy_(state["square_avg"])
-        self.flat_buf.copy_(state["momentum_buffer"])
-        for k in ("lr", "alpha", "eps", "weight_decay", "momentum"):
-            self.param_groups[0][k] = float(hyper[k])
+        for k, buf in self._rule_state().items():
+            buf.copy_(state[k])
+        if self.step_count is not None:
+            self.step_count.fill_(int(state["step"]))
+        for k in ("lr",) + self.HYPER:
+            self.param_groups[0][k] = hyper[k] if isinstance(hyper[k], bool) else float(hyper[k])
         self.gradient_clipping = float(hyper["gradient_clipping"])
         ops.WEIGHT_EPOCH += 1
 
@@ -482,7 +639,122 @@ class FusedRMSprop:
         return torch.as_strided(self.flat_g, p.shape, p.stride(), o)
 
 
-def _weak_grad_hook(opt: "FusedRMSprop"):
+class FusedRMSprop(FusedOptimizer):
+    """clip_grad_norm_ + torch.optim.RMSprop(momentum > 0, centered=False) over ONE flat buffer (FusedOptimizer): the
+    reference's optimizer and the default.  State: `flat_sq` (square_avg) and `flat_buf` (momentum_buffer);
+    uh_rmsprop_step / uh_rmsprop_step_ema."""
+
+    KIND = "rmsprop"
+    HYPER = ("alpha", "eps", "weight_decay", "momentum")
+
+    def __init__(self, params: Iterable[nn.Parameter], lr: float = 1e-5, alpha: float = 0.99, eps: float = 1e-8,
+                 weight_decay: float = 1e-8, momentum: float = 0.999, gradient_clipping: float = 1.0,
+                 process_group=None, bucket_bytes: int = 8 << 20, ema_decay: Optional[float] = None, ema_warmup: int = EmaConfig.warmup):
+        super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, momentum=momentum),
+                         gradient_clipping, process_group, bucket_bytes, ema_decay, ema_warmup)
+
+    def _alloc_state(self, total, dev):
+        self.flat_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.flat_buf = torch.zeros(total, dtype=torch.float32, device=dev)
+
+    def _rule_state(self):
+        return {"square_avg": self.flat_sq, "momentum_buffer": self.flat_buf}
+
+    def _launch(self, o, n, g, st):
+        if self.ema is None:
+            LIB.call("uh_rmsprop_step", self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(), self.flat_sq[o:].data_ptr(),
+                     self.flat_buf[o:].data_ptr(), n, self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]),
+                     float(g["alpha"]), float(g["eps"]), float(g["weight_decay"]), float(g["momentum"]), st)
+        else:
+            LIB.call("uh_rmsprop_step_ema", self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(),
+                     self.flat_sq[o:].data_ptr(), self.flat_buf[o:].data_ptr(), self.flat_ema[o:].data_ptr(), n,
+                     self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]), float(g["alpha"]), float(g["eps"]),
+                     float(g["weight_decay"]), float(g["momentum"]), *self._ema_args(), st)
+
+
+class FusedAdamW(FusedOptimizer):
+    """clip_grad_norm_ + torch.optim.AdamW(amsgrad=False, maximize=False) over ONE flat buffer (FusedOptimizer).  State:
+    `flat_m` (exp_avg), `flat_v` (exp_avg_sq) and `step_count`, a device int32[1] of the steps applied so far: the kernel
+    reads it for the bias corrections 1 - beta^t, t = step_count + 1 (uh_adamw_step / uh_adamw_step_ema), and uh_ema_tick
+    advances it once per applied step -- on the device, so that a step replayed from a captured graph uses its own t.  A step
+    skipped for a non-finite gradient norm does not count.
+
+    The counter is ONE per optimizer, where torch keeps one per parameter: a parameter skipped as stale (no gradient this
+    step) keeps exp_avg, exp_avg_sq and its value untouched, as in torch, but when it gets a gradient again its bias
+    corrections use the optimizer's t, not the number of updates it has itself received.  The U-Nets use every parameter on
+    every step, so for them the two agree."""
+
+    KIND = "adamw"
+    HYPER = ("beta1", "beta2", "eps", "weight_decay")
+
+    def __init__(self, params: Iterable[nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.01, gradient_clipping: float = 1.0, process_group=None, bucket_bytes: int = 8 << 20,
+                 ema_decay: Optional[float] = None, ema_warmup: int = EmaConfig.warmup):
+        cfg = OptimConfig("adamw", betas=betas, eps=eps, wd=weight_decay)           # (the range checks)
+        super().__init__(params, dict(lr=lr, beta1=cfg.betas[0], beta2=cfg.betas[1], eps=cfg.eps, weight_decay=cfg.wd),
+                         gradient_clipping, process_group, bucket_bytes, ema_decay, ema_warmup)
+
+    def _alloc_state(self, total, dev):
+        self.flat_m = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _rule_state(self):
+        return {"exp_avg": self.flat_m, "exp_avg_sq": self.flat_v}
+
+    def _launch(self, o, n, g, st):
+        args = (self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(), self.flat_m[o:].data_ptr(), self.flat_v[o:].data_ptr())
+        hyper = (self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]), float(g["beta1"]), float(g["beta2"]),
+                 float(g["eps"]), float(g["weight_decay"]), self.step_count.data_ptr())
+        if self.ema is None:
+            LIB.call("uh_adamw_step", *args, n, *hyper, st)
+        else:
+            LIB.call("uh_adamw_step_ema", *args, self.flat_ema[o:].data_ptr(), n, *hyper, *self._ema_args(), st)
+
+
+class FusedSGD(FusedOptimizer):
+    """clip_grad_norm_ + torch.optim.SGD(dampening=0) over ONE flat buffer (FusedOptimizer), Nesterov momentum by default.
+    State: `flat_buf` (momentum_buffer), zero-initialised -- with dampening 0 that gives torch's first step, which is why
+    dampening is not offered; no step counter (uh_sgd_step / uh_sgd_step_ema).  momentum=0 is plain SGD."""
+
+    KIND = "sgd"
+    HYPER = ("momentum", "weight_decay", "nesterov")
+
+    def __init__(self, params: Iterable[nn.Parameter], lr: float = 1e-2, momentum: float = 0.99, nesterov: bool = True,
+                 weight_decay: float = 3e-5, gradient_clipping: float = 1.0, process_group=None, bucket_bytes: int = 8 << 20,
+                 ema_decay: Optional[float] = None, ema_warmup: int = EmaConfig.warmup):
+        cfg = OptimConfig("sgd", momentum=momentum, nesterov=nesterov, wd=weight_decay)          # (the range checks)
+        super().__init__(params, dict(lr=lr, momentum=cfg.momentum, weight_decay=cfg.wd, nesterov=cfg.nesterov),
+                         gradient_clipping, process_group, bucket_bytes, ema_decay, ema_warmup)
+
+    def _alloc_state(self, total, dev):
+        self.flat_buf = torch.zeros(total, dtype=torch.float32, device=dev)
+
+    def _rule_state(self):
+        return {"momentum_buffer": self.flat_buf}
+
+    def _launch(self, o, n, g, st):
+        args = (self.flat_p[o:].data_ptr(), self.flat_g[o:].data_ptr(), self.flat_buf[o:].data_ptr())
+        hyper = (self.norm.data_ptr(), self.gradient_clipping, float(g["lr"]), float(g["weight_decay"]), float(g["momentum"]),
+                 int(bool(g["nesterov"])))
+        if self.ema is None:
+            LIB.call("uh_sgd_step", *args, n, *hyper, st)
+        else:
+            LIB.call("uh_sgd_step_ema", *args, self.flat_ema[o:].data_ptr(), n, *hyper, *self._ema_args(), st)
+
+
+def build_optimizer(config: OptimConfig, params, lr: float, **common) -> FusedOptimizer:
+    """The optimizer of a config (authoritative for the rule's hyper-parameters; lr and `common` -- gradient_clipping,
+    process_group, ema_decay, ema_warmup -- come from the caller)."""
+    if config.rule == "adamw":
+        return FusedAdamW(params, lr=lr, betas=config.betas, eps=config.eps, weight_decay=config.wd, **common)
+    if config.rule == "sgd":
+        return FusedSGD(params, lr=lr, momentum=config.momentum, nesterov=config.nesterov, weight_decay=config.wd, **common)
+    return FusedRMSprop(params, lr=lr, alpha=config.alpha, eps=config.eps, weight_decay=config.wd, momentum=config.momentum,
+                        **common)
+
+
+def _weak_grad_hook(opt: "FusedOptimizer"):
     ref = weakref.ref(opt)
 
     def hook(p):
@@ -492,7 +764,7 @@ def _weak_grad_hook(opt: "FusedRMSprop"):
     return hook
 
 
-def _weak_callback(opt: "FusedRMSprop", i: int):
+def _weak_callback(opt: "FusedOptimizer", i: int):
     ref = weakref.ref(opt)
 
     def cb(event=None):
@@ -538,7 +810,7 @@ def train_step(model: nn.Module, optimizer, images: torch.Tensor, true_masks: to
                gradient_clipping: float = 1.0, reduce_sums=None, world: int = 1, check_nan: bool = True,
                boundary_weight: Optional[float] = None, cc_loss: bool = False, surface_weight: float = 0.0,
                surface_classes=None, loss=None, distill=None) -> Dict[str, torch.Tensor]:
-    """Statement sequence of train.py:113-159.  `optimizer` is a FusedRMSprop (clipping fused into
+    """Statement sequence of train.py:113-159.  `optimizer` is a FusedOptimizer (clipping fused into
     its step) or any torch.optim optimizer (then clip_grad_norm_ is applied as in the reference).
     surface_weight / surface_classes: the surface term of seg_loss (0: off, the step is what it is without the option).
     loss: the focal + Tversky configuration of seg_loss (None: off, likewise).
@@ -578,8 +850,8 @@ def train_step(model: nn.Module, optimizer, images: torch.Tensor, true_masks: to
         if reduce_sums is not None:
             # data parallel: boundary_loss (and so the loss value) is per rank; every rank must take the SAME decision, or
             # the ranks that continue hang at their next collective while one has raised.  The same all-reduce carries the
-            # checksum of the previous step's fresh / stale gradient pattern (FusedRMSprop.pattern_probe).
-            probe = optimizer.pattern_probe() if isinstance(optimizer, FusedRMSprop) else None
+            # checksum of the previous step's fresh / stale gradient pattern (FusedOptimizer.pattern_probe).
+            probe = optimizer.pattern_probe() if isinstance(optimizer, FusedOptimizer) else None
             if probe is not None:
                 flag = torch.cat([flag.reshape(1), probe])
             flag = reduce_sums(flag)
@@ -597,10 +869,10 @@ def train_step(model: nn.Module, optimizer, images: torch.Tensor, true_masks: to
         if len(host) == 3:
             optimizer.check_probe(host[1], host[2], optimizer.sync.world)     # (`world` may be a ragged shard's gb / lb: the group's size counts)
         if host[0] > 0:
-            if isinstance(optimizer, FusedRMSprop):
+            if isinstance(optimizer, FusedOptimizer):
                 optimizer.abort_step()
             raise RuntimeError("Fatal: NaN loss detected!")                                   # train.py:149-151
-    if isinstance(optimizer, FusedRMSprop):
+    if isinstance(optimizer, FusedOptimizer):
         terms["grad_norm"] = optimizer.step()
     else:
         terms["grad_norm"] = torch.nn.utils.clip_grad_norm_(model.parameters(), gradient_clipping)
@@ -610,14 +882,19 @@ def train_step(model: nn.Module, optimizer, images: torch.Tensor, true_masks: to
 
 
 class TrainStepper:
-    """Model + FusedRMSprop (+ RCCL gradient sync when torch.distributed is initialised)."""
+    """Model + fused optimizer (FusedRMSprop unless `optimizer` names another rule) (+ RCCL gradient sync when
+    torch.distributed is initialised)."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-5, weight_decay: float = 1e-8, momentum: float = 0.999,
                  gradient_clipping: float = 1.0, amp: bool = True, process_group=None, check_nan: bool = True,
                  wgrad_stream: Optional[bool] = None, cc_loss: bool = False, sync_bn: bool = False, fp32_mode: str = "exact",
                  surface_weight: float = 0.0, surface_classes=None, ema: Union[None, str, EmaConfig] = None, loss=None,
-                 distill=None):
+                 distill=None, optimizer: Union[None, str, OptimConfig] = None):
         self.model = model
+        # optimizer: an OptimConfig or a spec string ("adamw", "sgd,momentum=0.9", ...): the update rule of the fused pass and
+        # its hyper-parameters, for which the config is authoritative (`weight_decay` and `momentum` above are RMSprop's and are
+        # not read then); `lr` and `gradient_clipping` stay this constructor's.  None (default): FusedRMSprop as ever.
+        self.optim_config = OptimConfig.of(optimizer)
         # distill: a utils.distill.Distiller, DistillConfig or spec string: every step adds w * kd against the frozen teacher's
         # logits for the step's images.  The teacher is an object beside the model: it is in no optimizer, flat buffer, moving
         # average, state_dict or checkpoint, and no collective touches it (every rank holds its own copy).  A config or spec
@@ -640,7 +917,7 @@ class TrainStepper:
             self.loss = LossConfig.of(loss)
             self.loss.for_head(model.n_classes)
         # ema: an EmaConfig or a spec string ("0.999,warmup=10"): the optimizer keeps a moving average of the parameters
-        # (FusedRMSprop), averaged() computes with it.  None (default): nothing is allocated or launched for it.
+        # (FusedOptimizer), averaged() computes with it.  None (default): nothing is allocated or launched for it.
         self.ema = EmaConfig.of(ema)
         self._averaged = False
         # the surface term of seg_loss; a plain attribute: the epoch loop may change the weight between steps (0 = off)
@@ -694,9 +971,12 @@ class TrainStepper:
                 ranks = dist.get_process_group_ranks(process_group) if process_group is not None else list(range(dist.get_world_size()))
                 self.bn_group = group = dist.new_group(ranks=ranks)
             self.sync_bn = (group, self.world)
-        self.optimizer = FusedRMSprop(model.parameters(), lr=lr, weight_decay=weight_decay, momentum=momentum,
-                                      gradient_clipping=gradient_clipping, process_group=process_group,
-                                      **({} if self.ema is None else {"ema_decay": self.ema.decay, "ema_warmup": self.ema.warmup}))
+        common = dict(gradient_clipping=gradient_clipping, process_group=process_group,
+                      **({} if self.ema is None else {"ema_decay": self.ema.decay, "ema_warmup": self.ema.warmup}))
+        if self.optim_config is None:
+            self.optimizer = FusedRMSprop(model.parameters(), lr=lr, weight_decay=weight_decay, momentum=momentum, **common)
+        else:
+            self.optimizer = build_optimizer(self.optim_config, model.parameters(), lr, **common)
         self._pack = None
         # the closing reductions of backward-weights wait for one batched launch behind the backward pass; data parallel: for
         # one launch per gradient bucket, so that the bucket's all-reduce still starts under the rest of the backward pass
@@ -726,7 +1006,7 @@ class TrainStepper:
     @contextlib.contextmanager
     def averaged(self):
         """`with stepper.averaged(): evaluate(model, ...)` -- inside the block the model's parameters ARE the moving average
-        (swapped in place, FusedRMSprop.swap_ema), on leaving it the live ones are back bit for bit, also after an exception.
+        (swapped in place, FusedOptimizer.swap_ema), on leaving it the live ones are back bit for bit, also after an exception.
         BatchNorm running statistics are shared with the live model and not averaged: they are already a moving average
         (momentum 0.1) of the statistics of recent batches.  Nesting the block or calling step() inside it raises
         RuntimeError: an update applied to the swapped buffers would train the average."""
@@ -815,12 +1095,13 @@ class TrainStepper:
 
 
 class GraphedTrainStepper(TrainStepper):
-    """TrainStepper whose whole step (forward, loss, backward, clip + RMSprop) is captured once into a HIP graph and
+    """TrainStepper whose whole step (forward, loss, backward, clip + update) is captured once into a HIP graph and
     replayed per batch: for launch-bound models (UNet_S / UNet_T: ~500 small kernels per step) the host no longer paces
     the GPU.  Fixed batch shape; re-captured when the learning rate changes (it is a kernel argument); single process
     only.  A NaN loss is detected after the replay (the fused optimizer kernel has skipped the update: non-finite norm).
     With `ema` the captured graph holds the averaging launches and the update counter's tick; the decay of the warm-up is
-    computed on the device from that counter, so every replay uses its own."""
+    computed on the device from that counter, so every replay uses its own.  Likewise with optimizer="adamw": the step number
+    of the bias corrections is FusedAdamW.step_count on the device, ticked inside the graph."""
 
     def __init__(self, model: nn.Module, *args, warmup: int = 2, **kw):
         kw.setdefault("wgrad_stream", False)         # one stream unless asked for: the graph is for launch-bound small models
@@ -852,8 +1133,7 @@ class GraphedTrainStepper(TrainStepper):
         opt = self.optimizer
         # the warm-up steps the capture protocol needs must not count as training: snapshot, warm up, restore
         snap_model = {k: v.clone() for k, v in self.model.state_dict().items()}
-        snap_opt = (opt.flat_p.clone(), opt.flat_sq.clone(), opt.flat_buf.clone())
-        snap_ema = (opt.flat_ema.clone(), opt.ema_updates.clone()) if opt.ema is not None else None
+        snap_opt = [t.clone() for t in opt.state_tensors()]          # parameters, the rule's state, the average, the counters
         self._im = images.detach().clone(memory_format=torch.preserve_format)
         self._mk = masks.detach().clone()
         side = torch.cuda.Stream()
@@ -864,9 +1144,8 @@ class GraphedTrainStepper(TrainStepper):
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         with torch.no_grad():
-            opt.flat_p.copy_(snap_opt[0]); opt.flat_sq.copy_(snap_opt[1]); opt.flat_buf.copy_(snap_opt[2])
-            if snap_ema is not None:
-                opt.flat_ema.copy_(snap_ema[0]); opt.ema_updates.copy_(snap_ema[1])
+            for t, snap in zip(opt.state_tensors(), snap_opt):
+                t.copy_(snap)
             for k, v in self.model.state_dict().items():
                 if v.data_ptr() < opt.flat_p.data_ptr() or v.data_ptr() >= opt.flat_p.data_ptr() + opt.flat_p.numel() * 4:
                     v.copy_(snap_model[k])                    # buffers (running statistics, num_batches_tracked)

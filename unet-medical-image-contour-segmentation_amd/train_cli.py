@@ -4,7 +4,7 @@
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
                              [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--elastic [SPEC]] [--surface-loss [SPEC]]
                              [--loss [SPEC]] [--ema [DECAY[,warmup=N]]] [--save-state] [--resume STATE]
-                             [--crop [SPEC]] [--tile [SPEC]] [--distill SPEC]
+                             [--crop [SPEC]] [--tile [SPEC]] [--distill SPEC] [--optimizer SPEC]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -55,8 +55,14 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     from --classes ends the command with status 2 before a dataset or a GPU is touched.  One log line per epoch gives the
     mean term and the mean share of pixels on which student and teacher pick the same class.  Validation, checkpoints and
     the saved model hold the student alone; --save-state records the spec and the SHA-256 of the teacher file;
+  - --optimizer SPEC (default: off, the reference's RMSprop) chooses the update rule of the fused optimizer pass
+    (train.OptimConfig, csrc/optim.hip): "adamw[,betas=B1/B2][,eps=E][,wd=W]" (defaults 0.9/0.999, 1e-8, 0.01: torch's),
+    "sgd[,momentum=M][,nesterov|plain][,wd=W]" (defaults 0.99, nesterov, 3e-5: nnU-Net's) or "rmsprop[,alpha=A][,eps=E]
+    [,momentum=M][,wd=W]" (defaults: the reference's values).  The learning rate stays -l and the loop's schedule drives it under
+    every rule; gradient clipping, --ema, --save-state and --resume work as with the default.  A malformed spec ends the
+    command with status 2; one log line names the canonical spec;
   - --save-state writes checkpoint_dir/train_state.pth at the end of every epoch (a temporary file renamed over it): model
-    and optimizer state (both RMSprop buffers, the moving average and its update count), epoch, global step, lr, the
+    and optimizer state (the rule's buffers and step count, the moving average and its update count), epoch, global step, lr, the
     loader's and the augmenter's seeds, and a record of the arguments that determine the run (RECORDED);
   - --resume STATE restores all of that and continues with the epoch after the saved one up to -e: the run is bit for bit
     the run that was never interrupted.  A determining argument that differs from the record ends the command with
@@ -81,7 +87,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
-from .train import EmaConfig
+from .train import EmaConfig, OptimConfig
 from .utils.focal_loss import LOSS_BARE, LossConfig
 
 MODELS = ("UNet_S", "UNet", "UNet_T", "UNet_SA")
@@ -104,7 +110,7 @@ RECORDED = (("model", "--model"), ("classes", "--classes"), ("bilinear", "--bili
             ("scale", "--scale"), ("amp", "--amp / --no-amp"), ("lr", "--learning-rate"), ("augment", "--augment"),
             ("elastic", "--elastic"), ("surface", "--surface-loss"), ("ema", "--ema"), ("loss", "--loss"),
             ("crop", "--crop"), ("tile", "--tile"), ("distill", "--distill"),
-            ("distill_sha256", "--distill (the SHA-256 of the teacher file)"))
+            ("distill_sha256", "--distill (the SHA-256 of the teacher file)"), ("optimizer", "--optimizer"))
 
 
 def parse_surface_spec(text: str) -> SurfaceSpec:
@@ -166,6 +172,13 @@ def _ema_arg(text: str):
         raise argparse.ArgumentTypeError(f"bad --ema {text!r}: {e}") from None
 
 
+def _optimizer_arg(text: str):
+    try:
+        return OptimConfig.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"bad --optimizer {text!r}: {e}") from None
+
+
 def _loss_arg(text: str):
     try:
         return LossConfig.parse(text)
@@ -203,6 +216,7 @@ def run_record(args: argparse.Namespace) -> Dict:
     parse or a teacher file that cannot be read."""
     from .utils.augment import AugmentConfig, ElasticConfig
     distill = getattr(args, "distill", None)
+    optimizer = getattr(args, "optimizer", None)
     if distill is not None:
         from .utils.distill import teacher_sha256
     return {"model": args.model, "classes": int(args.classes), "bilinear": bool(args.bilinear),
@@ -215,7 +229,8 @@ def run_record(args: argparse.Namespace) -> Dict:
             "crop": args.crop.spec() if getattr(args, "crop", None) is not None else None,
             "tile": getattr(args, "tile", None),
             "distill": distill.spec() if distill is not None else None,
-            "distill_sha256": teacher_sha256(distill.teacher) if distill is not None else None}
+            "distill_sha256": teacher_sha256(distill.teacher) if distill is not None else None,
+            "optimizer": optimizer.spec() if optimizer is not None else None}
 
 
 def load_resume_state(args: argparse.Namespace) -> Optional[Dict]:
@@ -295,6 +310,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Knowledge distillation: add W * T^2 * KL(teacher || student) at temperature T against the frozen network of "
                         "architecture NAME (UNet, UNet_S, UNet_T, UNet_SA; default UNet) loaded from the checkpoint PATH "
                         "(defaults: T=2, w=1; default: off)")
+    p.add_argument("--optimizer", default=None, type=_optimizer_arg, metavar="RULE[,key=value ...]",
+                   help="The update rule of the fused optimizer pass: 'adamw[,betas=B1/B2][,eps=E][,wd=W]', "
+                        "'sgd[,momentum=M][,nesterov|plain][,wd=W]' or 'rmsprop[,alpha=A][,eps=E][,momentum=M][,wd=W]'; the learning "
+                        "rate stays -l (default: off, the reference's RMSprop)")
     p.add_argument("--save-state", dest="save_state", action="store_true", default=False,
                    help=f"Write checkpoint_dir/{STATE_FILE} after every epoch: everything --resume needs (default: off)")
     p.add_argument("--resume", default=None, metavar="STATE",
@@ -339,7 +358,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                  train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
                  augment=None, surface: Optional[SurfaceSpec] = None, elastic=None, ema=None, save_state: bool = False,
                  resume: Optional[Dict] = None, record: Optional[Dict] = None, loss=None, crop=None, tile=None,
-                 distill=None) -> List[Dict]:
+                 distill=None, optimizer=None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
@@ -359,6 +378,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     `distill`: a DistillConfig, a spec string or a Distiller; every step adds the distillation term against the frozen teacher, the
     record gains the epoch's mean "kd" and "kd_agree", and one line per epoch logs them.  Evaluations and checkpoints hold the
     student alone.
+    `optimizer`: an OptimConfig or a spec string: the rule of the fused optimizer pass (None: RMSprop as ever); one line logs it.
     `save_state`: write checkpoint_dir/train_state.pth after every epoch, holding `record` (run_record) as its "args".
     `resume`: such a state (load_resume_state); the model must already hold its weights.  Optimizer state, lr, counters
     and the seeds are restored and the loop continues with the epoch after the saved one: only those epochs are returned."""
@@ -393,7 +413,10 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                 + (f"; elastic {augment.elastic.spec()}" if augment.elastic is not None else ""))
     val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
     stepper = TrainStepper(model, lr=learning_rate, amp=amp, surface_classes=surface.classes if surface is not None else None,
-                           ema=ema, loss=loss, **({} if distill is None else {"distill": distill}))
+                           ema=ema, loss=loss, **({} if distill is None else {"distill": distill}),
+                           **({} if optimizer is None else {"optimizer": optimizer}))
+    if stepper.optim_config is not None and log:
+        log(f"Optimizer: {stepper.optim_config.spec()}")
     if stepper.distill is not None and log:
         log(f"Distillation: teacher {stepper.distill.config.spec()}")
     lr = learning_rate
@@ -587,7 +610,7 @@ def main(argv=None) -> int:
                            workers=args.workers, log=logging.info, pred_dir=args.pred_dir, metrics=args.metrics,
                            augment=augment, surface=args.surface_loss, elastic=elastic, ema=args.ema,
                            save_state=args.save_state, resume=resume, record=record, loss=args.loss,
-                           crop=args.crop, tile=args.tile, distill=args.distill)
+                           crop=args.crop, tile=args.tile, distill=args.distill, optimizer=args.optimizer)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")
