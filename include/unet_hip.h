@@ -815,6 +815,30 @@ int uh_tile_gather(const float* x, float* tiles, int B, int H, int W, int C, int
 int uh_tile_merge(const void* src, int kind, int views, int B, int H, int W, int NC, int size, int overlap,
                   unsigned long long* sums, unsigned int* den, uint8_t* classes, float* probs, uh_stream stream);
 
+/* ---- checkpoint ensembles  (csrc/ensemble.hip; the reference has none) -------------------------------------------------
+ * The members' results are added per pixel and class as integers, each member with an integer weight; the work has no
+ * geometry, so every array is flat: [npix][NC], logits through the head's NHWC view.
+ * uh_ensemble_add: acc uint64 [npix][NC]; first != 0: acc[i] = weight s[i] (the accumulator needs no memset), first == 0:
+ *   acc[i] += weight s[i].  kind says what src holds: UH_F32 / UH_BF16 = a member's logits, s = q = (uint32) rintf(p 2^24), p the
+ *   fp32 softmax over the classes (NC = 1: the sigmoid) -- the device functions uh_tta_merge and uh_tile_merge quantise with,
+ *   so the same logits give the same q in all three; UH_TILE_SUMS_I32 = the uint32 sums of uh_tta_merge; UH_ENS_SUMS_U64 = the
+ *   uint64 sums of uh_tile_merge.  No atomics, no float after the quantisation: the result depends on no order of the members.
+ *   1 <= NC <= 256, 1 <= weight <= 1024, npix < 2^40.
+ * uh_ensemble_finish: per pixel T = den[pix] views 2^24 total_weight (den null: 1; views 1, 2, 4 or 8; 1 <= total_weight
+ *   <= 1024).  Outputs, each nullable (one at least): classes uint8 [npix], the first maximum of acc over the classes (NC = 1:
+ *   2 acc > T); probs float32 [npix][NC] = (float)((double) acc / (double) T); confidence uint8 [npix] = floor(255 max_c acc[c] /
+ *   sum_c acc[c]), 0 where the sum is 0 (NC = 1: floor(255 max(a, T - a) / T) with a = min(acc, T)).
+ * Bound: a member's tile sums stay below 2^49 with their views included (above), so acc < 2^49 total_weight <= 2^59 and
+ *   T < 2^22 2^3 2^24 2^10 = 2^59: every sum and 2 acc fit in 64 bits.  255 acc fits only while den views total_weight < 2^32;
+ *   the confidence is formed by a restoring division that never holds 255 acc, so it is exact over the whole range.
+ * Null or misaligned pointers (acc 8 bytes; src, den, probs their element), a bad kind, views, weight, total_weight or NC:
+ * UH_EINVAL before any launch. */
+enum { UH_ENS_SUMS_U64 = 4 };
+int uh_ensemble_add(const void* src, int kind, int64_t npix, int NC, unsigned weight, int first, unsigned long long* acc,
+                    uh_stream stream);
+int uh_ensemble_finish(const unsigned long long* acc, const unsigned int* den, int views, unsigned total_weight, int64_t npix,
+                       int NC, uint8_t* classes, float* probs, uint8_t* confidence, uh_stream stream);
+
 /* ---- patch training: seeded foreground-aware crops  (csrc/crop.hip; the reference has none) ---------------------------
  * One square crop of side `size` (a multiple of 16, >= 16) per item.  The item table is HOST memory, one row per item, and the
  * items may differ in size (1 <= H, W <= 16384, both >= size): every row is checked before any launch and the rows travel

@@ -19,7 +19,7 @@ UH_WFRAG, UH_WFRAG_D = 0x100, 0x200      # fragment-major filter packs (include/
 
 _CTYPES = {
     "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
-    "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64, "uh_stream": ctypes.c_void_p,
+    "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64, "uh_stream": ctypes.c_void_p, "unsigned": ctypes.c_uint,
 }
 _RET = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
 

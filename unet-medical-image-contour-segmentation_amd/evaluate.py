@@ -55,12 +55,13 @@ class _PredDump:
         self.writer.close()
 
 
-def _tta_merged(net, x, tta, sums=False):
+def _tta_merged(net, x, tta, sums=False, views=None):
     """ops.tta_merge of the views of a prepared batch [n,C,H,W] under `tta` (inside evaluate's autocast).  Each view of the
-    batch is a launch of its own, of the batch's length, under the pinned plan of one image."""
+    batch is a launch of its own, of the batch's length, under the pinned plan of one image.  `views`: ops.tta_views(x, tta)
+    where the caller has built it (an ensemble builds it once for all members)."""
     n, _, H, W = x.shape
     k0, k1 = tta_counts(tta)
-    views0, views1 = ops.tta_views(x, tta)
+    views0, views1 = ops.tta_views(x, tta) if views is None else views
     with ops.plan_images(1):
         logits0 = torch.cat([net(views0[k * n:(k + 1) * n]) for k in range(k0)])
         logits1 = torch.cat([net(views1[k * n:(k + 1) * n]) for k in range(k1)]) if k1 else None
@@ -72,18 +73,46 @@ def _tta_classes(net, image, tta):
     return _tta_merged(net, image, tta).classes
 
 
-def _tile_classes(net, image, tile, tta):
-    """uint8 [B,H,W]: the classes of the tiled prediction of a batch (inside evaluate's autocast).  The tiles go through the
-    network len(image) at a time under the pinned plan of one image; with `tta` every such launch group goes through
-    _tta_merged and the tile merge adds the views' integer sums."""
+def _tile_merged(net, image, tile, tta, sums=False, tiles=None):
+    """ops.tile_merge of the tiled prediction of a batch (inside evaluate's autocast).  The tiles go through the network
+    len(image) at a time under the pinned plan of one image; with `tta` every such launch group goes through _tta_merged and
+    the tile merge adds the views' integer sums.  `tiles`: ops.tile_gather(image, tile) where the caller has built it."""
     B, _, H, W = image.shape
-    tiles = ops.tile_gather(image, tile)
+    if tiles is None:
+        tiles = ops.tile_gather(image, tile)
     if tta is None:
         with ops.plan_images(1):
             src = torch.cat([net(tiles[s:s + B]) for s in range(0, tiles.shape[0], B)])
-        return ops.tile_merge(src, tile, (H, W)).classes
-    sums = torch.cat([_tta_merged(net, tiles[s:s + B], tta, sums=True).sums for s in range(0, tiles.shape[0], B)])
-    return ops.tile_merge(sums, tile, (H, W), sum(tta_counts(tta))).classes
+        return ops.tile_merge(src, tile, (H, W), sums=sums)
+    src = torch.cat([_tta_merged(net, tiles[s:s + B], tta, sums=True).sums for s in range(0, tiles.shape[0], B)])
+    return ops.tile_merge(src, tile, (H, W), sum(tta_counts(tta)), sums=sums)
+
+
+def _tile_classes(net, image, tile, tta):
+    """uint8 [B,H,W]: the classes of the tiled prediction of a batch."""
+    return _tile_merged(net, image, tile, tta).classes
+
+
+def _ensemble_classes(ens, image, tta, tile):
+    """uint8 [B,H,W]: the classes of an ensemble's prediction of a batch (inside evaluate's autocast): per member the logits
+    (under the pinned plan of one image), the view sums of _tta_merged or (tile: the batch is larger than one tile) the tile
+    sums of _tile_merged, added by ops.ensemble_add with the member's weight; the views and the tiles are built once.  The
+    one-channel head goes through the NC = 1 rule of uh_ensemble_finish, 2 acc > T."""
+    _, _, H, W = image.shape
+    views = ops.tta_views(image, tta) if tta is not None and tile is None else None
+    tiles = ops.tile_gather(image, tile) if tile is not None else None
+    acc = den = None
+    for net, w in zip(ens.members, ens.weights):
+        if tile is not None:
+            merged = _tile_merged(net, image, tile, tta, sums=True, tiles=tiles)
+            src, den = merged.sums, merged.den
+        elif tta is not None:
+            src = _tta_merged(net, image, tta, sums=True, views=views).sums
+        else:
+            with ops.plan_images(1):
+                src = net(image)
+        acc = ops.ensemble_add(src, w, acc)
+    return ops.ensemble_finish(acc, ens.total_weight, views=1 if tta is None else sum(tta_counts(tta)), den=den).classes
 
 
 @torch.inference_mode()
@@ -98,7 +127,14 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
     is the same 3-tuple either way.  `tta`: "hflip", "flips", "rot4" or "d4" -- the masks that are scored, post-processed,
     measured and dumped are those of the prediction averaged over these views (None: one forward, as the reference).
     `tile`: a TileConfig or a spec like "512,overlap=128" -- images larger than one tile are predicted tile by tile and merged
-    with the overlap blended (None: whole images)."""
+    with the overlap blended (None: whole images).
+    `net` may be a utils.ensemble.Ensemble: the masks that are scored are then the first maximum of the members' integer sums
+    (uh_ensemble_add, uh_ensemble_finish), under `tta` and `tile` as well; an Ensemble of one member is scored as that member."""
+    from .utils.ensemble import Ensemble, single_model
+    ens = net if isinstance(net, Ensemble) and single_model(net) is None else None
+    whole = net                                                      # what goes back into train mode at the end
+    if ens is None:
+        net = single_model(net)
     if tta is not None:
         tta = tta_mask(tta)
     if tile is not None:
@@ -117,7 +153,10 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
             image = image.to(device=device, dtype=torch.float32, memory_format=torch.channels_last)
             mask_true = mask_true.to(device=device, dtype=torch.float32)
             tiled = tile is not None and tile_count(image.shape[2], image.shape[3], tile) > 1
-            if tiled:
+            plain = tta is None and not tiled and ens is None
+            if ens is not None:
+                merged = _ensemble_classes(ens, image, tta, tile if tiled else None)
+            elif tiled:
                 merged = _tile_classes(net, image, tile, tta)
             elif tta is None:
                 mask_pred = net(image)
@@ -126,7 +165,7 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
             if net.n_classes == 1:
                 mask_true = torch.div(mask_true, 2, rounding_mode="floor")                      # evaluate.py:56
                 assert mask_true.min() >= 0 and mask_true.max() <= 1, "True mask indices should be in [0, 1]"
-                if tta is None and not tiled:
+                if plain:
                     pred = ops.threshold_mask(mask_pred.squeeze(1))    # sigmoid(x) > 0.5  <=>  x > 0   (evaluate.py:60-62)
                 else:
                     pred = merged.float()                              # the averaged (or blended) sigmoid > 0.5
@@ -149,7 +188,7 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
                 if dump is not None:                                                            # evaluate.py:88-105
                     dump.add(num_val_batches, pred.to(torch.uint8), "binary", processed_u8 if postprocess else None, "binary")
             else:
-                idx = ops.argmax_classes(mask_pred) if tta is None and not tiled else merged.long()   # evaluate.py:111
+                idx = ops.argmax_classes(mask_pred) if plain else merged.long()   # evaluate.py:111
                 true_c = (mask_true == 2).float()
                 d = dice_coeff((idx == 2).float(), true_c, reduce_batch_first=False)
                 cur = d
@@ -166,7 +205,7 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
                              "postprocessed")
             dice_score += d
             min_dice = torch.minimum(min_dice, cur.float())
-    net.train()
+    whole.train()
     if dump is not None:
         dump.close()                                            # every file is on disk before the metric is returned
     import torch.distributed as dist

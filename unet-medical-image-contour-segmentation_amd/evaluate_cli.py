@@ -1,6 +1,6 @@
 """Scores a checkpoint on a data split without training (the reference reaches evaluate.py from its train loop only):
 
-    python -m unet_amd.evaluate -m CKPT --data-root DIR [--split val] [--arch UNet_S|UNet|UNet_T|UNet_SA] [-c 3] [--bilinear]
+    python -m unet_amd.evaluate -m CKPT [MEMBER ...] --data-root DIR [--split val] [--arch UNet_S|UNet|UNet_T|UNet_SA] [-c 3] [--bilinear]
                                 [-b 8] [-s 0.5] [--no-postprocess] [--no-amp] [--no-metrics] [--spacing 1.0]
                                 [--pred-dir DIR] [--workers 8] [--json OUT] [--tta [hflip|flips|rot4|d4]]
                                 [--tile [SIZE[,overlap=N]]]
@@ -13,6 +13,8 @@ minimum -- and, unless --no-metrics, the contour metrics HD95 / HD / ASSD / IoU 
 predictions as grey-coded PNGs, as evaluate(epoch_pred_dir=...) does.  --json writes the set results and the per-image table.
 --tta scores the prediction averaged over the views of a mode (utils/tta.py; a bare --tta means d4) and records it in --json.
 --tile scores the sliding-window prediction (utils/tiling.py; a bare --tile means 512,overlap=128) and records its spec in --json.
+Several -m items, or one with a key or a glob (PATH[,arch=A][,w=N], utils/ensemble.py), score the ensemble of those checkpoints;
+--json then lists the members: path, arch, weight and the SHA-256 of the file.  One plain -m CKPT is scored as ever.
 Exit status 1: a missing directory, an empty split (or one shorter than a batch), a checkpoint that does not load.  There is
 no CPU fallback: without a GPU the command exits with status 2, after those checks."""
 from __future__ import annotations
@@ -28,8 +30,11 @@ ARCHS = ("UNet_S", "UNet", "UNet_T", "UNet_SA")
 
 
 def build_parser() -> argparse.ArgumentParser:
+    from .predict_cli import _MembersAction
     p = argparse.ArgumentParser(description="Score a checkpoint on a validation split: Dice and contour-distance metrics")
-    p.add_argument("--model", "-m", required=True, help="Checkpoint (.pth state_dict)")
+    p.add_argument("--model", "-m", required=True, nargs="+", action=_MembersAction, metavar="CKPT",
+                   help="Checkpoint (.pth state_dict); several items, each PATH[,arch=A][,w=N] (PATH may be a glob), are scored "
+                        "as an ensemble")
     p.add_argument("--data-root", required=True, help="Directory holding imgs/SPLIT and masks/SPLIT")
     p.add_argument("--split", default="val", help="Sub-directory of imgs/ and masks/ that is scored")
     p.add_argument("--arch", choices=ARCHS, default="UNet_S", help="Network (the train command's default)")
@@ -78,10 +83,12 @@ def _plain(v):
     return v
 
 
-def report(dice, contour, tta=None, tile=None) -> dict:
-    """What --json writes: {"dice": {...}, "metrics": {"raw": {...}, "post": {...}} or null}, "tta": mode under --tta and
-    "tile": spec under --tile."""
+def report(dice, contour, tta=None, tile=None, members=None) -> dict:
+    """What --json writes: {"dice": {...}, "metrics": {"raw": {...}, "post": {...}} or null}, "tta": mode under --tta,
+    "tile": spec under --tile and "members": [{"path", "arch", "weight", "sha256"}] for an ensemble."""
     out = {"dice": {"mean": float(dice[0]), "postprocessed": float(dice[1]), "min": float(dice[2])}, "metrics": None}
+    if members is not None:
+        out["members"] = [{k: r[k] for k in ("path", "arch", "weight", "sha256")} for r in members]
     if tta is not None:
         out["tta"] = tta
     if tile is not None:
@@ -103,7 +110,9 @@ def main(argv=None) -> int:
     if args.batch_size < 1 or args.workers < 1 or not 0 < args.scale <= 1 or not args.spacing > 0:
         logging.error("--batch-size and --workers must be at least 1, --scale in (0, 1], --spacing positive")
         return 1
-    if not os.path.isfile(args.model):
+    from .utils.ensemble import is_plain_single
+    plain = is_plain_single(args.members)                             # one bare path: the one-model statements below
+    if plain and not os.path.isfile(args.model):
         logging.error("Checkpoint does not exist: %s", args.model)
         return 1
     import torch
@@ -120,14 +129,23 @@ def main(argv=None) -> int:
                       args.batch_size)
         return 1
     try:
-        model = build_model(args.arch, args.classes, args.bilinear)
-        model = model.to(memory_format=torch.channels_last)
-        load_checkpoint(model, args.model, device="cpu")
+        if plain:
+            model = build_model(args.arch, args.classes, args.bilinear)
+            model = model.to(memory_format=torch.channels_last)
+            load_checkpoint(model, args.model, device="cpu")
+        else:
+            from .utils.ensemble import Ensemble
+            model = Ensemble.load(args.members, 1, args.classes, args.arch, "cpu")
     except Exception as e:
         logging.error("Failed to load the model %s: %s", args.model, e)
         return 1
-    logging.info("Model loaded: %s, %d classes, %s upscaling", args.arch, args.classes,
-                 "bilinear" if args.bilinear else "transposed conv")
+    if plain:
+        logging.info("Model loaded: %s, %d classes, %s upscaling", args.arch, args.classes,
+                     "bilinear" if args.bilinear else "transposed conv")
+    else:
+        for r in model.records:
+            logging.info("Member loaded: %s, %s, %s upscaling, weight %d", r["path"], r["arch"],
+                         "bilinear" if r["bilinear"] else "transposed conv", r["weight"])
     if not torch.cuda.is_available():
         logging.error("evaluate: no GPU found. This port evaluates on the MI355X through its HIP kernels and has no CPU path.")
         return 2
@@ -148,7 +166,7 @@ def main(argv=None) -> int:
         logging.info(format_line(contour, args.postprocess))
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(report(dice, contour, args.tta, args.tile), f, indent=1)
+            json.dump(report(dice, contour, args.tta, args.tile, None if plain else model.records), f, indent=1)
         logging.info("Results written to %s", args.json)
     return 0
 

@@ -1783,6 +1783,73 @@ def tile_merge(src: torch.Tensor, cfg, size: Tuple[int, int], views: int = 1, *,
     return TileMerged(classes, s, d, p)
 
 
+# ----------------------------------------------------------------------------- checkpoint ensembles (csrc/ensemble.hip)
+UH_ENS_SUMS_U64 = 4                           # include/unet_hip.h: the uint64 sums of uh_tile_merge as the source of uh_ensemble_add
+
+
+class EnsembleMerged(NamedTuple):
+    classes: torch.Tensor                     # uint8 [B,H,W]
+    probs: Optional[torch.Tensor]             # float32 [B,H,W,NC] = acc / (den * views * 2^24 * total_weight)
+    confidence: Optional[torch.Tensor]        # uint8 [B,H,W] = floor(255 * max_c acc / sum_c acc)
+
+
+def ensemble_add(src: torch.Tensor, weight: int = 1, acc: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adds one member's result, `weight` times, into the accumulator int64 [B,H,W,NC] (uint64 in the library) and returns it;
+    acc = None: a new accumulator that the member is assigned to (no memset).  src: the member's logits [B,NC,H,W] (fp32 or
+    bf16, read through their NHWC view and quantised as tta_merge / tile_merge quantise), the int32 sums [B,H,W,NC] of
+    tta_merge(sums=True), or the int64 sums [B,H,W,NC] of tile_merge(sums=True)."""
+    _require_gpu(src, "member results")
+    if isinstance(weight, bool) or not isinstance(weight, int) or not 1 <= weight <= 1024:
+        raise ValueError(f"ensemble_add: weight is an integer in 1..1024, got {weight!r}")
+    if src.dim() != 4:
+        raise RuntimeError(f"ensemble_add expects 4-d member results, got {tuple(src.shape)}")
+    if src.dtype in (torch.int32, torch.int64):
+        v, kind = src, UH_TILE_SUMS_I32 if src.dtype == torch.int32 else UH_ENS_SUMS_U64
+    else:
+        v = src.permute(0, 2, 3, 1)
+        if v.dtype not in (torch.float32, torch.bfloat16):
+            v = v.float()
+        kind = _dt(v)
+    if not v.is_contiguous():
+        v = v.contiguous()
+    B, H, W, NC = v.shape
+    if NC > 256 or v.numel() == 0:
+        raise RuntimeError(f"ensemble_add expects 1..256 classes and at least one pixel, got {tuple(src.shape)}")
+    first = acc is None
+    if first:
+        acc = torch.empty(B, H, W, NC, dtype=torch.int64, device=v.device)
+    elif acc.dtype != torch.int64 or tuple(acc.shape) != (B, H, W, NC) or not acc.is_contiguous() or acc.device != v.device:
+        raise RuntimeError(f"ensemble_add: the accumulator must be a contiguous int64 [{B},{H},{W},{NC}] on the member's device")
+    LIB.call("uh_ensemble_add", v.data_ptr(), kind, B * H * W, NC, weight, 1 if first else 0, acc.data_ptr(), _stream())
+    return acc
+
+
+def ensemble_finish(acc: torch.Tensor, total_weight: int, *, views: int = 1, den: Optional[torch.Tensor] = None, probs: bool = False,
+                    confidence: bool = False) -> EnsembleMerged:
+    """The accumulator of ensemble_add over members of `total_weight` in all -> EnsembleMerged(classes, probs or None, confidence
+    or None).  views: the views every member's sums add up (1, 2, 4 or 8); den: the int32 [B,H,W] weights of tile_merge (the
+    same for every member), None for untiled members."""
+    _require_gpu(acc, "accumulator")
+    if views not in (1, 2, 4, 8):
+        raise ValueError(f"ensemble_finish: views is 1, 2, 4 or 8, got {views!r}")
+    if isinstance(total_weight, bool) or not isinstance(total_weight, int) or not 1 <= total_weight <= 1024:
+        raise ValueError(f"ensemble_finish: total_weight is an integer in 1..1024, got {total_weight!r}")
+    if acc.dtype != torch.int64 or acc.dim() != 4 or not acc.is_contiguous() or acc.shape[3] > 256 or acc.numel() == 0:
+        raise RuntimeError(f"ensemble_finish expects a contiguous int64 [B,H,W,NC<=256] accumulator, got {acc.dtype} {tuple(acc.shape)}")
+    B, H, W, NC = acc.shape
+    if den is not None:
+        _require_gpu(den, "den")
+        if den.dtype != torch.int32 or tuple(den.shape) != (B, H, W) or not den.is_contiguous():
+            raise RuntimeError(f"ensemble_finish: den must be a contiguous int32 [{B},{H},{W}]")
+    dev = acc.device
+    classes = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    p = torch.empty(B, H, W, NC, dtype=torch.float32, device=dev) if probs else None
+    c = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if confidence else None
+    LIB.call("uh_ensemble_finish", acc.data_ptr(), _p(den), int(views), total_weight, B * H * W, NC, classes.data_ptr(), _p(p), _p(c),
+             _stream())
+    return EnsembleMerged(classes, p, c)
+
+
 # ----------------------------------------------------------------------------- patch training (csrc/crop.hip)
 def crop_select(labels: Sequence[torch.Tensor], words, size: int, class_mask: int, threshold: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """The crop origins of utils/crop.py for int64 label planes [H,W] of any sizes: words uint32 [B,4] (r0..r3 per plane),

@@ -226,6 +226,16 @@ class LaunchPlanner:
         return self.batch if self.tta is None else self.tta_group(th, tw)
 
 
+class _Member:
+    """What a member of an ensemble keeps to itself: its network, its weight, its launch arithmetic and its graph cache."""
+
+    def __init__(self, model: torch.nn.Module, weight: int, batch: int, amp: bool, batch_invariant: bool, tta):
+        self.model, self.weight = model, int(weight)
+        self.planner = LaunchPlanner(model, batch, amp, batch_invariant, tta)
+        self._graphs: "OrderedDict[Tuple[int, int, int], object]" = OrderedDict()
+        self._seen = set()
+
+
 class BatchPredictor:
     """`predictor(images)` -> one uint8 [H,W] grey-coded mask per image, in input order: what
     mask_to_image(postprocess_mask(predict_img(model, image, device))) returns for that image (mask_to_image(predict_img(...))
@@ -250,7 +260,15 @@ class BatchPredictor:
     "Tiled prediction").  Post-processing and grey coding run on the whole-image map as ever.  An image that fits in one tile
     is that tile and gets the bits of the untiled path.  With `tta`, every chunk of `tta_group` tiles goes through the views,
     the forward and uh_tta_merge, and the tile merge adds the views' integer sums; the tile origins are not mirror-symmetric,
-    so a posed image is NOT promised the posed prediction here.  None: nothing of this runs."""
+    so a posed image is NOT promised the posed prediction here.  None: nothing of this runs.
+
+    `model` may be a utils.ensemble.Ensemble (DESIGN.md section 3 "Ensembles").  Upload, prepare, uh_tta_views and uh_tile_gather
+    run once per batch; every member runs its forward on the same staged tensor, cut by its own LaunchPlanner and replaying its
+    own graph cache (MAX_GRAPHS each); its logits -- under `tta` its view sums, under `tile` its tile sums -- go through
+    uh_ensemble_add with the member's weight, and uh_ensemble_finish takes the first maximum of the integer sums, so the masks
+    depend on no order of the members.  `probabilities(images)` then also works without `tta` or `tile`, and
+    `confidence(images)` returns floor(255 max / sum) of the summed probabilities per pixel.  A bare module, or an Ensemble of
+    one member, runs the one-model statements unchanged."""
 
     MAX_GRAPHS = 4
 
@@ -274,14 +292,23 @@ class BatchPredictor:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise RuntimeError("BatchPredictor needs an MI355X: the HIP path has no CPU fallback")
-        self.model = model.to(self.device).eval()
+        from .utils.ensemble import single_model
+        solo = single_model(model)
+        self.ensemble = model.to(self.device).eval() if solo is None else None     # None: one network, today's statements
+        self.model = solo.to(self.device).eval() if solo is not None else self.ensemble
         self.batch, self.postprocess, self.amp = int(batch), bool(postprocess), bool(amp)
         self.min_area, self.ksize = int(min_area), int(morph_kernel_size)
         self._lut = torch.from_numpy(GREY_CLASSES.copy()).to(self.device)
         self._flags = torch.empty(self.batch, dtype=torch.int32, device=self.device)
         self._graphs: "OrderedDict[Tuple[int, int, int], object]" = OrderedDict()
         self._seen = set()
-        self.planner = LaunchPlanner(self.model, self.batch, self.amp, self.batch_invariant, self.tta)
+        if self.ensemble is None:
+            self.planner = LaunchPlanner(self.model, self.batch, self.amp, self.batch_invariant, self.tta)
+            self._members: List[_Member] = []
+        else:
+            self._members = [_Member(m, w, self.batch, self.amp, self.batch_invariant, self.tta)
+                             for m, w in zip(self.ensemble.members, self.ensemble.weights)]
+            self.planner = self._members[0].planner
         self._pin_in: Optional[torch.Tensor] = None
         self._pin_out: Optional[torch.Tensor] = None
         self._upload_done = torch.cuda.Event()                        # recorded behind every upload out of _pin_in
@@ -296,10 +323,10 @@ class BatchPredictor:
         return self.planner.launch_lengths(H, W)
 
     def tta_group(self, H: int, W: int) -> int:
-        return self.planner.tta_group(H, W)
+        return min([self.planner.tta_group(H, W)] + [m.planner.tta_group(H, W) for m in self._members])
 
     def tile_chunk(self, th: int, tw: int) -> int:
-        return self.planner.tile_chunk(th, tw)
+        return min([self.planner.tile_chunk(th, tw)] + [m.planner.tile_chunk(th, tw) for m in self._members])
 
     def _pinned(self, which: str, nbytes: int) -> torch.Tensor:
         buf = getattr(self, which)
@@ -330,29 +357,35 @@ class BatchPredictor:
         self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
         return x
 
-    def _forward(self, x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
-        full = self.launch_lengths(*size)[-1]                          # the longest launch this size allows
+    def _forward(self, x: torch.Tensor, size: Tuple[int, int], m=None) -> torch.Tensor:
+        """`m`: the ensemble member whose network, planner and graph cache serve the call (None: the predictor's own)."""
+        m = self if m is None else m
+        full = m.planner.launch_lengths(*size)[-1]                     # the longest launch this size allows
         size = (x.shape[0],) + tuple(size)
-        if x.shape[0] == full and size in self._seen:
-            g = self._graphs.pop(size, None)
+        if x.shape[0] == full and size in m._seen:
+            g = m._graphs.pop(size, None)
             if g is None:
-                while len(self._graphs) >= self.MAX_GRAPHS:
-                    self._graphs.popitem(last=False)                  # least recently used
-                g = GraphedForward(self.model, x, amp=self.amp, plan_images=1 if self.batch_invariant else 0)
-            self._graphs[size] = g
+                while len(m._graphs) >= self.MAX_GRAPHS:
+                    m._graphs.popitem(last=False)                     # least recently used
+                g = GraphedForward(m.model, x, amp=self.amp, plan_images=1 if self.batch_invariant else 0)
+            m._graphs[size] = g
             self.graph_replays += 1
             return g(x)
         if x.shape[0] == full:
-            self._seen.add(size)
-        return eval_forward(self.model, x, self.amp, plan_images=1 if self.batch_invariant else 0)
+            m._seen.add(size)
+        return eval_forward(m.model, x, self.amp, plan_images=1 if self.batch_invariant else 0)
 
-    def run_batch(self, arrays: List[np.ndarray], grey: bool = True, probs: bool = False) -> np.ndarray:
+    def run_batch(self, arrays: List[np.ndarray], grey: bool = True, probs: bool = False, conf: bool = False) -> np.ndarray:
         """One batch of equally sized uint8 [H,W] images -> uint8 [B,H,W] on the host (grey-coded, or class indices), in as
-        few launches as launch_lengths allows; or (probs, under `tta` or `tile`) float32 [B,NC,H,W]."""
+        few launches as launch_lengths allows; or (probs; under `tta`, `tile` or an ensemble) float32 [B,NC,H,W]; or (conf; an
+        ensemble) uint8 [B,2,H,W], the masks and the confidence maps."""
         H, W = arrays[0].shape
         if self.tile is not None:
-            return np.stack(self._run_tiled(arrays, grey, probs))
-        if self.tta is not None:
+            return np.stack(self._run_tiled(arrays, grey, probs, conf))
+        if self.ensemble is not None:
+            g = self.batch if self.tta is None else self.tta_group(H, W)
+            out = [self._launch_ensemble(arrays[s:s + g], grey, probs, conf) for s in range(0, len(arrays), g)]
+        elif self.tta is not None:
             g = self.tta_group(H, W)
             out = [self._launch_tta(arrays[s:s + g], grey, probs) for s in range(0, len(arrays), g)]
         else:
@@ -385,21 +418,22 @@ class BatchPredictor:
         return out.numpy().copy()
 
     # ---------------------------------------------------------------- test-time augmentation
-    def _forward_cut(self, x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+    def _forward_cut(self, x: torch.Tensor, size: Tuple[int, int], m=None) -> torch.Tensor:
         """_forward for a view batch of any length, in as few launches as launch_lengths allows."""
-        cut = self.planner.cut(x.shape[0], *size)
+        cut = (self if m is None else m).planner.cut(x.shape[0], *size)
         if len(cut) == 1:
-            return self._forward(x, size)
-        return torch.cat([self._forward(part, size).clone() for part in x.split(cut)])   # (a replayed graph returns its static buffer)
+            return self._forward(x, size, m)
+        return torch.cat([self._forward(part, size, m).clone() for part in x.split(cut)])   # (a replayed graph returns its static buffer)
 
-    def _tta_logits(self, x: torch.Tensor, H: int, W: int):
-        """The logits of the views of a prepared batch [B,C,H,W]: (untransposed views, transposed views or None)."""
-        v0, v1 = self._mark("views", ops.tta_views, x, self.tta)
+    def _tta_logits(self, x: torch.Tensor, H: int, W: int, m=None, views=None):
+        """The logits of the views of a prepared batch [B,C,H,W]: (untransposed views, transposed views or None).  `views`:
+        the result of ops.tta_views(x) when the caller has built it (an ensemble builds it once for all members)."""
+        v0, v1 = self._mark("views", ops.tta_views, x, self.tta) if views is None else views
         if v1 is not None and H == W:                                  # one view shape: one forward
-            l0, l1 = self._mark("forward", self._forward_cut, ops.tta_joint_views(v0, v1), (H, W)), None
+            l0, l1 = self._mark("forward", self._forward_cut, ops.tta_joint_views(v0, v1), (H, W), m), None
         else:
-            l0 = self._mark("forward", self._forward_cut, v0, (H, W))
-            l1 = self._mark("forward", self._forward_cut, v1, (W, H)) if v1 is not None else None
+            l0 = self._mark("forward", self._forward_cut, v0, (H, W), m)
+            l1 = self._mark("forward", self._forward_cut, v1, (W, H), m) if v1 is not None else None
         if tuple(l0.shape[-2:]) != (H, W) or (l1 is not None and tuple(l1.shape[-2:]) != (W, H)):
             raise RuntimeError(f"the network returned {tuple(l0.shape[-2:])} for a {(H, W)} input")
         return l0, l1
@@ -414,6 +448,44 @@ class BatchPredictor:
                 return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
             return self._deliver(merged.classes, grey)
 
+    # ---------------------------------------------------------------- ensembles
+    def _views(self) -> int:
+        if self.tta is None:
+            return 1
+        from .utils.tta import tta_counts
+        return sum(tta_counts(self.tta))
+
+    def _ensemble_deliver(self, acc: torch.Tensor, den, grey: bool, probs: bool, conf: bool) -> np.ndarray:
+        """The members' summed results -> uint8 [B,H,W] as _launch, (probs) float32 [B,NC,H,W], or (conf) uint8 [B,2,H,W]: the
+        masks as _launch returns them and the confidence maps."""
+        merged = self._mark("ensemble_finish", ops.ensemble_finish, acc, self.ensemble.total_weight, views=self._views(), den=den,
+                            probs=probs, confidence=conf)
+        if probs:
+            return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
+        masks = self._deliver(merged.classes, grey)
+        if conf:
+            return np.stack([masks, merged.confidence.cpu().numpy()], axis=1)
+        return masks
+
+    def _launch_ensemble(self, arrays: List[np.ndarray], grey: bool, probs: bool = False, conf: bool = False) -> np.ndarray:
+        """One launch group of an ensemble: one upload, one prepare and (under `tta`) one set of views; per member the forward
+        on that tensor and uh_ensemble_add of its logits or of its view sums."""
+        H, W = arrays[0].shape
+        with torch.cuda.device(self.device):
+            x = self._stage(arrays)
+            views = self._mark("views", ops.tta_views, x, self.tta) if self.tta is not None else None
+            acc = None
+            for m in self._members:
+                if self.tta is None:
+                    src = self._mark("forward", self._forward_cut, x, (H, W), m)
+                    if tuple(src.shape[-2:]) != (H, W):
+                        raise RuntimeError(f"the network returned {tuple(src.shape[-2:])} for a {(H, W)} input")
+                else:
+                    l0, l1 = self._tta_logits(x, H, W, m, views)
+                    src = self._mark("merge", ops.tta_merge, l0, l1, self.tta, (H, W), sums=True).sums
+                acc = self._mark("ensemble_add", ops.ensemble_add, src, m.weight, acc)
+            return self._ensemble_deliver(acc, None, grey, probs, conf)
+
     # ---------------------------------------------------------------- tiled prediction
     def _prepare_tiles(self, arrays: List[np.ndarray]) -> torch.Tensor:
         """Equally sized images -> their tiles [B*ny*nx,1,th,tw] on the device; the prepare sees the WHOLE images."""
@@ -424,6 +496,8 @@ class BatchPredictor:
         """One forward step of the tiled flow: the logits [n,NC,th,tw] of the tiles, or under test-time augmentation the
         int32 sums [n,th,tw,NC] over their views."""
         th, tw = shape
+        if self.ensemble is not None:
+            return self._tile_forward_ensemble(tiles, shape)
         with torch.cuda.device(self.device):
             if self.tta is None:
                 logits = self._mark("forward", self._forward_cut, tiles, shape)
@@ -433,9 +507,40 @@ class BatchPredictor:
             l0, l1 = self._tta_logits(tiles, th, tw)
             return self._mark("merge", ops.tta_merge, l0, l1, self.tta, shape, sums=True).sums
 
-    def _tile_finish(self, src: torch.Tensor, H: int, W: int, grey: bool, probs: bool) -> np.ndarray:
+    def _tile_forward_ensemble(self, tiles: torch.Tensor, shape: Tuple[int, int]) -> torch.Tensor:
+        """_tile_forward of every member on the same tiles, the members side by side in dimension 1: logits [n,M,NC,th,tw],
+        or under test-time augmentation (the views built once) int32 sums [n,M,th,tw,NC]."""
+        th, tw = shape
+        with torch.cuda.device(self.device):
+            views = self._mark("views", ops.tta_views, tiles, self.tta) if self.tta is not None else None
+            out = []
+            for m in self._members:
+                if self.tta is None:
+                    logits = self._mark("forward", self._forward_cut, tiles, shape, m)
+                    if tuple(logits.shape[-2:]) != (th, tw):
+                        raise RuntimeError(f"the network returned {tuple(logits.shape[-2:])} for a {(th, tw)} input")
+                    out.append(logits)
+                else:
+                    l0, l1 = self._tta_logits(tiles, th, tw, m, views)
+                    out.append(self._mark("merge", ops.tta_merge, l0, l1, self.tta, shape, sums=True).sums)
+            return torch.stack(out, dim=1)                              # (copies: a replayed graph returns its static buffer)
+
+    def _tile_finish_ensemble(self, src: torch.Tensor, H: int, W: int, grey: bool, probs: bool, conf: bool) -> np.ndarray:
+        """The members' results for every tile of a batch of H x W images: per member uh_tile_merge to its 64-bit sums (the
+        weights `den` are the same for all), uh_ensemble_add, then the finish as for any ensemble."""
+        with torch.cuda.device(self.device):
+            acc = den = None
+            for k, m in enumerate(self._members):
+                merged = self._mark("tile_merge", ops.tile_merge, src[:, k], self.tile, (H, W), self._views(), sums=True)
+                den = merged.den
+                acc = self._mark("ensemble_add", ops.ensemble_add, merged.sums, m.weight, acc)
+            return self._ensemble_deliver(acc, den, grey, probs, conf)
+
+    def _tile_finish(self, src: torch.Tensor, H: int, W: int, grey: bool, probs: bool, conf: bool = False) -> np.ndarray:
         """The results of every tile of a batch of H x W images -> uint8 [B,H,W] as _launch, or (probs) float32 [B,NC,H,W]."""
         from .utils.tiling import tile_count
+        if self.ensemble is not None:
+            return self._tile_finish_ensemble(src, H, W, grey, probs, conf)
         views = 1
         if self.tta is not None:
             from .utils.tta import tta_counts
@@ -450,7 +555,7 @@ class BatchPredictor:
                 cls = self._mark("tile_merge", ops.tile_merge, src, self.tile, (H, W), views).classes
             return self._deliver(cls, grey)
 
-    def _run_tiled(self, arrays: List[np.ndarray], grey: bool, probs: bool = False) -> List[np.ndarray]:
+    def _run_tiled(self, arrays: List[np.ndarray], grey: bool, probs: bool = False, conf: bool = False) -> List[np.ndarray]:
         """Images of any sizes -> their results in input order.  The tiles of all images that share a tile shape are pooled:
         same-size images (up to `batch`) share an upload, a prepare, a gather and a merge; the pool forwards `tile_chunk`
         tiles at a time, so every forward step but the last of a tile shape is full, and an image is merged and delivered
@@ -479,7 +584,7 @@ class BatchPredictor:
                         have = done[0] if len(done) == 1 else torch.cat(done)
                         done = [have[n:]] if have.shape[0] > n else []
                         n_done -= n
-                        out = self._tile_finish(have[:n], H, W, grey, probs)
+                        out = self._tile_finish(have[:n], H, W, grey, probs, conf)
                         for k, i in enumerate(idx):
                             result[i] = np.ascontiguousarray(out[k])
 
@@ -492,13 +597,13 @@ class BatchPredictor:
             advance(True)
         return result
 
-    def _run(self, images, grey: bool, probs: bool = False) -> List[np.ndarray]:
+    def _run(self, images, grey: bool, probs: bool = False, conf: bool = False) -> List[np.ndarray]:
         arrays = [_as_grey_array(im) for im in images]
         if self.tile is not None:
-            return self._run_tiled(arrays, grey, probs)
+            return self._run_tiled(arrays, grey, probs, conf)
         result: List[Optional[np.ndarray]] = [None] * len(arrays)
         for _, members in plan_batches([a.shape for a in arrays], self.batch):
-            out = self.run_batch([arrays[i] for i in members], grey, probs)
+            out = self.run_batch([arrays[i] for i in members], grey, probs, conf)
             for k, i in enumerate(members):
                 result[i] = np.ascontiguousarray(out[k])
         return result
@@ -511,11 +616,25 @@ class BatchPredictor:
 
     def probabilities(self, images) -> List[np.ndarray]:
         """float32 [NC,H,W] per image: the mean over the views of the softmax probabilities (multiples of 2^-24 / V); under
-        `tile` the weighted mean over the covering tiles (and their views), (float)(sum / (den V 2^24))."""
-        if self.tta is None and self.tile is None:
+        `tile` the weighted mean over the covering tiles (and their views), (float)(sum / (den V 2^24)); for an ensemble the
+        weighted mean over its members of either, or of the members' plain probabilities, (float)(sum / (den V 2^24 weights))."""
+        if self.tta is None and self.tile is None and getattr(self, "ensemble", None) is None:
             raise RuntimeError("probabilities() returns the mean over the views of test-time augmentation (tta=...) or over the "
                                "covering tiles of tiled prediction (tile=...): build the predictor with one of them")
         return self._run(images, False, probs=True)
+
+    def masks_and_confidence(self, images, grey: bool = True) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+        """(what predictor(images) returns, what confidence(images) returns) from one pass over the images."""
+        if getattr(self, "ensemble", None) is None:
+            raise RuntimeError("confidence() measures how far the members of an ensemble agree: build the predictor with a "
+                               "utils.ensemble.Ensemble of two or more members")
+        both = self._run(images, grey, conf=True)
+        return [np.ascontiguousarray(b[0]) for b in both], [np.ascontiguousarray(b[1]) for b in both]
+
+    def confidence(self, images) -> List[np.ndarray]:
+        """uint8 [H,W] per image: floor(255 max_c s_c / sum_c s_c) of the ensemble's summed probabilities s (255: every
+        member puts everything on one class), formed in integers on the device (uh_ensemble_finish)."""
+        return self.masks_and_confidence(images)[1]
 
 
 def main(argv=None) -> int:

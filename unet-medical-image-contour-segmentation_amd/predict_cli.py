@@ -1,8 +1,8 @@
 """The reference's prediction command line, /root/reference/predict.py:31-152, on the HIP path:
 
-    python -m unet_amd.predict -m model.pth -i FILE_OR_DIR [-o OUT] [-n] [-v] [--no-postprocess]
+    python -m unet_amd.predict -m model.pth [MEMBER ...] -i FILE_OR_DIR [-o OUT] [-n] [-v] [--no-postprocess]
                                [--arch UNet] [-c 3] [--bilinear] [--no-amp] [-b 8] [--workers 8] [--no-batch-invariant]
-                               [--tta [hflip|flips|rot4|d4]] [--tile [SIZE[,overlap=N]]]
+                               [--tta [hflip|flips|rot4|d4]] [--tile [SIZE[,overlap=N]]] [--confidence-dir DIR]
 
 Every image is predicted at its own size (scale 1).  The images of a folder are decoded by a thread pool, grouped by size,
 run through BatchPredictor in batches (prepare, eval forward, classes, post-processing and grey coding on the device, one
@@ -12,6 +12,10 @@ batch-invariant (BatchPredictor(batch_invariant=True)): a batch is one launch an
 (utils/tta.py; a bare --tta means d4): -b stays the number of images per forward launch, views included.  --tile predicts
 every image as overlapping tiles of one shape (utils/tiling.py; a bare --tile means 512,overlap=128): the images are grouped
 by tile shape instead of size, the tiles of a group share full forward launches of -b tiles, and the overlap is blended.
+Several -m items, or one with a key or a glob (PATH[,arch=A][,w=N], utils/ensemble.py), make an ensemble: the members'
+probabilities are added as integers with their weights before the argmax; --arch is the architecture of a member without
+arch=, and bilinear vs transposed-conv upsampling is read off each checkpoint.  --confidence-dir DIR also writes
+<stem>_conf.png, floor(255 max / sum) of the summed probabilities per pixel.  One plain -m x.pth runs the one-model path.
 
 Reference behaviour that is kept, awkward parts included:
   - predict.py:33-38  the flags -m, -i (both required), -o, -v, -n, and -p, a store_true whose default is already True;
@@ -47,10 +51,27 @@ ARCHS = ("UNet", "UNet_S", "UNet_T", "UNet_SA")
 EXTENSIONS = (".png", ".jpg", ".jpeg")
 
 
+class _MembersAction(argparse.Action):
+    """-m SPEC [SPEC ...]: `members` holds the specs; `model` stays the string it has always been for one -m item and is the
+    list for several."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        from .utils.ensemble import parse_member_spec
+        for v in values:
+            try:
+                parse_member_spec(v)
+            except ValueError as e:
+                parser.error(f"argument {option_string}: {e}")
+        namespace.members = list(values)
+        namespace.model = values[0] if len(values) == 1 else list(values)
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Predict multi-class masks for an image or a directory of images")
     # the reference's flags, short forms and defaults (predict.py:31-40)
-    p.add_argument("--model", "-m", required=True, help="Model weights (.pth state_dict)")
+    p.add_argument("--model", "-m", required=True, nargs="+", action=_MembersAction, metavar="MODEL",
+                   help="Model weights (.pth state_dict); several items, each PATH[,arch=A][,w=N] (PATH may be a glob), make "
+                        "an ensemble")
     p.add_argument("--input", "-i", required=True, help="Input image file or directory (walked recursively)")
     p.add_argument("--output", "-o", help="Output directory (default: <stem>.png next to each input, overwriting a PNG input)")
     p.add_argument("--viz", "-v", action="store_true", default=False, help="Show each result (needs matplotlib)")
@@ -83,6 +104,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--tile", nargs="?", const=DEFAULT_SPEC, default=None, type=tile_spec, metavar="SPEC",
                    help="Sliding-window prediction: cut every image into tiles of SIZE[,overlap=N] pixels and blend the overlap "
                         f"(a bare --tile: {DEFAULT_SPEC}; default: off)")
+    p.add_argument("--confidence-dir", default=None, metavar="DIR",
+                   help="Ensembles: also write <stem>_conf.png there, floor(255 max / sum) of the summed probabilities")
     return p
 
 
@@ -124,8 +147,14 @@ def _show(plt, path, img, grey):
     plt.show()
 
 
-def run(predictor, files: List[str], output: Optional[str], save: bool, workers: int, show=None, window: Optional[int] = None):
-    """Predicts `files` and writes the masks.  -> (written paths in write order, failed input paths)."""
+def confidence_path(confidence_dir: str, input_file: str) -> str:
+    return os.path.join(confidence_dir, os.path.splitext(os.path.basename(input_file))[0] + "_conf.png")
+
+
+def run(predictor, files: List[str], output: Optional[str], save: bool, workers: int, show=None, window: Optional[int] = None,
+        confidence_dir: Optional[str] = None):
+    """Predicts `files` and writes the masks (and, with `confidence_dir`, an ensemble's confidence maps, from the same pass).
+    -> (written paths in write order, failed input paths)."""
     from .predict import BatchPlanner
     from .utils.png_writer import OrderedPngWriter
     workers = max(1, int(workers))
@@ -137,10 +166,16 @@ def run(predictor, files: List[str], output: Optional[str], save: bool, workers:
     held = {}
     with ThreadPoolExecutor(max_workers=workers, thread_name_prefix="predict-io") as pool:
         writer = OrderedPngWriter(pool=pool)
+        conf_writer = OrderedPngWriter(pool=pool) if confidence_dir is not None else None
 
         def finish(members):
             imgs = [held.pop(i) for i in members]
-            out = predictor(imgs) if tile is not None else predictor.run_batch(imgs)     # (tiled: sizes are mixed)
+            if conf_writer is not None:
+                out, conf = predictor.masks_and_confidence(imgs)
+                for k, i in enumerate(members):
+                    conf_writer.submit(i, confidence_path(confidence_dir, files[i]), conf[k])
+            else:
+                out = predictor(imgs) if tile is not None else predictor.run_batch(imgs)     # (tiled: sizes are mixed)
             for k, i in enumerate(members):
                 if save:
                     writer.submit(i, output_path(output, files[i]), out[k])
@@ -164,6 +199,8 @@ def run(predictor, files: List[str], output: Optional[str], save: bool, workers:
                 logging.error("Error while processing image %s: %s", files[i], e)
                 failed.append(files[i])
                 writer.skip(i)
+                if conf_writer is not None:
+                    conf_writer.skip(i)
                 continue
             held[i] = img
             for _, members in planner.add(i, img.shape if tile is None else tile_shape(img.shape[0], img.shape[1], tile)):
@@ -171,6 +208,8 @@ def run(predictor, files: List[str], output: Optional[str], save: bool, workers:
         for _, members in planner.flush():
             finish(members)
         written = writer.close()
+        if conf_writer is not None:
+            conf_writer.close()
     return written, failed
 
 
@@ -193,13 +232,16 @@ def main(argv=None) -> int:
         logging.error("--batch-size and --workers must be at least 1")
         return 1
     # model format (predict.py:93-116); checked before anything touches the device
-    if args.model.endswith(".pt"):
-        logging.error("TorchScript models (.pt) are not supported: %s. This port runs .pth state_dicts through its HIP "
-                      "kernels; there is no TorchScript path.", args.model)
-        return 1
-    if not args.model.endswith(".pth"):
-        logging.error("Unsupported model format: %s (only .pth state_dicts are supported)", args.model)
-        return 1
+    from .utils.ensemble import is_plain_single, parse_member_spec
+    plain = is_plain_single(args.members)                             # one bare path: the one-model statements below
+    for path in (parse_member_spec(m).path for m in args.members):
+        if path.endswith(".pt"):
+            logging.error("TorchScript models (.pt) are not supported: %s. This port runs .pth state_dicts through its HIP "
+                          "kernels; there is no TorchScript path.", path)
+            return 1
+        if not path.endswith(".pth"):
+            logging.error("Unsupported model format: %s (only .pth state_dicts are supported)", path)
+            return 1
     plt = None
     if args.viz:
         try:
@@ -214,14 +256,25 @@ def main(argv=None) -> int:
         if args.classes < 2:
             raise ValueError("predict.py takes argmax(dim=1): it needs a multi-class head (--classes >= 2); binary models "
                              "are scored and dumped by unet_amd.evaluate(..., epoch_pred_dir=...)")
-        model = build_model(args.arch, args.classes, args.bilinear)
-        load_checkpoint(model, args.model, device="cpu")              # mask_values dropped (predict.py:106-108)
-        model.eval()
+        if plain:
+            model = build_model(args.arch, args.classes, args.bilinear)
+            load_checkpoint(model, args.model, device="cpu")          # mask_values dropped (predict.py:106-108)
+            model.eval()
+        else:
+            from .utils.ensemble import Ensemble
+            model = Ensemble.load(args.members, 1, args.classes, args.arch, "cpu")
+        if args.confidence_dir is not None and len(getattr(model, "members", ())) < 2:
+            raise ValueError("--confidence-dir needs an ensemble of two or more members")
     except Exception as e:
         logging.error("Failed to load the model %s: %s", args.model, e)
         return 1
-    logging.info("Model loaded: %s, %d classes, %s upscaling", args.arch, args.classes,
-                 "bilinear" if args.bilinear else "transposed conv")
+    if plain:
+        logging.info("Model loaded: %s, %d classes, %s upscaling", args.arch, args.classes,
+                     "bilinear" if args.bilinear else "transposed conv")
+    else:
+        for r in model.records:
+            logging.info("Member loaded: %s, %s, %s upscaling, weight %d", r["path"], r["arch"],
+                         "bilinear" if r["bilinear"] else "transposed conv", r["weight"])
     if not torch.cuda.is_available():
         logging.error("predict: no GPU found. This port predicts on the MI355X through its HIP kernels and has no CPU path.")
         return 2
@@ -232,8 +285,11 @@ def main(argv=None) -> int:
                                batch_invariant=args.batch_invariant, tta=args.tta, tile=args.tile)
     if args.output is not None and not args.no_save:
         os.makedirs(args.output, exist_ok=True)                       # predict.py:48
+    if args.confidence_dir is not None:
+        os.makedirs(args.confidence_dir, exist_ok=True)
     show = (lambda path, img, grey: _show(plt, path, img, grey)) if plt is not None else None
-    written, failed = run(predictor, in_files, args.output, not args.no_save, args.workers, show)
+    written, failed = run(predictor, in_files, args.output, not args.no_save, args.workers, show,
+                          **({"confidence_dir": args.confidence_dir} if args.confidence_dir is not None else {}))
     logging.info("%d of %d images predicted, %d masks written%s", len(in_files) - len(failed), len(in_files), len(written),
                  f", {len(failed)} failed" if failed else "")
     return 0

@@ -109,25 +109,26 @@ def teacher_sha256(path: str) -> str:
     return h.hexdigest()
 
 
-def _load_state(path: str) -> Dict[str, torch.Tensor]:
+def _load_state(path: str, what: str = "teacher") -> Dict[str, torch.Tensor]:
     if not os.path.isfile(path):
-        raise ValueError(f"the teacher file {path!r} does not exist")
+        raise ValueError(f"the {what} file {path!r} does not exist")
     try:
         try:
             state = torch.load(path, map_location="cpu", weights_only=True)
         except Exception:
             state = torch.load(path, map_location="cpu", weights_only=False)
     except Exception as e:
-        raise ValueError(f"the teacher file {path!r} is not a checkpoint: {e}") from None
+        raise ValueError(f"the {what} file {path!r} is not a checkpoint: {e}") from None
     if not isinstance(state, dict) or "outc.conv.weight" not in state or "inc.double_conv.0.weight" not in state:
-        raise ValueError(f"the teacher file {path!r} is not a checkpoint of this project's networks (no inc / outc weights)")
+        raise ValueError(f"the {what} file {path!r} is not a checkpoint of this project's networks (no inc / outc weights)")
     return state
 
 
-def teacher_shape(path: str) -> Dict:
+def teacher_shape(path: str, what: str = "teacher") -> Dict:
     """What the checkpoint's keys say about the teacher, read on the CPU: {'n_channels', 'n_classes', 'bilinear'} -- input
-    channels of the stem, outputs of the head, and bilinear (no transposed-conv weights) vs transposed-conv upsampling."""
-    state = _load_state(path)
+    channels of the stem, outputs of the head, and bilinear (no transposed-conv weights) vs transposed-conv upsampling.
+    `what` names the file's role in the error text (utils/ensemble.py reads its members through this)."""
+    state = _load_state(path, what)
     return {"n_channels": int(state["inc.double_conv.0.weight"].shape[1]), "n_classes": int(state["outc.conv.weight"].shape[0]),
             "bilinear": not any(k.endswith(".up.weight") for k in state)}
 
