@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Record what the inference routes ask of the C ABI and of themselves: every LIB.call launch of BatchPredictor (plain,
-batch-invariant, test-time augmentation, tiled), evaluate() and ContourPipeline on small seeded cases, the stage names their
+batch-invariant, test-time augmentation, tiled, an ensemble untiled and tiled), evaluate() of one network and of an ensemble, and
+ContourPipeline on small seeded cases, the stage names their
 `events` collect, `graph_replays`, `launch_lengths`, and sha256 digests of everything they return.
 tests/test_gpu_predict_trace.py replays the same cases (it imports CASES / run_case from this file) and requires the record of
 tests/golden/predict_call_trace_parent.json, row for row.
@@ -170,14 +171,65 @@ def _tiled():
     return prepare, run
 
 
+ENSEMBLE_SEEDS, ENSEMBLE_WEIGHTS = (3, 5), [2, 1]
+
+
+def _members(classes=3):
+    import unet_amd
+    return unet_amd.Ensemble([_model(classes, seed=s) for s in ENSEMBLE_SEEDS], weights=ENSEMBLE_WEIGHTS)
+
+
+def _ensemble():
+    def prepare():
+        return _members(), _images([((48, 48), 2), ((32, 48), 3)], 5)
+
+    def run(state):
+        import unet_amd
+        ens, images = state
+        res, facts = {}, {}
+        for tag, tta in (("plain", None), ("d4", "d4")):
+            p = unet_amd.BatchPredictor(ens, batch=4, min_area=MIN_AREA, batch_invariant=True, tta=tta)
+            p.events = []
+            first, second = p(images), p(images)                          # the second call replays graphs
+            masks, confidence = p.masks_and_confidence(images)
+            for name, got in (("first", first), ("second", second), ("classes", p.classes(images)),
+                              ("probabilities", p.probabilities(images)), ("masks", masks), ("confidence", confidence)):
+                res.update({f"{tag}.{name}.{i}": a for i, a in enumerate(got)})
+            facts[tag] = {"events": _stages(p), "graph_replays": p.graph_replays,
+                          "launch_lengths": _lengths(p, [(48, 48), (32, 48), (48, 32)])}
+        facts["levels"] = _levels(res)
+        return res, facts
+    return prepare, run
+
+
+def _ensemble_tiled():
+    def prepare():
+        return _members(), _tiled()[0]()[1]
+
+    def run(state):
+        import unet_amd
+        ens, images = state
+        res, facts = {}, {}
+        for tag, tta in (("plain", None), ("flips", "flips")):
+            p = unet_amd.BatchPredictor(ens, batch=4, min_area=MIN_AREA, tile="32,overlap=8", tta=tta)
+            p.events = []
+            for name, fn in (("call", p), ("probabilities", p.probabilities), ("confidence", p.confidence)):
+                res.update({f"{tag}.{name}.{i}": a for i, a in enumerate(fn(images))})
+            facts[tag] = {"events": _stages(p), "graph_replays": p.graph_replays, "launch_lengths": _lengths(p, [(32, 32)])}
+        facts["levels"] = _levels(res)
+        return res, facts
+    return prepare, run
+
+
 # ------------------------------------------------------------------------------------------ evaluate
-def _evaluate():
+def _evaluate(build=_model):
+    """`build(classes)`: the network (or the ensemble) that is scored."""
     def prepare():
         images = [_image(60 + k, 48, 64) for k in range(4)]
         masks = [_mask(70 + k, 48, 64) for k in range(4)]
         loader = [{"image": torch.from_numpy(np.stack([(i.astype(np.float32) / np.float32(255.0))[None] for i in images[s:s + 2]])),
                    "mask": torch.from_numpy(np.stack(masks[s:s + 2]))} for s in (0, 2)]
-        return {3: _model(3), 1: _model(1)}, loader
+        return {3: build(3), 1: build(1)}, loader
 
     def run(state):
         import unet_amd
@@ -233,7 +285,8 @@ def _pipeline():
     return prepare, run
 
 
-CASES = {"p1": _plain(False), "p2": _plain(True), "p3": _tta(), "p4": _tiled(), "e1": _evaluate(), "s1": _pipeline()}
+CASES = {"p1": _plain(False), "p2": _plain(True), "p3": _tta(), "p4": _tiled(), "p5": _ensemble(), "p6": _ensemble_tiled(),
+         "e1": _evaluate(), "e2": _evaluate(_members), "s1": _pipeline()}
 
 
 def run_case(name):

@@ -1,6 +1,7 @@
-"""The inference routes -- BatchPredictor (plain, batch-invariant, test-time augmentation, tiled), evaluate() and ContourPipeline
--- ask of the C ABI exactly what they asked at the commit tests/golden/predict_call_trace_parent.json was recorded at (5c34f76,
-before the routes shared their eval forward, launch planner and staging path): the same launches with the same arguments in the
+"""The inference routes -- BatchPredictor (plain, batch-invariant, test-time augmentation, tiled, ensembles), evaluate() and
+ContourPipeline -- ask of the C ABI exactly what they asked at the commit tests/golden/predict_call_trace_parent.json was recorded
+at (9d4a175, before views, tiles and members were composed in one place; the six cases from before ensembles existed still
+equal their record of 5c34f76): the same launches with the same arguments in the
 same order on the same streams, the same stage names in `events`, the same `graph_replays` and `launch_lengths`, and
 bit-identical results.  The cases and the record's format are those of tests/golden/make_predict_call_trace.py, which this file
 replays."""
@@ -22,7 +23,8 @@ PARENT = rec.load(os.path.join(GOLDEN, "predict_call_trace_parent.json"))      #
 
 # entry points the record must hold at least once, so that a case which falls off its route fails instead of passing trivially
 REQUIRED = ["uh_tta_views", "uh_tta_merge", "uh_tile_gather", "uh_tile_merge", "uh_predict_prepare_u8", "uh_batch_prepare",
-            "uh_logits_to_classes_u8", "uh_postprocess_masks", "uh_classes_to_grey_u8", "uh_contours_emit"]
+            "uh_logits_to_classes_u8", "uh_postprocess_masks", "uh_classes_to_grey_u8", "uh_contours_emit", "uh_ensemble_add",
+            "uh_ensemble_finish"]
 
 
 def test_the_parent_record_reaches_every_route():
@@ -34,6 +36,11 @@ def test_the_parent_record_reaches_every_route():
     replays = [f["graph_replays"] for f in (cases["p1"]["facts"], cases["p2"]["facts"], cases["p3"]["facts"],
                                             cases["p4"]["facts"]["plain"], cases["p4"]["facts"]["flips"])]
     assert all(n > 0 for n in replays), replays
+    # the ensemble routes replay their members' graphs too (p5 without views has groups of 2 and 3 at batch 4: no full launch)
+    replays = {c: sum(f["graph_replays"] for tag, f in cases[c]["facts"].items() if tag != "levels") for c in ("p5", "p6")}
+    assert all(n > 0 for n in replays.values()), replays
+    assert cases["p5"]["facts"]["d4"]["graph_replays"] > 0
+    assert all(cases["p6"]["facts"][t]["graph_replays"] > 0 for t in ("plain", "flips"))
     # the plain route cut a batch: more launches (one uh_predict_prepare_u8 each) than planned batches, three passes over the images
     p1 = cases["p1"]
     launches = [r[4] for r in p1["rows"] if r[0] == "uh_predict_prepare_u8"]
@@ -44,7 +51,9 @@ def test_the_parent_record_reaches_every_route():
     assert p2 == 3 * cases["p2"]["facts"]["planned_batches"]                     # batch-invariant: one launch per planned batch
     # the class maps are not constant, every evaluate and pipeline result is there, and the full pipeline batch is graphed (stream 1)
     assert max(p1["facts"]["levels"]) >= 2 and max(cases["p3"]["facts"]["levels"]) == 3 and max(cases["p4"]["facts"]["levels"]) >= 2
+    assert max(cases["p5"]["facts"]["levels"]) >= 2 and max(cases["p6"]["facts"]["levels"]) >= 2
     assert len(cases["e1"]["digests"]) == 16 and len(set(cases["e1"]["digests"].values())) > 8
+    assert len(cases["e2"]["digests"]) == 16 and len(set(cases["e2"]["digests"].values())) > 8
     assert len(cases["s1"]["digests"]) == 30
     assert any(r[-1] == 1 for r in cases["s1"]["rows"] if r[0] == "uh_conv1x1_fwd")
     for tag in ("default", "invariant"):

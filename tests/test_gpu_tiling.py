@@ -288,7 +288,7 @@ def test_pool_fills_the_launches():
     p = unet_amd.BatchPredictor(model, batch=4, postprocess=False, tile=_cfg(32, 8), batch_invariant=True)
     seen = []
     forward = p._forward_cut
-    p._forward_cut = lambda x, size: (seen.append((x.shape[0], tuple(size))), forward(x, size))[1]
+    p._forward_cut = lambda x, size, m: (seen.append((x.shape[0], tuple(size))), forward(x, size, m))[1]
     images = [_image(6, 70, 90), _image(7, 50, 70)]                                        # 3 x 4 and 2 x 3 tiles of 32 x 32
     both = p.classes(images)
     assert seen == [(4, (32, 32))] * 4 + [(2, (32, 32))]

@@ -89,7 +89,7 @@ def torch_merge(l0, l1, views, B):
 
 
 def torch_launch(p, arrays, views):
-    """BatchPredictor._launch_tta with the two kernels replaced by their torch-op compositions."""
+    """BatchPredictor._launch under test-time augmentation with the two kernels replaced by their torch-op compositions."""
     from unet_amd import ops
     H, W = arrays[0].shape
     B = len(arrays)
@@ -99,11 +99,11 @@ def torch_launch(p, arrays, views):
     v0, v1 = torch_views(x.permute(0, 2, 3, 1), views)
     if v1 is not None and H == W:
         n0 = v0.shape[0]
-        logits = p._forward_cut(torch.cat([v0, v1]).permute(0, 3, 1, 2), (H, W)).permute(0, 2, 3, 1)
+        logits = p._forward_cut(torch.cat([v0, v1]).permute(0, 3, 1, 2), (H, W), p._members[0]).permute(0, 2, 3, 1)
         l0, l1 = logits[:n0], logits[n0:]
     else:
-        l0 = p._forward_cut(v0.permute(0, 3, 1, 2), (H, W)).permute(0, 2, 3, 1)
-        l1 = p._forward_cut(v1.permute(0, 3, 1, 2), (W, H)).permute(0, 2, 3, 1) if v1 is not None else None
+        l0 = p._forward_cut(v0.permute(0, 3, 1, 2), (H, W), p._members[0]).permute(0, 2, 3, 1)
+        l1 = p._forward_cut(v1.permute(0, 3, 1, 2), (W, H), p._members[0]).permute(0, 2, 3, 1) if v1 is not None else None
     return p._deliver(torch_merge(l0, l1, views, B), True)
 
 

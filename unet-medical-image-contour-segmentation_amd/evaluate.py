@@ -19,9 +19,10 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .inference import finish_group, forward_step
 from .utils.dice_score import dice_coeff
 from .utils.post_process import postprocess_mask
-from .utils.tta import tta_counts, tta_mask
+from .utils.tta import tta_mask
 
 
 class _PredDump:
@@ -55,64 +56,21 @@ class _PredDump:
         self.writer.close()
 
 
-def _tta_merged(net, x, tta, sums=False, views=None):
-    """ops.tta_merge of the views of a prepared batch [n,C,H,W] under `tta` (inside evaluate's autocast).  Each view of the
-    batch is a launch of its own, of the batch's length, under the pinned plan of one image.  `views`: ops.tta_views(x, tta)
-    where the caller has built it (an ensemble builds it once for all members)."""
-    n, _, H, W = x.shape
-    k0, k1 = tta_counts(tta)
-    views0, views1 = ops.tta_views(x, tta) if views is None else views
-    with ops.plan_images(1):
-        logits0 = torch.cat([net(views0[k * n:(k + 1) * n]) for k in range(k0)])
-        logits1 = torch.cat([net(views1[k * n:(k + 1) * n]) for k in range(k1)]) if k1 else None
-    return ops.tta_merge(logits0, logits1, tta, (H, W), sums=sums)
-
-
-def _tta_classes(net, image, tta):
-    """uint8 [B,H,W]: the classes of the probabilities averaged over the views of `tta`."""
-    return _tta_merged(net, image, tta).classes
-
-
-def _tile_merged(net, image, tile, tta, sums=False, tiles=None):
-    """ops.tile_merge of the tiled prediction of a batch (inside evaluate's autocast).  The tiles go through the network
-    len(image) at a time under the pinned plan of one image; with `tta` every such launch group goes through _tta_merged and
-    the tile merge adds the views' integer sums.  `tiles`: ops.tile_gather(image, tile) where the caller has built it."""
-    B, _, H, W = image.shape
-    if tiles is None:
-        tiles = ops.tile_gather(image, tile)
-    if tta is None:
+def _pieces(net, n):
+    """The forward evaluate gives inference.forward_step (inside evaluate's autocast): `net` on pieces of `n` inputs -- each view
+    of a batch is a launch of its own, of the batch's length -- under the pinned plan of one image."""
+    def forward(x, size):
         with ops.plan_images(1):
-            src = torch.cat([net(tiles[s:s + B]) for s in range(0, tiles.shape[0], B)])
-        return ops.tile_merge(src, tile, (H, W), sums=sums)
-    src = torch.cat([_tta_merged(net, tiles[s:s + B], tta, sums=True).sums for s in range(0, tiles.shape[0], B)])
-    return ops.tile_merge(src, tile, (H, W), sum(tta_counts(tta)), sums=sums)
+            out = [net(x[s:s + n]) for s in range(0, x.shape[0], n)]
+        return out[0] if len(out) == 1 else torch.cat(out)
+    return forward
 
 
-def _tile_classes(net, image, tile, tta):
-    """uint8 [B,H,W]: the classes of the tiled prediction of a batch."""
-    return _tile_merged(net, image, tile, tta).classes
-
-
-def _ensemble_classes(ens, image, tta, tile):
-    """uint8 [B,H,W]: the classes of an ensemble's prediction of a batch (inside evaluate's autocast): per member the logits
-    (under the pinned plan of one image), the view sums of _tta_merged or (tile: the batch is larger than one tile) the tile
-    sums of _tile_merged, added by ops.ensemble_add with the member's weight; the views and the tiles are built once.  The
-    one-channel head goes through the NC = 1 rule of uh_ensemble_finish, 2 acc > T."""
-    _, _, H, W = image.shape
-    views = ops.tta_views(image, tta) if tta is not None and tile is None else None
-    tiles = ops.tile_gather(image, tile) if tile is not None else None
-    acc = den = None
-    for net, w in zip(ens.members, ens.weights):
-        if tile is not None:
-            merged = _tile_merged(net, image, tile, tta, sums=True, tiles=tiles)
-            src, den = merged.sums, merged.den
-        elif tta is not None:
-            src = _tta_merged(net, image, tta, sums=True, views=views).sums
-        else:
-            with ops.plan_images(1):
-                src = net(image)
-        acc = ops.ensemble_add(src, w, acc)
-    return ops.ensemble_finish(acc, ens.total_weight, views=1 if tta is None else sum(tta_counts(tta)), den=den).classes
+def _tile_results(net, tiles, B, tta):
+    """What one network gives for every tile of a batch, the tiles going through forward_step `B` at a time (under `tta` each
+    such chunk with views of its own).  A member's tiles all go through before the next member's."""
+    return torch.cat([r for s in range(0, tiles.shape[0], B)
+                      for r in forward_step(tiles[s:s + B], [_pieces(net, min(B, tiles.shape[0] - s))], tta)])
 
 
 @torch.inference_mode()
@@ -135,6 +93,7 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
     whole = net                                                      # what goes back into train mode at the end
     if ens is None:
         net = single_model(net)
+    members, weights = ([net], None) if ens is None else (ens.members, ens.weights)
     if tta is not None:
         tta = tta_mask(tta)
     if tile is not None:
@@ -154,14 +113,16 @@ def evaluate(net, dataloader, device, amp, epoch_pred_dir=None, postprocess=True
             mask_true = mask_true.to(device=device, dtype=torch.float32)
             tiled = tile is not None and tile_count(image.shape[2], image.shape[3], tile) > 1
             plain = tta is None and not tiled and ens is None
-            if ens is not None:
-                merged = _ensemble_classes(ens, image, tta, tile if tiled else None)
-            elif tiled:
-                merged = _tile_classes(net, image, tile, tta)
-            elif tta is None:
+            if plain:
                 mask_pred = net(image)
-            else:
-                merged = _tta_classes(net, image, tta)
+            else:                                                      # the ladder of inference.py, uint8 [B,H,W] classes
+                B, size = image.shape[0], tuple(image.shape[2:])
+                if tiled:
+                    tiles = ops.tile_gather(image, tile)
+                    results = (_tile_results(m, tiles, B, tta) for m in members)
+                else:
+                    results = forward_step(image, [_pieces(m, B) for m in members], tta, last=ens is None)
+                merged = finish_group(results, weights, tile if tiled else None, size, tta).classes
             if net.n_classes == 1:
                 mask_true = torch.div(mask_true, 2, rounding_mode="floor")                      # evaluate.py:56
                 assert mask_true.min() >= 0 and mask_true.max() <= 1, "True mask indices should be in [0, 1]"

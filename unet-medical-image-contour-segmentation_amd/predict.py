@@ -23,7 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .inference import GraphedForward, eval_forward, timed_stage
+from .inference import GraphedForward, eval_forward, finish_group, forward_step, timed_stage
 
 
 def _table(pairs) -> np.ndarray:
@@ -227,10 +227,11 @@ class LaunchPlanner:
 
 
 class _Member:
-    """What a member of an ensemble keeps to itself: its network, its weight, its launch arithmetic and its graph cache."""
+    """What a network of the predictor keeps to itself: the network, its weight in an ensemble (None: it runs alone), its
+    launch arithmetic and its graph cache."""
 
-    def __init__(self, model: torch.nn.Module, weight: int, batch: int, amp: bool, batch_invariant: bool, tta):
-        self.model, self.weight = model, int(weight)
+    def __init__(self, model: torch.nn.Module, weight: Optional[int], batch: int, amp: bool, batch_invariant: bool, tta):
+        self.model, self.weight = model, weight
         self.planner = LaunchPlanner(model, batch, amp, batch_invariant, tta)
         self._graphs: "OrderedDict[Tuple[int, int, int], object]" = OrderedDict()
         self._seen = set()
@@ -241,36 +242,44 @@ class BatchPredictor:
     mask_to_image(postprocess_mask(predict_img(model, image, device))) returns for that image (mask_to_image(predict_img(...))
     with postprocess=False).  `predictor.classes(images)` returns the class maps instead.  Images may have mixed sizes; they
     are grouped by (H, W) and run up to `batch` at a time.  A full batch of a size that has been seen before replays a
-    captured graph (at most MAX_GRAPHS are kept, least recently used first out); everything else runs un-graphed.  A batch
-    is cut into launches of the lengths `launch_lengths` allows, all lengths under `batch_invariant=True` (LaunchPlanner).
+    captured graph (at most MAX_GRAPHS are kept per network, least recently used first out); everything else runs un-graphed.
+    A batch is cut into launches of the lengths `launch_lengths` allows, all lengths under `batch_invariant=True` (LaunchPlanner).
 
-    `tta` (a mode of utils/tta.py: "hflip", "flips", "rot4", "d4"): test-time augmentation.  Every image is predicted in each
-    view of the mode and the views' probabilities are averaged before the argmax (uh_tta_views, the forward, uh_tta_merge;
-    DESIGN.md section 3 "Test-time augmentation").  `batch` stays the number of images per forward launch, so a launch group
-    holds batch // (views per launch) source images (`tta_group`); the view batches are cut by `launch_lengths` and replay
-    captured graphs like any other batch, so every view gets the logits it gets alone and the prediction of a posed image is
-    exactly the posed prediction.  `probabilities(images)` returns the averaged probabilities.  None: nothing of this runs.
+    Three options compose (inference.forward_step and inference.finish_group; DESIGN.md section 3 "How a prediction is composed"):
+      `tta`    a mode of utils/tta.py ("hflip", "flips", "rot4", "d4"): every image is predicted in each view of the mode and the
+               views' quantised probabilities are added before the argmax (uh_tta_views, the forward, uh_tta_merge);
+      `tile`   a utils.tiling.TileConfig or its spec, "512,overlap=128": every image is cut into tiles of one shape,
+               (min(size, H), min(size, W)), after the prepare of the WHOLE image (uh_tile_gather), and uh_tile_merge adds the
+               tiles' quantised probabilities, weighted by a tent over the overlap;
+      `model`  may be a utils.ensemble.Ensemble: every member runs its forward on the same staged tensor, cut by its own
+               LaunchPlanner and replaying its own graph cache, and uh_ensemble_add adds the members' sums by their weights.
+    Upload, prepare, views and gather run once per group, whatever the number of members (M) and views (V):
 
-    `tile` (a utils.tiling.TileConfig or its spec string, "512,overlap=128"): sliding-window prediction.  Every image is cut
-    into tiles of one shape, (min(size, H), min(size, W)), on the device (uh_tile_gather, after the prepare of the WHOLE image);
-    the tiles of all images of a call that share a tile shape are pooled, whatever the images' sizes, and forwarded `batch` at
-    a time through the same launch cutting and graph cache as any batch, so every launch but the last of a tile shape is full
-    and device memory holds `batch` tiles of activations plus the logits of the images in flight; uh_tile_merge adds the tiles'
-    quantised probabilities, weighted by a tent over the overlap, as integers and takes the first maximum (DESIGN.md section 3
-    "Tiled prediction").  Post-processing and grey coding run on the whole-image map as ever.  An image that fits in one tile
-    is that tile and gets the bits of the untiled path.  With `tta`, every chunk of `tta_group` tiles goes through the views,
-    the forward and uh_tta_merge, and the tile merge adds the views' integer sums; the tile origins are not mirror-symmetric,
-    so a posed image is NOT promised the posed prediction here.  None: nothing of this runs.
+      tta  tile  members   per forward step                                     per image group
+      -    -     1         forward                                              logits_to_classes_u8
+      yes  -     1         views, forward(s), tta_merge: classes / probs        -
+      any  -     M         views once; per member forward (+ tta_merge: sums)   per member ensemble_add; ensemble_finish(V)
+      -    yes   1         forward, the logits kept                             tile_merge: classes / probs (*)
+      yes  yes   1         views, forward(s), tta_merge: sums                   tile_merge(V): classes / probs
+      any  yes   M         views once; per member as the two rows above         per member tile_merge: sums, ensemble_add;
+                                                                                ensemble_finish(V, den)
+      (*) the classes of an image that is one tile: logits_to_classes_u8, the untiled statement
 
-    `model` may be a utils.ensemble.Ensemble (DESIGN.md section 3 "Ensembles").  Upload, prepare, uh_tta_views and uh_tile_gather
-    run once per batch; every member runs its forward on the same staged tensor, cut by its own LaunchPlanner and replaying its
-    own graph cache (MAX_GRAPHS each); its logits -- under `tta` its view sums, under `tile` its tile sums -- go through
-    uh_ensemble_add with the member's weight, and uh_ensemble_finish takes the first maximum of the integer sums, so the masks
-    depend on no order of the members.  `probabilities(images)` then also works without `tta` or `tile`, and
-    `confidence(images)` returns floor(255 max / sum) of the summed probabilities per pixel.  A bare module, or an Ensemble of
-    one member, runs the one-model statements unchanged."""
+    Everything after the quantiser is an integer sum and the last rung takes the first maximum, so the masks depend on no order
+    of views, tiles or members.  Post-processing and grey coding run on the whole-image class map as ever.
+    Untiled, a launch group is a cut piece of the batch for one plain model and `tta_group` source images otherwise: `batch`
+    stays the number of network inputs per forward launch, the view batches are cut by `launch_lengths` and replay graphs like
+    any batch, so every view gets the logits it gets alone and the prediction of a posed image is exactly the posed prediction.
+    Tiled, the tiles of all images of a call that share a tile shape are pooled, whatever the images' sizes, and forwarded
+    `tile_chunk` at a time, so every forward step but the last of a tile shape is full and device memory holds `batch` tiles of
+    activations plus the results of the images in flight.  An image that fits in one tile is that tile and, without `tta`, gets
+    the bits of the untiled path; the tile origins are not mirror-symmetric, so under `tile` a posed image is NOT promised the
+    posed prediction.
+    `probabilities(images)` returns the averaged probabilities of any row but the first, `confidence(images)` floor(255 max / sum)
+    of an ensemble's summed probabilities per pixel.  A bare module, or an Ensemble of one member, runs the one-model rows."""
 
     MAX_GRAPHS = 4
+    tta = tile = ensemble = None              # what a predictor has that was built with none of them
 
     def __init__(self, model: torch.nn.Module, batch: int = 8, postprocess: bool = True, amp: bool = True, device=None,
                  min_area: int = 15000, morph_kernel_size: int = 3, batch_invariant: bool = False, tta=None, tile=None):
@@ -294,21 +303,15 @@ class BatchPredictor:
             raise RuntimeError("BatchPredictor needs an MI355X: the HIP path has no CPU fallback")
         from .utils.ensemble import single_model
         solo = single_model(model)
-        self.ensemble = model.to(self.device).eval() if solo is None else None     # None: one network, today's statements
+        self.ensemble = model.to(self.device).eval() if solo is None else None     # None: one network, the one-model rows
         self.model = solo.to(self.device).eval() if solo is not None else self.ensemble
         self.batch, self.postprocess, self.amp = int(batch), bool(postprocess), bool(amp)
         self.min_area, self.ksize = int(min_area), int(morph_kernel_size)
         self._lut = torch.from_numpy(GREY_CLASSES.copy()).to(self.device)
         self._flags = torch.empty(self.batch, dtype=torch.int32, device=self.device)
-        self._graphs: "OrderedDict[Tuple[int, int, int], object]" = OrderedDict()
-        self._seen = set()
-        if self.ensemble is None:
-            self.planner = LaunchPlanner(self.model, self.batch, self.amp, self.batch_invariant, self.tta)
-            self._members: List[_Member] = []
-        else:
-            self._members = [_Member(m, w, self.batch, self.amp, self.batch_invariant, self.tta)
-                             for m, w in zip(self.ensemble.members, self.ensemble.weights)]
-            self.planner = self._members[0].planner
+        nets = [(self.model, None)] if solo is not None else zip(self.ensemble.members, self.ensemble.weights)
+        self._members = [_Member(m, w, self.batch, self.amp, self.batch_invariant, self.tta) for m, w in nets]
+        self.planner = self._members[0].planner
         self._pin_in: Optional[torch.Tensor] = None
         self._pin_out: Optional[torch.Tensor] = None
         self._upload_done = torch.cuda.Event()                        # recorded behind every upload out of _pin_in
@@ -322,11 +325,16 @@ class BatchPredictor:
     def launch_lengths(self, H: int, W: int) -> List[int]:
         return self.planner.launch_lengths(H, W)
 
+    @property
+    def _graphs(self):
+        """The graph cache of the first network (the only one of a bare model): kept by the member, read here as `planner` is."""
+        return self._members[0]._graphs
+
     def tta_group(self, H: int, W: int) -> int:
-        return min([self.planner.tta_group(H, W)] + [m.planner.tta_group(H, W) for m in self._members])
+        return min(m.planner.tta_group(H, W) for m in self._members)
 
     def tile_chunk(self, th: int, tw: int) -> int:
-        return min([self.planner.tile_chunk(th, tw)] + [m.planner.tile_chunk(th, tw) for m in self._members])
+        return min(m.planner.tile_chunk(th, tw) for m in self._members)
 
     def _pinned(self, which: str, nbytes: int) -> torch.Tensor:
         buf = getattr(self, which)
@@ -357,9 +365,8 @@ class BatchPredictor:
         self._mark("prepare", ops.predict_prepare_u8, img, x, flags)
         return x
 
-    def _forward(self, x: torch.Tensor, size: Tuple[int, int], m=None) -> torch.Tensor:
-        """`m`: the ensemble member whose network, planner and graph cache serve the call (None: the predictor's own)."""
-        m = self if m is None else m
+    def _forward(self, x: torch.Tensor, size: Tuple[int, int], m: _Member) -> torch.Tensor:
+        """One launch of the network of `m`, through its planner and graph cache."""
         full = m.planner.launch_lengths(*size)[-1]                     # the longest launch this size allows
         size = (x.shape[0],) + tuple(size)
         if x.shape[0] == full and size in m._seen:
@@ -382,27 +389,40 @@ class BatchPredictor:
         H, W = arrays[0].shape
         if self.tile is not None:
             return np.stack(self._run_tiled(arrays, grey, probs, conf))
-        if self.ensemble is not None:
-            g = self.batch if self.tta is None else self.tta_group(H, W)
-            out = [self._launch_ensemble(arrays[s:s + g], grey, probs, conf) for s in range(0, len(arrays), g)]
-        elif self.tta is not None:
-            g = self.tta_group(H, W)
-            out = [self._launch_tta(arrays[s:s + g], grey, probs) for s in range(0, len(arrays), g)]
+        if self.ensemble is None and self.tta is None:
+            groups = self.planner.cut(len(arrays), H, W)               # one plain model: a group is a launch
         else:
-            out, s = [], 0
-            for b in self.planner.cut(len(arrays), H, W):
-                out.append(self._launch(arrays[s:s + b], grey))
-                s += b
+            g = self.batch if self.tta is None else self.tta_group(H, W)
+            groups = [min(g, len(arrays) - s) for s in range(0, len(arrays), g)]
+        more = {k: True for k, v in (("probs", probs), ("conf", conf)) if v}     # masks alone are _launch(arrays, grey), as ever
+        out, s = [], 0
+        for b in groups:
+            out.append(self._launch(arrays[s:s + b], grey, **more))
+            s += b
         return out[0] if len(out) == 1 else np.concatenate(out)
 
-    def _launch(self, arrays: List[np.ndarray], grey: bool) -> np.ndarray:
-        H, W = arrays[0].shape
+    def _forwards(self):
+        """Per member the forward that inference.forward_step calls: _forward_cut through that member's planner and graphs."""
+        return [lambda x, size, m=m: self._forward_cut(x, size, m) for m in self._members]
+
+    def _launch(self, arrays: List[np.ndarray], grey: bool, probs: bool = False, conf: bool = False) -> np.ndarray:
+        """One launch group of equally sized images: stage, forward step, finish, deliver."""
         with torch.cuda.device(self.device):
-            logits = self._mark("forward", self._forward, self._stage(arrays), (H, W))
-            if tuple(logits.shape[-2:]) != (H, W):
-                raise RuntimeError(f"the network returned {tuple(logits.shape[-2:])} for a {(H, W)} input")     # predict.py:26 is dead at scale 1
-            cls = self._mark("classes", ops.logits_to_classes_u8, logits)
-            return self._deliver(cls, grey)
+            results = forward_step(self._stage(arrays), self._forwards(), self.tta, last=self.ensemble is None, probs=probs,
+                                   mark=self._mark)
+            return self._finish(results, None, arrays[0].shape, grey, probs, conf)
+
+    def _finish(self, results, tile, size: Tuple[int, int], grey: bool, probs: bool, conf: bool) -> np.ndarray:
+        """The members' results for a group of images -> uint8 [B,H,W] on the host, (probs) float32 [B,NC,H,W], or (conf; an
+        ensemble) uint8 [B,2,H,W]: the masks and the confidence maps."""
+        weights = None if self.ensemble is None else [m.weight for m in self._members]
+        out = finish_group(results, weights, tile, size, self.tta, probs=probs, confidence=conf, mark=self._mark)
+        if probs:
+            return out.probs.permute(0, 3, 1, 2).cpu().numpy()
+        masks = self._deliver(out.classes, grey)
+        if conf:
+            return np.stack([masks, out.confidence.cpu().numpy()], axis=1)
+        return masks
 
     def _deliver(self, cls: torch.Tensor, grey: bool) -> np.ndarray:
         """Class maps uint8 [B,H,W] on the device -> post-processed, grey-coded, on the host."""
@@ -417,74 +437,12 @@ class BatchPredictor:
         torch.cuda.current_stream().synchronize()
         return out.numpy().copy()
 
-    # ---------------------------------------------------------------- test-time augmentation
-    def _forward_cut(self, x: torch.Tensor, size: Tuple[int, int], m=None) -> torch.Tensor:
-        """_forward for a view batch of any length, in as few launches as launch_lengths allows."""
-        cut = (self if m is None else m).planner.cut(x.shape[0], *size)
+    def _forward_cut(self, x: torch.Tensor, size: Tuple[int, int], m: _Member) -> torch.Tensor:
+        """_forward for a batch of any length (views, tiles), in as few launches as launch_lengths allows."""
+        cut = m.planner.cut(x.shape[0], *size)
         if len(cut) == 1:
             return self._forward(x, size, m)
         return torch.cat([self._forward(part, size, m).clone() for part in x.split(cut)])   # (a replayed graph returns its static buffer)
-
-    def _tta_logits(self, x: torch.Tensor, H: int, W: int, m=None, views=None):
-        """The logits of the views of a prepared batch [B,C,H,W]: (untransposed views, transposed views or None).  `views`:
-        the result of ops.tta_views(x) when the caller has built it (an ensemble builds it once for all members)."""
-        v0, v1 = self._mark("views", ops.tta_views, x, self.tta) if views is None else views
-        if v1 is not None and H == W:                                  # one view shape: one forward
-            l0, l1 = self._mark("forward", self._forward_cut, ops.tta_joint_views(v0, v1), (H, W), m), None
-        else:
-            l0 = self._mark("forward", self._forward_cut, v0, (H, W), m)
-            l1 = self._mark("forward", self._forward_cut, v1, (W, H), m) if v1 is not None else None
-        if tuple(l0.shape[-2:]) != (H, W) or (l1 is not None and tuple(l1.shape[-2:]) != (W, H)):
-            raise RuntimeError(f"the network returned {tuple(l0.shape[-2:])} for a {(H, W)} input")
-        return l0, l1
-
-    def _launch_tta(self, arrays: List[np.ndarray], grey: bool, probs: bool = False) -> np.ndarray:
-        """One launch group under test-time augmentation -> uint8 [B,H,W] as _launch, or (probs) float32 [B,NC,H,W]."""
-        H, W = arrays[0].shape
-        with torch.cuda.device(self.device):
-            l0, l1 = self._tta_logits(self._stage(arrays), H, W)
-            merged = self._mark("merge", ops.tta_merge, l0, l1, self.tta, (H, W), probs=probs)
-            if probs:
-                return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
-            return self._deliver(merged.classes, grey)
-
-    # ---------------------------------------------------------------- ensembles
-    def _views(self) -> int:
-        if self.tta is None:
-            return 1
-        from .utils.tta import tta_counts
-        return sum(tta_counts(self.tta))
-
-    def _ensemble_deliver(self, acc: torch.Tensor, den, grey: bool, probs: bool, conf: bool) -> np.ndarray:
-        """The members' summed results -> uint8 [B,H,W] as _launch, (probs) float32 [B,NC,H,W], or (conf) uint8 [B,2,H,W]: the
-        masks as _launch returns them and the confidence maps."""
-        merged = self._mark("ensemble_finish", ops.ensemble_finish, acc, self.ensemble.total_weight, views=self._views(), den=den,
-                            probs=probs, confidence=conf)
-        if probs:
-            return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
-        masks = self._deliver(merged.classes, grey)
-        if conf:
-            return np.stack([masks, merged.confidence.cpu().numpy()], axis=1)
-        return masks
-
-    def _launch_ensemble(self, arrays: List[np.ndarray], grey: bool, probs: bool = False, conf: bool = False) -> np.ndarray:
-        """One launch group of an ensemble: one upload, one prepare and (under `tta`) one set of views; per member the forward
-        on that tensor and uh_ensemble_add of its logits or of its view sums."""
-        H, W = arrays[0].shape
-        with torch.cuda.device(self.device):
-            x = self._stage(arrays)
-            views = self._mark("views", ops.tta_views, x, self.tta) if self.tta is not None else None
-            acc = None
-            for m in self._members:
-                if self.tta is None:
-                    src = self._mark("forward", self._forward_cut, x, (H, W), m)
-                    if tuple(src.shape[-2:]) != (H, W):
-                        raise RuntimeError(f"the network returned {tuple(src.shape[-2:])} for a {(H, W)} input")
-                else:
-                    l0, l1 = self._tta_logits(x, H, W, m, views)
-                    src = self._mark("merge", ops.tta_merge, l0, l1, self.tta, (H, W), sums=True).sums
-                acc = self._mark("ensemble_add", ops.ensemble_add, src, m.weight, acc)
-            return self._ensemble_deliver(acc, None, grey, probs, conf)
 
     # ---------------------------------------------------------------- tiled prediction
     def _prepare_tiles(self, arrays: List[np.ndarray]) -> torch.Tensor:
@@ -493,67 +451,19 @@ class BatchPredictor:
             return self._mark("gather", ops.tile_gather, self._stage(arrays), self.tile)
 
     def _tile_forward(self, tiles: torch.Tensor, shape: Tuple[int, int]) -> torch.Tensor:
-        """One forward step of the tiled flow: the logits [n,NC,th,tw] of the tiles, or under test-time augmentation the
-        int32 sums [n,th,tw,NC] over their views."""
-        th, tw = shape
-        if self.ensemble is not None:
-            return self._tile_forward_ensemble(tiles, shape)
+        """One forward step of the tiled flow, in a tensor that outlives the next step: the logits [n,NC,th,tw] of the tiles,
+        or under test-time augmentation the int32 sums [n,th,tw,NC] over their views; for an ensemble the members' side by
+        side in dimension 1, [n,M,...]."""
         with torch.cuda.device(self.device):
-            if self.tta is None:
-                logits = self._mark("forward", self._forward_cut, tiles, shape)
-                if tuple(logits.shape[-2:]) != (th, tw):
-                    raise RuntimeError(f"the network returned {tuple(logits.shape[-2:])} for a {(th, tw)} input")
-                return logits.clone()                                  # (a replayed graph returns its static buffer)
-            l0, l1 = self._tta_logits(tiles, th, tw)
-            return self._mark("merge", ops.tta_merge, l0, l1, self.tta, shape, sums=True).sums
-
-    def _tile_forward_ensemble(self, tiles: torch.Tensor, shape: Tuple[int, int]) -> torch.Tensor:
-        """_tile_forward of every member on the same tiles, the members side by side in dimension 1: logits [n,M,NC,th,tw],
-        or under test-time augmentation (the views built once) int32 sums [n,M,th,tw,NC]."""
-        th, tw = shape
-        with torch.cuda.device(self.device):
-            views = self._mark("views", ops.tta_views, tiles, self.tta) if self.tta is not None else None
-            out = []
-            for m in self._members:
-                if self.tta is None:
-                    logits = self._mark("forward", self._forward_cut, tiles, shape, m)
-                    if tuple(logits.shape[-2:]) != (th, tw):
-                        raise RuntimeError(f"the network returned {tuple(logits.shape[-2:])} for a {(th, tw)} input")
-                    out.append(logits)
-                else:
-                    l0, l1 = self._tta_logits(tiles, th, tw, m, views)
-                    out.append(self._mark("merge", ops.tta_merge, l0, l1, self.tta, shape, sums=True).sums)
-            return torch.stack(out, dim=1)                              # (copies: a replayed graph returns its static buffer)
-
-    def _tile_finish_ensemble(self, src: torch.Tensor, H: int, W: int, grey: bool, probs: bool, conf: bool) -> np.ndarray:
-        """The members' results for every tile of a batch of H x W images: per member uh_tile_merge to its 64-bit sums (the
-        weights `den` are the same for all), uh_ensemble_add, then the finish as for any ensemble."""
-        with torch.cuda.device(self.device):
-            acc = den = None
-            for k, m in enumerate(self._members):
-                merged = self._mark("tile_merge", ops.tile_merge, src[:, k], self.tile, (H, W), self._views(), sums=True)
-                den = merged.den
-                acc = self._mark("ensemble_add", ops.ensemble_add, merged.sums, m.weight, acc)
-            return self._ensemble_deliver(acc, den, grey, probs, conf)
+            out = list(forward_step(tiles, self._forwards(), self.tta, mark=self._mark))
+            if self.ensemble is not None:
+                return torch.stack(out, dim=1)                          # (copies: a replayed graph returns its static buffer)
+            return out[0].clone() if self.tta is None else out[0]      # (the same; the view sums are a fresh tensor)
 
     def _tile_finish(self, src: torch.Tensor, H: int, W: int, grey: bool, probs: bool, conf: bool = False) -> np.ndarray:
-        """The results of every tile of a batch of H x W images -> uint8 [B,H,W] as _launch, or (probs) float32 [B,NC,H,W]."""
-        from .utils.tiling import tile_count
-        if self.ensemble is not None:
-            return self._tile_finish_ensemble(src, H, W, grey, probs, conf)
-        views = 1
-        if self.tta is not None:
-            from .utils.tta import tta_counts
-            views = sum(tta_counts(self.tta))
+        """The results of _tile_forward for every tile of a batch of H x W images -> what _finish returns."""
         with torch.cuda.device(self.device):
-            if probs:
-                merged = self._mark("tile_merge", ops.tile_merge, src, self.tile, (H, W), views, probs=True)
-                return merged.probs.permute(0, 3, 1, 2).cpu().numpy()
-            if self.tta is None and tile_count(H, W, self.tile) == 1:
-                cls = self._mark("classes", ops.logits_to_classes_u8, src)     # the tile is the image: the untiled statement
-            else:
-                cls = self._mark("tile_merge", ops.tile_merge, src, self.tile, (H, W), views).classes
-            return self._deliver(cls, grey)
+            return self._finish([src] if self.ensemble is None else src.unbind(1), self.tile, (H, W), grey, probs, conf)
 
     def _run_tiled(self, arrays: List[np.ndarray], grey: bool, probs: bool = False, conf: bool = False) -> List[np.ndarray]:
         """Images of any sizes -> their results in input order.  The tiles of all images that share a tile shape are pooled:
@@ -618,14 +528,14 @@ class BatchPredictor:
         """float32 [NC,H,W] per image: the mean over the views of the softmax probabilities (multiples of 2^-24 / V); under
         `tile` the weighted mean over the covering tiles (and their views), (float)(sum / (den V 2^24)); for an ensemble the
         weighted mean over its members of either, or of the members' plain probabilities, (float)(sum / (den V 2^24 weights))."""
-        if self.tta is None and self.tile is None and getattr(self, "ensemble", None) is None:
+        if self.tta is None and self.tile is None and self.ensemble is None:
             raise RuntimeError("probabilities() returns the mean over the views of test-time augmentation (tta=...) or over the "
                                "covering tiles of tiled prediction (tile=...): build the predictor with one of them")
         return self._run(images, False, probs=True)
 
     def masks_and_confidence(self, images, grey: bool = True) -> Tuple[List[np.ndarray], List[np.ndarray]]:
         """(what predictor(images) returns, what confidence(images) returns) from one pass over the images."""
-        if getattr(self, "ensemble", None) is None:
+        if self.ensemble is None:
             raise RuntimeError("confidence() measures how far the members of an ensemble agree: build the predictor with a "
                                "utils.ensemble.Ensemble of two or more members")
         both = self._run(images, grey, conf=True)
