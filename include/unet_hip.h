@@ -868,6 +868,26 @@ int uh_crop_select(const uh_crop_item* items, int B, int size, uint64_t class_ma
 int uh_crop_gather(const uh_crop_item* items, int B, int C, int dt, int size, const int32_t* origin, void* image_out, int ld_out,
                    int64_t* labels_out, uh_stream stream);
 
+/* ---- device-resident dataset cache: cut a batch from cached entries  (csrc/cache.hip; the reference has none) ---------------
+ * uh_cache_gather_u8: image_out DEVICE uint8 [B][image_bytes] and mask_out DEVICE uint8 [B][mask_bytes], both contiguous, each
+ *   nullable (one at least): item b of an output is a copy of the image_bytes (mask_bytes) bytes at row b's pointer.  Rows may
+ *   repeat and come in any order.  The item table is HOST memory, one row per batch item: every row is checked before any
+ *   launch and the rows travel by value in the kernel arguments, 32 per launch, so no call copies to the device, allocates or
+ *   synchronises with the host.  Without image_out (mask_out) the rows' `image` (`mask`) may be null and its length is not read.
+ * Sources: every pointer is 16-byte aligned and READABLE UP TO ITS LENGTH ROUNDED UP TO 16: the kernel reads whole aligned
+ *   16-byte units, so it may read up to 15 bytes of padding behind a source and nothing beyond them.  The cache pads every
+ *   entry of its arena to a multiple of 16 bytes to guarantee this (utils/dataset_cache.py, plan_entries).
+ * Destinations: the output bases are 16-byte aligned; item b starts at b * bytes, aligned or not.  Any length >= 1 (at most
+ *   2^40) is copied exactly: no byte outside [out, out + B * bytes) is written.  Aligned 16-byte units of a destination are
+ *   written with 16-byte stores, the fewer than 16 bytes in front of and behind them one by one.
+ * Null or misaligned pointers, B < 1, both outputs null, or a zero length with a non-null output: UH_EINVAL before any launch. */
+typedef struct uh_cache_item {
+    const uint8_t* image;              /* DEVICE uint8 [image_bytes], 16-byte aligned, padded to a multiple of 16; or NULL */
+    const uint8_t* mask;               /* DEVICE uint8 [mask_bytes], likewise */
+} uh_cache_item;
+int uh_cache_gather_u8(const uh_cache_item* items, int B, size_t image_bytes, size_t mask_bytes, uint8_t* image_out,
+                       uint8_t* mask_out, uh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

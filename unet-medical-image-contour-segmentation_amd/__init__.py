@@ -21,6 +21,7 @@ from .utils.post_process import postprocess_mask, remove_internal_regions  # noq
 from .utils.tta import tta_mask, tta_view_shape, tta_source_position  # noqa: F401
 from .utils.tiling import TileConfig, parse_tile_spec, tile_grid  # noqa: F401
 from .utils.crop import CropConfig, BatchCrop  # noqa: F401
+from .utils.dataset_cache import DatasetCache, DatasetCacheTooLarge, plan_entries  # noqa: F401
 from .utils.ensemble import Ensemble, MemberSpec, parse_member_spec  # noqa: F401
 from .inference import GraphedForward  # noqa: F401
 from .utils.raw2png import read_raw, window_level  # noqa: F401

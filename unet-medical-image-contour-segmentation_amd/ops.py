@@ -10,6 +10,7 @@ import ctypes
 import os
 from typing import NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 from torch.autograd import Function
 
@@ -1910,6 +1911,47 @@ def crop_gather(images: Optional[Sequence[torch.Tensor]], labels: Optional[Seque
         LIB.call("uh_crop_gather", table.ctypes.data, B, C, dt, size, origins.data_ptr(), _p(out), ld_out, _p(lab), _stream())
     del keep
     return (out[..., :C].permute(0, 3, 1, 2) if out is not None else None), lab
+
+
+# ----------------------------------------------------------------------------- dataset cache (csrc/cache.hip)
+def cache_gather(rows, image_bytes: int, mask_bytes: int, want_image: bool = True,
+                 want_mask: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """One batch cut from cached entries: rows = one (image, mask) pair per batch item, contiguous uint8 device tensors whose
+    storage starts 16-byte aligned and is readable up to the length rounded up to 16 (utils/dataset_cache.py pads its arena so);
+    rows may repeat.  -> (uint8 [B, image_bytes] or None, uint8 [B, mask_bytes] or None): the first image_bytes / mask_bytes bytes
+    of every row's tensors, in one launch per 32 rows.  A side that is not wanted may be None in the rows.  A pure copy."""
+    rows = list(rows)
+    if not rows:
+        raise ValueError("cache_gather needs at least one row")
+    if not (want_image or want_mask):
+        raise ValueError("cache_gather: want_image and want_mask are both False")
+    image_bytes, mask_bytes = int(image_bytes), int(mask_bytes)
+    table = np.zeros((len(rows), 2), dtype=np.uint64)                    # include/unet_hip.h: uh_cache_item (16 bytes)
+    dev = None
+    for b, row in enumerate(rows):
+        if len(row) != 2:
+            raise ValueError(f"cache_gather: rows[{b}] is not an (image, mask) pair")
+        for col, (t, want, need, what) in enumerate(zip(row, (want_image, want_mask), (image_bytes, mask_bytes), ("image", "mask"))):
+            if not want:
+                continue
+            if t is None:
+                raise RuntimeError(f"cache_gather: rows[{b}] has no {what}")
+            _require_gpu(t, f"rows[{b}] {what}")
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise RuntimeError(f"cache_gather: rows[{b}] {what} must be a contiguous uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+            if need < 1 or t.numel() < need:
+                raise RuntimeError(f"cache_gather: {what}_bytes={need} does not fit rows[{b}] {what} of {t.numel()} bytes")
+            if dev is None:
+                dev = t.device
+            elif t.device != dev:
+                raise RuntimeError(f"cache_gather: rows[{b}] {what} is on {t.device}, the first row on {dev}")
+            table[b, col] = t.data_ptr()
+    B = len(rows)
+    with torch.cuda.device(dev):
+        image = torch.empty((B, image_bytes), dtype=torch.uint8, device=dev) if want_image else None
+        mask = torch.empty((B, mask_bytes), dtype=torch.uint8, device=dev) if want_mask else None
+        LIB.call("uh_cache_gather_u8", table.ctypes.data, B, image_bytes, mask_bytes, _p(image), _p(mask), _stream())
+    return image, mask
 
 
 # ----------------------------------------------------------------------------- contour metrics (csrc/contour_metrics.hip)

@@ -4,7 +4,7 @@
                              [--model UNet_S] [--data-root DIR] [--checkpoint-dir DIR] [--workers 8] [--seed N]
                              [--pred-dir DIR] [--metrics] [--augment [SPEC]] [--elastic [SPEC]] [--surface-loss [SPEC]]
                              [--loss [SPEC]] [--ema [DECAY[,warmup=N]]] [--save-state] [--resume STATE]
-                             [--crop [SPEC]] [--tile [SPEC]] [--distill SPEC] [--optimizer SPEC]
+                             [--crop [SPEC]] [--tile [SPEC]] [--distill SPEC] [--optimizer SPEC] [--cache [limit=GiB]]
 
 It reads data_root/{imgs,masks}/{train,val} (BasicDataset, x4 quarter-turn augmentation) and runs the epoch loop of
 train.py:29-220, restated literally ("reproduced, not fixed"):
@@ -61,6 +61,13 @@ train.py:29-220, restated literally ("reproduced, not fixed"):
     [,momentum=M][,wd=W]" (defaults: the reference's values).  The learning rate stays -l and the loop's schedule drives it under
     every rule; gradient clipping, --ema, --save-state and --resume work as with the default.  A malformed spec ends the
     command with status 2; one log line names the canonical spec;
+  - --cache [limit=GiB] (default: off) keeps the decoded training and validation files on the device (utils/dataset_cache.py,
+    csrc/cache.hip): every file is decoded once, before the first epoch, and every batch of every epoch -- the in-loop
+    evaluations' too -- is cut from that arena with one launch instead of being decoded again.  The batches are the same bits,
+    so it is NOT a determining argument: it is not recorded by --save-state and --resume takes a run with or without it.
+    limit is the most a set may take, in GiB (default: half of the device memory that is free).  One log line per set gives
+    its files, MiB and build seconds; a set that is over the limit or does not decode to 8 bits is served as without the
+    option, with a warning that says why.  A malformed spec ends the command with status 2;
   - --save-state writes checkpoint_dir/train_state.pth at the end of every epoch (a temporary file renamed over it): model
     and optimizer state (the rule's buffers and step count, the moving average and its update count), epoch, global step, lr, the
     loader's and the augmenter's seeds, and a record of the arguments that determine the run (RECORDED);
@@ -194,6 +201,50 @@ def _crop_arg(text: str):
         raise argparse.ArgumentTypeError(f"bad --crop {text!r}: {e}") from None
 
 
+class CacheSpec(NamedTuple):
+    """--cache: the most one dataset's cache may take, in bytes (None: half of the free device memory)."""
+    limit_bytes: Optional[int] = None
+
+
+def parse_cache_spec(text: str) -> CacheSpec:
+    """"" or "limit=GiB" -> CacheSpec; ValueError names what is wrong."""
+    text = str(text).strip()
+    if not text:
+        return CacheSpec()
+    key, eq, val = (t.strip() for t in text.partition("="))
+    if key != "limit" or not eq or not val:
+        raise ValueError(f"{text!r} is not limit=GiB")
+    try:
+        gib = float(val)
+    except ValueError:
+        raise ValueError(f"limit {val!r} is not a number") from None
+    if not math.isfinite(gib) or gib <= 0.0:
+        raise ValueError(f"limit {val!r} must be finite and > 0")
+    return CacheSpec(int(gib * (1 << 30)))
+
+
+def _cache_arg(text: str) -> CacheSpec:
+    try:
+        return parse_cache_spec(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"bad --cache {text!r}: {e}") from None
+
+
+def build_cache(ds, what: str, spec: CacheSpec, device, workers: int, log=None):
+    """The DatasetCache of `ds` under --cache, logged in one line, or None -- with a warning naming the reason -- for a set that is
+    over the limit or does not decode to 8 bits: that set is then served through the uncached path."""
+    from .utils.dataset_cache import DatasetCache, DatasetCacheTooLarge
+    try:
+        cache = DatasetCache(ds, device=device, workers=workers, limit_bytes=spec.limit_bytes)
+    except (DatasetCacheTooLarge, TypeError) as e:
+        logging.warning(f"Dataset cache ({what}): not cached, served through the decode threads: {e}")
+        return None
+    if log:
+        log(f"Dataset cache ({what}): {cache.entries} files, {cache.nbytes / (1 << 20):.1f} MiB on the device, built in "
+            f"{cache.build_seconds:.2f} s")
+    return cache
+
+
 def _distill_arg(text: str):
     from .utils.distill import DistillConfig
     try:
@@ -314,6 +365,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="The update rule of the fused optimizer pass: 'adamw[,betas=B1/B2][,eps=E][,wd=W]', "
                         "'sgd[,momentum=M][,nesterov|plain][,wd=W]' or 'rmsprop[,alpha=A][,eps=E][,momentum=M][,wd=W]'; the learning "
                         "rate stays -l (default: off, the reference's RMSprop)")
+    p.add_argument("--cache", nargs="?", const=CacheSpec(), default=None, type=_cache_arg, metavar="limit=GiB",
+                   help="Decode every training and validation file once and keep the pixels on the device; every batch is cut "
+                        "from there.  limit: the most one set may take, in GiB (default: half of the free device memory).  The "
+                        "batches are the same bits, so --resume takes a run with or without it (default: off)")
     p.add_argument("--save-state", dest="save_state", action="store_true", default=False,
                    help=f"Write checkpoint_dir/{STATE_FILE} after every epoch: everything --resume needs (default: off)")
     p.add_argument("--resume", default=None, metavar="STATE",
@@ -358,7 +413,7 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                  train_loader=None, log=None, pred_dir: Optional[str] = None, metrics: bool = False,
                  augment=None, surface: Optional[SurfaceSpec] = None, elastic=None, ema=None, save_state: bool = False,
                  resume: Optional[Dict] = None, record: Optional[Dict] = None, loss=None, crop=None, tile=None,
-                 distill=None, optimizer=None) -> List[Dict]:
+                 distill=None, optimizer=None, cache: Optional[CacheSpec] = None) -> List[Dict]:
     """The epoch loop of train.py:29-220 over directory datasets.  Returns one record per epoch: the summed loss, the
     last evaluation's three Dice figures (None in an epoch without one), the lr, the training images/s of the epoch (train
     images over the epoch's wall time without its evaluations) and the seconds spent evaluating.
@@ -379,6 +434,8 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     record gains the epoch's mean "kd" and "kd_agree", and one line per epoch logs them.  Evaluations and checkpoints hold the
     student alone.
     `optimizer`: an OptimConfig or a spec string: the rule of the fused optimizer pass (None: RMSprop as ever); one line logs it.
+    `cache`: a CacheSpec: both loaders are served from a DatasetCache of their set (build_cache; a set that cannot be cached is
+    served as without it).  The batches are the same bits, so nothing of it is recorded.
     `save_state`: write checkpoint_dir/train_state.pth after every epoch, holding `record` (run_record) as its "args".
     `resume`: such a state (load_resume_state); the model must already hold its weights.  Optimizer state, lr, counters
     and the seeds are restored and the loop continues with the epoch after the saved one: only those epochs are returned."""
@@ -392,6 +449,10 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
                                          seed=seed if resume is None else resume["loader_seed"], workers=workers, device=device)
     elif resume is not None:
         train_loader.seed = int(resume["loader_seed"])
+    built = []                                                               # the caches of this call, closed at its end
+    if cache is not None and train_loader.cache is None and not train_loader.host_rescale:
+        train_loader.cache = build_cache(train_set, "training", cache, device, workers, log)
+        built.append(train_loader.cache)
     if crop is not None:
         from .utils.crop import BatchCrop
         if not isinstance(crop, BatchCrop):
@@ -411,7 +472,10 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
         if log:
             log(f"Training augmentation (seed {augment.seed}): {augment.config.spec()}"
                 + (f"; elastic {augment.elastic.spec()}" if augment.elastic is not None else ""))
-    val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device)
+    if cache is not None:
+        built.append(build_cache(val_set, "validation", cache, device, workers, log))
+    val_loader = DeviceBatchLoader(val_set, batch_size, shuffle=False, drop_last=True, workers=workers, device=device,
+                                   cache=built[-1] if cache is not None else None)
     stepper = TrainStepper(model, lr=learning_rate, amp=amp, surface_classes=surface.classes if surface is not None else None,
                            ema=ema, loss=loss, **({} if distill is None else {"distill": distill}),
                            **({} if optimizer is None else {"optimizer": optimizer}))
@@ -520,6 +584,9 @@ def run_training(model, device, train_set, val_set, *, epochs: int, batch_size: 
     if stepper.ema is not None and history:
         history[-1]["ema_state_dict"] = stepper.ema_state_dict()
     stepper.close()
+    for c in built:
+        if c is not None:
+            c.close()
     return history
 
 
@@ -610,7 +677,7 @@ def main(argv=None) -> int:
                            workers=args.workers, log=logging.info, pred_dir=args.pred_dir, metrics=args.metrics,
                            augment=augment, surface=args.surface_loss, elastic=elastic, ema=args.ema,
                            save_state=args.save_state, resume=resume, record=record, loss=args.loss,
-                           crop=args.crop, tile=args.tile, distill=args.distill, optimizer=args.optimizer)
+                           crop=args.crop, tile=args.tile, distill=args.distill, optimizer=args.optimizer, cache=args.cache)
     path = f"model_epoch{args.epochs}.pth"
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)                # train.py:220
     logging.info(f"Model saved to {path}")

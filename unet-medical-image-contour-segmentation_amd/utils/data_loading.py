@@ -234,12 +234,19 @@ class DeviceBatchLoader:
     `crop`: a utils.crop.BatchCrop (patch training).  A batch's raw items are then collated and prepared one decoded shape
     (and turn parity, and scale) at a time instead of as one stack, so the items of a batch may differ in size; every prepared
     item is cropped on the device (the host-item fallback too) and the crop batch is what `augment` receives.  None (the
-    default) changes nothing."""
+    default) changes nothing.
+    `cache`: a utils.dataset_cache.DatasetCache built on the same `ds`, or True to build one here with the loader's `workers` and
+    `device` (a dataset that does not decode to 8-bit is then served through the host path as without it).  With a cache an
+    epoch starts no thread, decodes nothing and reads no file: a batch's uint8 pixels are cut from the cache's device arena
+    (csrc/cache.hip) and go through the same prepare, `crop` and `augment` stages, so the batches are the uncached loader's bit
+    for bit.  The cache holds decoded pixels, so host_rescale=True with one is an error.  None (the default) changes nothing."""
 
     def __init__(self, ds, batch_size: int = 1, shuffle: bool = False, drop_last: bool = False, seed=None, workers: int = 8,
-                 device=None, prefetch: int = 2, host_rescale: bool = False, augment=None, crop=None):
+                 device=None, prefetch: int = 2, host_rescale: bool = False, augment=None, crop=None, cache=None):
         if batch_size < 1 or workers < 1 or prefetch < 1:
             raise ValueError("DeviceBatchLoader: batch_size, workers and prefetch must be positive")
+        if cache is not None and host_rescale:
+            raise ValueError("DeviceBatchLoader: host_rescale=True cannot be combined with a cache (it holds decoded pixels)")
         self.ds, self.batch_size, self.shuffle, self.drop_last = ds, int(batch_size), bool(shuffle), bool(drop_last)
         self.seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
         self.workers, self.prefetch, self.device = int(workers), int(prefetch), device
@@ -250,6 +257,22 @@ class DeviceBatchLoader:
         self.host_rescale = bool(host_rescale)     # True: Pillow rescales in the decode threads (the earlier path; benchmarks)
         self.augment = augment
         self.crop = crop
+        self.cache = None
+        if cache is True:
+            from .dataset_cache import DatasetCache
+            try:
+                self.cache = DatasetCache(ds, device=device, workers=self.workers)
+            except TypeError as e:
+                import logging
+                logging.info(f"DeviceBatchLoader: {e}; serving ds[i] through the host path")
+                self.host_items = True
+        elif cache is not None:
+            from .dataset_cache import DatasetCache
+            if not isinstance(cache, DatasetCache):
+                raise ValueError(f"DeviceBatchLoader: cache is a DatasetCache, True or None, got {cache!r}")
+            if cache.ds is not ds:
+                raise ValueError("DeviceBatchLoader: the cache was built on another dataset")
+            self.cache = cache
 
     def epoch_order(self, epoch: int) -> List[int]:
         n = len(self.ds)
@@ -323,6 +346,15 @@ class DeviceBatchLoader:
         self.orders.append(order)
         batches = self.batches_of(order)
         dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.cache is not None:                         # no pool, no decode: gather, then the stages below as they are
+            for idx in batches:
+                if self.crop is not None:
+                    out = self.crop(self._prepared_items(self.cache.gather_groups(idx), dev), epoch, idx)
+                else:
+                    raw = self.cache.gather(idx)
+                    out = prepare_batch_device(raw["image_u8"], raw["mask_u8"], raw["turns"], device=dev, scale=raw["scale"])
+                yield out if self.augment is None else self.augment(out, epoch, idx)
+            return
         with ThreadPoolExecutor(self.workers) as items_pool, ThreadPoolExecutor(self.prefetch) as batch_pool:
             def submit(idx):
                 if self.crop is not None:
